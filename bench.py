@@ -11,7 +11,11 @@ PCIe-inclusive rate).  At N GPUs every rank verifies its own 1M batch (weak
 scaling, no data-path collective); the per-rank valid counts are summed with one
 int64 all-reduce after the timed region (the tally exchange of SURVEY.md §8e).
 
-Extra JSON fields:
+A plain run sets up, warms up, times the steps and prints the C2 line; `--dump-outputs DIR` also
+writes the last timed step's decisions (DIR/decisions.npy).  Everything below takes runs of its
+own and is measured only with `--full` (the fields are null in a plain run).
+
+Extra JSON fields (`--full`):
   roofline      integer-VALU roofline of the verify kernel (HBM traffic ~212 B/verify
                 is negligible; MFMA has no 32x32->64 integer path): achieved
                 v_mad_i64_i32 per second = verifies/s(kernel time) x mads/verify,
@@ -103,13 +107,18 @@ def mads_keyset_main(b_bits: int = 24, a_bits: int = 8) -> int:
 MADS_KEYSET_MAIN = mads_keyset_main(16)
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1,
                     help="GPUs of this node; without a torchrun environment bench.py starts N ranks itself")
     ap.add_argument("--steps", type=int, default=200)  # ~2 s timed: long enough for an smi busy sample
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--sigs", type=int, default=1 << 20, help="signatures per GPU (C2: 2^20)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's decisions as DIR/decisions.npy (float32, one per signature)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the C2 line: roofline, CPU baselines, key-cached C2, C1, C3, C4, "
+                         "C5, ZIP-215 (the --no-* and leg-size options below apply to these)")
     ap.add_argument("--cpu-sample", type=int, default=150_000, help="signatures timed on the 1-thread CPU baseline")
     ap.add_argument("--openssl-sample", type=int, default=60_000, help="signatures timed on the OpenSSL anchor")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -125,7 +134,27 @@ def parse():
     ap.add_argument("--c3-headers", type=int, default=10_000)
     ap.add_argument("--mix", choices=["c2", "c5"], default="c2",
                     help="c5: 1%% of the batch replaced by edge-case / invalid tuples (BASELINE C5)")
-    return ap.parse_args()
+    return ap.parse_args(argv)
+
+
+DUMP_MAX_BYTES = 64_000_000  # --dump-outputs: all files of one run together, headers included
+
+
+def dump_outputs(path, decisions, rank=0, world=1, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: what a caller of the timed path receives — the uint8 decision per signature
+    that verify_device left in `out` in the last timed step — as float32 in <path>/decisions.npy
+    (decisions_rank<r>.npy at N > 1).  A batch over this rank's share of `max_bytes` is written as a
+    fixed sample (seed 0, ascending indices), with the indices beside it as float64."""
+    os.makedirs(path, exist_ok=True)
+    name = "decisions" if world == 1 else "decisions_rank%d" % rank
+    dec = np.asarray(decisions).reshape(-1)
+    share = max_bytes // world - 256  # two .npy headers of 128 B
+    if dec.size * 4 > share:
+        keep = max(1, share // 12)  # 4 B decision + 8 B index per sampled signature
+        idx = np.sort(np.random.default_rng(0).choice(dec.size, size=keep, replace=False))
+        np.save(os.path.join(path, name + "_index.npy"), idx.astype(np.float64))
+        dec = dec[idx]
+    np.save(os.path.join(path, name + ".npy"), dec.astype(np.float32))
 
 
 def spawn_ranks(n: int) -> int:
@@ -250,23 +279,26 @@ def main():
         valid_all, n_all = valid, n
     total = n_all * args.steps
     value = total / elapsed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, d_out.cpu().numpy(), rank, world)
 
     # ---- the dominant kernel's roofline, read right after the C2 timed region (rank 0): the
     # lattice step's window statistics of THIS batch (later legs' seam calls reset them) and one
     # extra untimed pass with live per-kernel HIP-event timing
     roof = peak = None
-    if rank == 0:
+    if args.full and rank == 0:
         roof, peak = roofline_leg(eng, step, dev, n, offs, kernel_ms, args.no_peak)
 
     # ---- C4 on every rank (weak scaling: c4_blocks per GPU, contiguous heights, RCCL tallies)
     c4 = None
-    if not args.no_c4:
+    if args.full and not args.no_c4:
         c4 = c4_shard(eng, coll, args.c4_blocks, rank, world)
 
     result = None
     if rank == 0:
+        side = args.full and world == 1  # the rank-0 legs beside the C2 line
         cpu = cpu_all = None
-        if not args.no_cpu_baseline and world == 1:
+        if side and not args.no_cpu_baseline:
             cpu = cpu_baseline(d_pub, d_sig, msgs, offs, min(args.cpu_sample, n), d_out,
                                min(args.openssl_sample, n))
             cpu_all = cpu_baseline_threads(d_pub, d_sig, msgs, offs, n, d_out, cpu["value"], value)
@@ -276,19 +308,19 @@ def main():
                                 "extrapolated_value": cpu_all["all_cores_extrapolated"]["value"],
                                 "gpu_speedup_vs_all_cores": cpu_all["all_cores_extrapolated"]["gpu_speedup"]}
         keyset = None
-        if not args.no_keyset and world == 1:
+        if side and not args.no_keyset:
             keyset = c2_keyset(eng, dev, torch_stream, n, args.steps, args.warmup, peak)
         c1 = None
-        if not args.no_c1 and world == 1:
+        if side and not args.no_c1:
             c1 = c1_latency(eng, args.c1_reps, not args.no_cpu_baseline)
         c5 = None
-        if not args.no_c5 and world == 1 and args.mix == "c2":
+        if side and not args.no_c5 and args.mix == "c2":
             c5 = c5_leg(eng, dev, torch_stream, d_pub, d_sig, d_msg, d_off, msgs, offs, n, args.steps // 10 + 1)
         zip_leg = None
-        if not args.no_zip215 and world == 1 and args.mix == "c2":
+        if side and not args.no_zip215 and args.mix == "c2":
             zip_leg = zip215_leg(eng, dev, torch_stream, d_pub, d_sig, d_msg, d_off, msgs, offs, n, args.steps // 10 + 1)
         c3 = None
-        if not args.no_c3 and world == 1:
+        if side and not args.no_c3:
             c3 = c3_leg(eng, args.c3_headers)
         result = {
             "metric": "ed25519 verifies/sec at %d/8 MI355X" % world,

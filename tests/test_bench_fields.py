@@ -74,6 +74,36 @@ def test_archived_pmc_only_for_this_trees_kernels(tmp_path, monkeypatch):
     assert bench.pmc_clock("verify_main_hs_kernel") == 2.0
 
 
+def test_plain_run_is_the_default_and_full_is_an_option():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, None)
+    a = bench.parse(["--full", "--no-c4", "--dump-outputs", "d"])
+    assert a.full and a.no_c4 and a.dump_outputs == "d"
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """A batch within the size limit is written whole as float32; a larger one as the same seeded
+    sample every time, with its indices, inside the limit."""
+    import numpy as np
+    dec = (np.arange(1000) % 7 != 1).astype(np.uint8)
+    bench.dump_outputs(str(tmp_path / "a"), dec)
+    got = np.load(tmp_path / "a" / "decisions.npy")
+    assert got.dtype == np.float32 and (got == dec).all()
+    assert os.listdir(tmp_path / "a") == ["decisions.npy"]
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), dec, max_bytes=4096)
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert files == ["decisions.npy", "decisions_index.npy"]
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in files) <= 4096
+    idx = np.load(tmp_path / "b" / "decisions_index.npy")
+    got = np.load(tmp_path / "b" / "decisions.npy")
+    assert idx.dtype == np.float64 and got.dtype == np.float32 and 300 <= len(idx) < 1000
+    assert (np.diff(idx) > 0).all() and (got == dec[idx.astype(np.int64)]).all()
+    assert (idx == np.load(tmp_path / "c" / "decisions_index.npy")).all()
+    bench.dump_outputs(str(tmp_path / "r"), dec, rank=1, world=2)
+    assert os.listdir(tmp_path / "r") == ["decisions_rank1.npy"]
+
+
 def test_kernel_digest_tracks_device_sources(tmp_path):
     """The digest covers kernels.hip and every csrc header, nothing else."""
     from tmed.srcdigest import kernel_src_digest

@@ -15,7 +15,7 @@ for r in $(seq 1 ${ROUNDS:-3}); do
       cur) lib=tendermint-fork_amd/lib/libtmed25519_hip.so;;
       *) lib=tendermint-fork_amd/lib_var/$v/libtmed25519_hip.so;;
     esac
-    env ${envs//,/ } TMED_LIB=$lib timeout -k 10 300 python bench.py --steps ${STEPS:-20} --no-cpu-baseline --no-c1 ${BENCH_ARGS:---no-keyset} > $OUT/$v.$r.log 2>&1; rc=$?
+    env ${envs//,/ } TMED_LIB=$lib timeout -k 10 300 python bench.py --full --steps ${STEPS:-20} --no-cpu-baseline --no-c1 ${BENCH_ARGS:---no-keyset} > $OUT/$v.$r.log 2>&1; rc=$?
     line=$(grep '^{' $OUT/$v.$r.log | tail -1)
     echo "$r $v rc=$rc $(echo "$line" | python3 -c 'import json,sys
 try:

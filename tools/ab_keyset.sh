@@ -8,7 +8,7 @@ mkdir -p $OUT
 for r in $(seq 1 ${ROUNDS:-3}); do
   for v in "$@"; do
     if [ "$v" = cur ]; then lib=tendermint-fork_amd/lib/libtmed25519_hip.so; else lib=tendermint-fork_amd/lib_var/$v/libtmed25519_hip.so; fi
-    TMED_LIB=$lib timeout -k 10 300 python bench.py --steps 10 --no-cpu-baseline --no-c1 --no-peak > $OUT/$v.$r.log 2>&1; rc=$?
+    TMED_LIB=$lib timeout -k 10 300 python bench.py --full --steps 10 --no-cpu-baseline --no-c1 --no-peak > $OUT/$v.$r.log 2>&1; rc=$?
     line=$(tail -1 $OUT/$v.$r.log)
     echo "$r $v rc=$rc $(echo "$line" | python3 -c 'import json,sys
 try:

@@ -3,6 +3,7 @@
 # own time limit; a fault/abort/timeout (124/134/137/139) ends the session there.
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
+R=$PWD
 mkdir -p gpurun_out
 OUT=gpurun_out
 fatal() { case "$1" in 124|134|137|139) return 0;; *) return 1;; esac; }
@@ -17,11 +18,11 @@ for s in $STEPS; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; rc=$?
       echo "smoke rc=$rc" | tee -a $OUT/smoke.log ;;
     bench)
-      t0=$(date +%s); timeout -k 10 600 python bench.py > $OUT/bench.log 2>&1; rc=$?; echo "bench wall $(( $(date +%s) - t0 )) s" >> $OUT/bench.log
+      t0=$(date +%s); timeout -k 10 600 python bench.py --full > $OUT/bench.log 2>&1; rc=$?; echo "bench wall $(( $(date +%s) - t0 )) s" >> $OUT/bench.log
       echo "bench rc=$rc" | tee -a $OUT/bench.log; tail -1 $OUT/bench.log ;;
     prof)
       cd /tmp && export TMPDIR=/tmp
-      timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/$OUT/prof -o run --output-format csv -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline ${PROF_ARGS:-} > $GRAFT_REPO_ROOT/$OUT/prof.log 2>&1; rc=$?
+      timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $R/$OUT/prof -o run --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline ${PROF_ARGS:-} > $R/$OUT/prof.log 2>&1; rc=$?
       cd $GRAFT_REPO_ROOT; echo "prof rc=$rc" | tee -a $OUT/prof.log ;;
     profc2)  # the C2 leg alone: every main-kernel launch is the full batch (its rocprof average = the roofline's)
       cd /tmp && export TMPDIR=/tmp
@@ -56,7 +57,7 @@ for s in $STEPS; do
       IFS='|' read -ra SETS <<< "$PMC_SETS"
       for ctr in "${SETS[@]}"; do
         tag=$(echo $ctr | tr ' ' '_')
-        timeout -s KILL 120 rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $GRAFT_REPO_ROOT/$OUT/pmc_$tag -o run -- python3 $GRAFT_REPO_ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline ${PMC_ARGS---no-peak} --c1-reps 50 --no-c4 --no-c5 --no-zip215 > $GRAFT_REPO_ROOT/$OUT/pmc_$tag.log 2>&1; rc=$?
+        timeout -s KILL 120 rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $R/$OUT/pmc_$tag -o run -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline ${PMC_ARGS---no-peak} --c1-reps 50 --no-c4 --no-c5 --no-zip215 > $R/$OUT/pmc_$tag.log 2>&1; rc=$?
         echo "pmc $ctr rc=$rc" | tee -a $GRAFT_REPO_ROOT/$OUT/pmc.log
         if fatal $rc; then break; fi
       done
