@@ -6,12 +6,21 @@ hashing either side of signature verification in the light client and blocksync:
            untrusted set of every header: the C3 shape)
   headers  Header.Hash for 100,000 headers (light/verifier.go:237, blockchain/v0/reactor.go:359)
   partset  PartSet roots of 256 blocks x 1 MiB in 64 KiB parts (reactor.go:359-361 MakePartSet)
+  commit_hash  Commit.Hash for 1,000 commits x 10,000 signatures from packed arrays
+           (types/block.go:894-912, recomputed per block by Block.ValidateBasic, :55-106)
+  txs_hash     Data.Hash for 1,000 blocks x 2,000 transactions of 250 B (types/block.go:1004-1012)
+
+The last two also run the only route there was before tmed_commit_hashes / tmed_txs_hashes:
+the leaves built on the host (the CommitSig protos marshalled by compiled code, shim/go_marshal.cpp;
+the transaction digests by hashlib) and passed through tmed_merkle_roots, in the same run, with
+both rates and their ratio in the line.  --legs a,b,... runs a subset.
 
 Each line: objects/s and hashed bytes/s end to end through the C ABI (host buffers in, roots
 out: staging + H2D + kernels + D2H), next to the same work on one host core with hashlib
 (OpenSSL SHA-256) through oracle/merkle.py on a bounded sample ("port", cpu_baseline only)."""
 from __future__ import annotations
 
+import argparse
 import hashlib
 import json
 import os
@@ -46,15 +55,130 @@ def cpu_rate(fn, items, budget_s=3.0):
     return (n // 2) / dt, n // 2
 
 
+LEGS = ("valset", "headers", "partset", "commit_hash", "txs_hash")
+
+
+def commit_hash_leg(eng, TM, rng, C=1000, V=10_000):
+    """Commit.Hash from packed arrays (one absent CommitSig in 50) vs host marshal + tmed_merkle_roots."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import blockhash_cases as B  # the restatement (checker only)
+    from tmed import gomarshal as G
+    N = C * V
+    flags = np.full(N, 2, np.uint8)
+    addrs = rng.integers(0, 256, (N, 20), dtype=np.uint8)
+    alens = np.full(N, 20, np.uint32)
+    sec = (1_700_000_000 + np.arange(N, dtype=np.int64) // V)
+    nanos = rng.integers(0, 1_000_000_000, N, dtype=np.int32)
+    sigs = rng.integers(0, 256, (N, 64), dtype=np.uint8)
+    slens = np.full(N, 64, np.uint32)
+    absent = np.arange(7, N, 50)
+    flags[absent], alens[absent], slens[absent] = 1, 0, 0
+    sec[absent], nanos[absent] = B.ZERO_TIME_SECONDS, 0
+    sigs[absent] = 0
+    off = (np.arange(C + 1, dtype=np.int64) * V)
+    batch = TM.commit_hashes_packed(eng, flags, addrs, sec, nanos, sigs, slens, off, alens)  # structs built once
+    kms = []
+
+    def new():
+        out, ok = batch.run(eng)
+        kms.append(eng.last_kernel_ms())
+        return out.copy(), ok.copy()
+
+    dt_new, (got, ok) = timed(new, reps=3)
+    assert ok.all()
+    buf, boff = np.empty(109 * N + 8, np.uint8), np.empty(N + 1, np.uint64)
+    tree_off = off.astype(np.uint32)
+    tm = []
+
+    def old():
+        t = time.perf_counter()
+        G.marshal_commitsigs(flags, addrs, sec, nanos, sigs, slens, alens, out=buf, out_off=boff)
+        tm.append(time.perf_counter() - t)
+        return TM.merkle_roots_packed(eng, buf, boff, tree_off)
+
+    dt_old, ref = timed(old, reps=3)
+    assert (got == ref).all(), "device-encoded roots != host-marshalled roots"
+    for c in (0, C - 1):
+        s = [(int(flags[i]), bytes(addrs[i, :alens[i]]), int(sec[i]), int(nanos[i]), bytes(sigs[i, :slens[i]]))
+             for i in range(c * V, (c + 1) * V)]
+        assert bytes(got[c]) == B.commit_hash(s)
+    return {"metric": "Commit.Hash commits/s (10,000 signatures)", "value": round(C / dt_new, 1), "unit": "commits/s",
+            "signatures_per_s": round(N / dt_new, 1), "seconds": round(dt_new, 4),
+            "leaf_kernel_ms": round(min(kms[1:]), 3),
+            "note": "C call from packed arrays: host pack into pinned staging + H2D + kernels + D2H",
+            "host_marshal_route": {"value": round(C / dt_old, 1), "unit": "commits/s", "seconds": round(dt_old, 4),
+                                   "marshal_seconds": round(min(tm[1:]), 4),
+                                   "kind": "CommitSig protos marshalled on the host (compiled, OpenMP) + "
+                                           "tmed_merkle_roots"},
+            "ratio_vs_host_marshal_route": round(dt_old / dt_new, 2),
+            "config": {"workload": "commit_hash: %d commits x %d signatures" % (C, V)}}
+
+
+def txs_hash_leg(eng, TM, rng, NB=1000, NT=2000, SZ=250):
+    """Data.Hash from packed transactions vs hashlib digests + tmed_merkle_roots."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import blockhash_cases as B  # the restatement (checker only)
+    L = NB * NT
+    data = rng.integers(0, 256, L * SZ + 8, dtype=np.uint8)
+    tx_off = (np.arange(L + 1, dtype=np.uint64) * SZ)
+    block_off = (np.arange(NB + 1) * NT).astype(np.uint32)
+    kms = []
+
+    def new():
+        out = TM.txs_hashes_packed(eng, data, tx_off, block_off)
+        kms.append(eng.last_kernel_ms())
+        return out
+
+    dt_new, got = timed(new, reps=3)
+    mv = memoryview(data)
+    leaf_off = (np.arange(L + 1, dtype=np.uint64) * 32)
+    th = []
+
+    def old():
+        t = time.perf_counter()
+        sha = hashlib.sha256
+        digests = np.frombuffer(b"".join([sha(mv[i * SZ:(i + 1) * SZ]).digest() for i in range(L)]) + bytes(8), np.uint8)
+        th.append(time.perf_counter() - t)
+        return TM.merkle_roots_packed(eng, digests, leaf_off, block_off)
+
+    dt_old, ref = timed(old, reps=1)
+    assert (got == ref).all(), "device-hashed roots != host-digest roots"
+    for b in (0, NB - 1):
+        assert bytes(got[b]) == B.txs_hash([bytes(mv[i * SZ:(i + 1) * SZ]) for i in range(b * NT, (b + 1) * NT)])
+    return {"metric": "Data.Hash blocks/s (2,000 transactions of 250 B)", "value": round(NB / dt_new, 1),
+            "unit": "blocks/s", "tx_bytes_per_s": round(L * SZ / dt_new, 1), "seconds": round(dt_new, 4),
+            "leaf_kernel_ms": round(min(kms[1:]), 3),
+            "note": "C call from packed transactions: H2D + kernels + D2H",
+            "host_digest_route": {"value": round(NB / dt_old, 1), "unit": "blocks/s", "seconds": round(dt_old, 4),
+                                  "hashlib_seconds": round(min(th[1:]), 4),
+                                  "kind": "hashlib SHA-256 per transaction (one core) + tmed_merkle_roots"},
+            "ratio_vs_host_digest_route": round(dt_old / dt_new, 2),
+            "config": {"workload": "txs_hash: %d blocks x %d transactions x %d B" % (NB, NT, SZ)}}
+
+
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--legs", default=",".join(LEGS), help="comma-separated subset of: " + ", ".join(LEGS))
+    legs = [l for l in ap.parse_args().legs.split(",") if l]
+    unknown = [l for l in legs if l not in LEGS]
+    if unknown:
+        ap.error("unknown leg(s): " + ", ".join(unknown))
     sys.path.insert(0, ROOT)
     from oracle import merkle as M  # cpu_baseline leg only
     from tmed import Engine
     from tmed import merkle as TM
     eng = Engine(0)
     rng = np.random.default_rng(1)
-    res = []
+    runs = {"valset": lambda: valset_leg(eng, TM, M, rng), "headers": lambda: headers_leg(eng, TM, M),
+            "partset": lambda: partset_leg(eng, TM, M, rng), "commit_hash": lambda: commit_hash_leg(eng, TM, rng),
+            "txs_hash": lambda: txs_hash_leg(eng, TM, rng)}
+    for leg in LEGS:
+        if leg in legs:
+            print(json.dumps(runs[leg]()), flush=True)
+    eng.close()
 
+
+def valset_leg(eng, TM, M, rng):
     # valset: 10k x 175
     S, V = 10_000, 175
     pubs = rng.integers(0, 256, (S * V, 32), dtype=np.uint8)
@@ -65,12 +189,14 @@ def main():
     assert all(bytes(got[s]) == M.valset_hash(sets[s]) for s in range(8))
     cpu, m = cpu_rate(M.valset_hash, sets)
     leaf_b = S * V * 39
-    res.append({"metric": "ValidatorSet.Hash sets/s (175 validators)", "value": round(S / dt, 1), "unit": "sets/s",
-                "leaf_bytes_per_s": round(leaf_b / dt, 1), "seconds": round(dt, 4),
-                "cpu_baseline": {"value": round(cpu, 1), "unit": "sets/s", "cores": 1, "kind": "port",
-                                 "sample": "%d sets, hashlib SHA-256 via oracle/merkle.py" % m},
-                "config": {"workload": "f3 valset: %d sets x %d validators" % (S, V)}})
+    return {"metric": "ValidatorSet.Hash sets/s (175 validators)", "value": round(S / dt, 1), "unit": "sets/s",
+            "leaf_bytes_per_s": round(leaf_b / dt, 1), "seconds": round(dt, 4),
+            "cpu_baseline": {"value": round(cpu, 1), "unit": "sets/s", "cores": 1, "kind": "port",
+                             "sample": "%d sets, hashlib SHA-256 via oracle/merkle.py" % m},
+            "config": {"workload": "f3 valset: %d sets x %d validators" % (S, V)}}
 
+
+def headers_leg(eng, TM, M):
     # headers: 100k
     H = 100_000
     base = {"version_block": 11, "version_app": 1, "chain_id": "test_chain_id", "height": 1,
@@ -87,12 +213,14 @@ def main():
     dt, got = timed(lambda: hb.run(eng), reps=2)
     assert all(got[i] == M.header_hash(hs[i]) for i in range(0, H, 9973))
     cpu, m = cpu_rate(M.header_hash, hs)
-    res.append({"metric": "Header.Hash headers/s", "value": round(H / dt, 1), "unit": "headers/s",
-                "seconds": round(dt, 4), "note": "C call: host-side field encoding (C++) + H2D + kernels + D2H",
-                "cpu_baseline": {"value": round(cpu, 1), "unit": "headers/s", "cores": 1, "kind": "port",
-                                 "sample": "%d headers" % m},
-                "config": {"workload": "f3 headers: %d headers" % H}})
+    return {"metric": "Header.Hash headers/s", "value": round(H / dt, 1), "unit": "headers/s",
+            "seconds": round(dt, 4), "note": "C call: host-side field encoding (C++) + H2D + kernels + D2H",
+            "cpu_baseline": {"value": round(cpu, 1), "unit": "headers/s", "cores": 1, "kind": "port",
+                             "sample": "%d headers" % m},
+            "config": {"workload": "f3 headers: %d headers" % H}}
 
+
+def partset_leg(eng, TM, M, rng):
     # partset: 256 x 1 MiB
     B, SZ = 256, 1 << 20
     blocks = [rng.integers(0, 256, SZ, dtype=np.uint8).tobytes() for _ in range(B)]
@@ -101,15 +229,12 @@ def main():
     dt, got = timed(lambda: TM.partset_roots_packed(eng, data, off, 65536))
     assert all(bytes(got[b]) == M.partset_root(blocks[b], 65536) for b in range(4))
     cpu, m = cpu_rate(lambda b: M.partset_root(b, 65536), blocks)
-    res.append({"metric": "PartSet root bytes/s", "value": round(B * SZ / dt, 1), "unit": "B/s",
-                "blocks_per_s": round(B / dt, 1), "seconds": round(dt, 4),
-                "note": "end to end incl. %d MiB H2D over PCIe" % (B * SZ >> 20),
-                "cpu_baseline": {"value": round(cpu * SZ, 1), "unit": "B/s", "cores": 1, "kind": "port",
-                                 "sample": "%d blocks" % m},
-                "config": {"workload": "f3 partset: %d blocks x 1 MiB, 64 KiB parts" % B}})
-    for r in res:
-        print(json.dumps(r), flush=True)
-    eng.close()
+    return {"metric": "PartSet root bytes/s", "value": round(B * SZ / dt, 1), "unit": "B/s",
+            "blocks_per_s": round(B / dt, 1), "seconds": round(dt, 4),
+            "note": "end to end incl. %d MiB H2D over PCIe" % (B * SZ >> 20),
+            "cpu_baseline": {"value": round(cpu * SZ, 1), "unit": "B/s", "cores": 1, "kind": "port",
+                             "sample": "%d blocks" % m},
+            "config": {"workload": "f3 partset: %d blocks x 1 MiB, 64 KiB parts" % B}}
 
 
 if __name__ == "__main__":

@@ -489,6 +489,41 @@ int tmed_header_hashes(tmed_ctx *ctx, const tmed_header *headers, size_t n, uint
 int tmed_partset_roots(tmed_ctx *ctx, const uint8_t *data, const uint64_t *data_off, size_t n_blocks,
                        uint32_t part_size, uint8_t *roots);
 
+/*
+ * The two other hashes Block.ValidateBasic recomputes for every block (types/block.go:55-106;
+ * Evidence.Hash is a plain byte-slice tree: tmed_merkle_roots).
+ *
+ * tmed_commit_hashes: Commit.Hash() (types/block.go:894-912) for n commits =
+ * HashFromByteSlices over cs.ToProto().Marshal() of every CommitSig, encoded on the device from the
+ * flat arrays of tmed_commit (height, round and block_id are not hashed).  The CommitSig encoding is
+ * the reference's rule as derived from the generated marshaller
+ * (proto/tendermint/types/types.pb.go:1563-1596, gogoproto StdTime; fields in ascending order):
+ *     08 varint(flag)   only if flag != 0
+ *     12 len addr       only if len(addr) > 0
+ *     1a len ts         always; ts = [08 varint(uint64(seconds))] if seconds != 0,
+ *                                    [10 varint(nanos)] if nanos != 0
+ *     22 len sig        only if len(sig) > 0
+ * The reference holds no Commit.Hash known answer: the rule is pinned only by its size bound,
+ * MaxCommitSigBytes = 109 (types/block.go:591, types/block_test.go:260-274).
+ * out: n x 32 bytes.  ok[i] = 0 (out[i] zeroed, the other commits unaffected; the caller runs the Go
+ * method) where this struct cannot reproduce the hash: a sig_lens[j] > 64 or an address length
+ * other than 0 or 20 (the struct does not carry those bytes), or a timestamp the reference's
+ * Marshal rejects, so that Commit.Hash panics (seconds outside [-62135596800, 253402300800), nanos
+ * outside [0, 10^9)).  n_sigs == 0 gives SHA-256("") with ok = 1.  TMED_EINVAL: addresses == NULL
+ * with an address length of 20, or another array the commit's signatures need is NULL.
+ * Submitted blocksync windows are collected first, as by every seam call.
+ *
+ * tmed_txs_hashes: Data.Hash() = Txs.Hash() (types/block.go:1004-1012 -> types/tx.go:47-55) for
+ * n_blocks blocks: block b's transactions are indices [block_off[b], block_off[b+1]), transaction i
+ * is txs[tx_off[i] .. tx_off[i+1]); every leaf is SHA-256(tx), hashed on the device.  out:
+ * n_blocks x 32 bytes; a block without transactions gives SHA-256("").
+ *
+ * After either call tmed_last_kernel_ms reports the device time of its leaf kernel.
+ */
+int tmed_commit_hashes(tmed_ctx *ctx, const tmed_commit *commits, size_t n, uint8_t *out, uint8_t *ok);
+int tmed_txs_hashes(tmed_ctx *ctx, const uint8_t *txs, const uint64_t *tx_off, const uint32_t *block_off,
+                    size_t n_blocks, uint8_t *out);
+
 /* ------------------------------------------------- blocksync replay (f4) */
 
 /*

@@ -881,6 +881,11 @@ static int bs_drain(tmed_ctx *ctx) {
   return rc;
 }
 
+namespace tmed {
+int bs_collect_submitted(tmed_ctx *c) { return bs_drain(c); }
+void bs_release_collected(tmed_ctx *c) { bs_reap(c); }
+}  // namespace tmed
+
 // One window through the stream and back (every batch collected before returning).
 static int run_pipelined(tmed_ctx *ctx, const tmed_commit_request *reqs, size_t nb, size_t bsz, uint64_t keyset,
                          tmed_commit_result *out, const KcCall *kc) {

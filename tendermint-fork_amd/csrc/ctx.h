@@ -114,6 +114,11 @@ Keyset *find_keyset(tmed_ctx *c, uint64_t handle);
 struct KeyCacheDev;
 void keycache_destroy(tmed_ctx *c);
 void bs_destroy(tmed_ctx *c);  // commit.hip: the blocksync batch stream (before keycache_destroy)
+// The seam's rule for a call that is not itself a blocksync window: collect every batch of the
+// submitted windows first (ctx->mu held), and after the lock is dropped release the windows that
+// completed (their key-set cache pins take the lock).
+int bs_collect_submitted(tmed_ctx *c);
+void bs_release_collected(tmed_ctx *c);
 struct Lane;
 void lane_release(Lane &L);    // keyset.hip: the second kernel lane's stream and scratch
 bool lanes_on();               // keyset.hip: TMED_LANES != 1
@@ -269,6 +274,10 @@ struct tmed_ctx {
   BsStream *bs = nullptr;   // batches of submitted blocksync windows in flight (tmed_blocksync_submit)
   tmed::Lane lane1;         // the pipelined seam's second kernel lane (VoteStage::lane)
   tmed::DevBuf d_merkle_a, d_merkle_b, d_merkle_idx;  // Merkle level digests (ping-pong) + level indexes
+  // tmed_commit_hashes (merkle.hip): the commits' arrays packed per kind (pinned) and their device
+  // copy, plus the roots.  Its own buffers: no batch of a submitted blocksync window ever holds them.
+  tmed::HostBuf h_csig;
+  tmed::DevBuf d_csig;
   tmed::DevBuf d_korder;  // key-grouped order of a key-cached batch: counts / cursors + permutation
   tmed::DevBuf d_zip;     // ZIP-215 batch mode scratch (zip215.hip zip_bufs: points, digits, sort, buckets)
   bool zip_dense = false; // ZIP-215: the last large chunk had failures (zip215.hip: decide the next one singly first)

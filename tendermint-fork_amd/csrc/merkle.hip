@@ -8,8 +8,11 @@
 //   types/validator.go:117-133      Validator.Bytes = SimpleValidator{PubKey, VotingPower} proto
 //   types/block.go:440-475          Header.Hash = HashFromByteSlices(14 encoded fields)
 //   types/part_set.go:166-194       PartSet root = ProofsFromByteSlices(part_size chunks) root
+//   types/block.go:894-912          Commit.Hash = HashFromByteSlices(CommitSig proto ...)
+//   types/block.go:1004-1012        Data.Hash = Txs.Hash (types/tx.go:47-55): leaves are SHA-256(tx)
 // Callers: light/verifier.go:183 (untrustedVals.Hash() per header), :237 (Header.Hash),
-// blockchain/v0/reactor.go:359-361 (MakePartSet + first.Hash() per block).
+// blockchain/v0/reactor.go:359-361 (MakePartSet + first.Hash() per block),
+// types/block.go:55-106 (Block.ValidateBasic recomputes LastCommit.Hash and Data.Hash per block).
 //
 // Device shape: one lane per leaf (SHA-256 of 0x00 || leaf), then one launch per tree level
 // over ALL trees of the call (one lane per output node).  The split-point recursion of
@@ -20,9 +23,12 @@
 #include <string.h>
 
 #include <algorithm>
+#include <new>
+#include <thread>
 #include <vector>
 
 #include "../../include/tmed25519.h"
+#include "commitsig_leaf.h"
 #include "ctx.h"
 #include "sha256.h"
 
@@ -94,6 +100,42 @@ __global__ __launch_bounds__(256) void valset_leaf_kernel(const uint8_t *__restr
   uint32_t st[8];
   sha256_init(st);
   sha256_compress(st, w);
+  store_digest(out + i, st);
+}
+
+// leafHash(CommitSig proto) for Commit.Hash: one lane per CommitSig of the call, read from the
+// commits' flat arrays (meta = flag | address length << 8 | signature length << 16; 16-byte loads
+// of the 64-byte signature row, dword loads of the 20-byte address row).  The encoding
+// (commitsig_leaf.h) is assembled directly as big-endian message words in registers.
+__global__ __launch_bounds__(256) void commit_leaf_kernel(const uint32_t *__restrict__ meta,
+                                                          const int64_t *__restrict__ seconds,
+                                                          const int32_t *__restrict__ nanos,
+                                                          const uint8_t *__restrict__ addrs,
+                                                          const uint8_t *__restrict__ sigs, uint32_t n,
+                                                          Digest *__restrict__ out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t m = meta[i];
+  uint32_t w[32], st[8];
+  const uint32_t len = commitsig_leaf_words(w, m & 0xffu, (m >> 8) & 0xffu, seconds[i], nanos[i], (m >> 16) & 0xffu,
+                                            addrs + 20 * (size_t)i, sigs + 64 * (size_t)i);
+  sha256_init(st);
+  sha256_compress(st, w);
+  if (len + 1 > 55) sha256_compress(st, w + 16);  // at most two blocks (static_assert in commitsig_leaf.h)
+  store_digest(out + i, st);
+}
+
+// leafHash(SHA-256(tx)) for Data.Hash (types/tx.go:47-55): one lane per transaction, the
+// transaction streamed as a part-set leaf is, then one block over its digest's state words.
+__global__ __launch_bounds__(256) void txs_leaf_kernel(const uint8_t *__restrict__ txs,
+                                                       const uint64_t *__restrict__ off, uint32_t n,
+                                                       Digest *__restrict__ out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t o0 = off[i], o1 = off[i + 1];
+  uint32_t h[8], st[8];
+  sha256_prefixed(h, 0, 0, txs + o0, (uint32_t)(o1 - o0));
+  sha256_leaf32(st, h);
   store_digest(out + i, st);
 }
 
@@ -239,9 +281,11 @@ void header_leaves(const tmed_header &h, std::vector<uint8_t> &leaves, std::vect
   }
 }
 
-// Leaves on the host -> roots on the host: the common driver of the byte-slice APIs.
+// Leaves on the host -> roots on the host: the common driver of the byte-slice APIs.  txs: the
+// byte slices are transactions (leaf = leafHash(SHA-256(tx)), txs_leaf_kernel, timed for
+// tmed_last_kernel_ms); else they are the leaves themselves.
 int roots_from_host_leaves(tmed_ctx *c, const uint8_t *leaves, const uint64_t *leaf_off, size_t L,
-                           const std::vector<uint32_t> &counts, uint8_t *roots) {
+                           const std::vector<uint32_t> &counts, uint8_t *roots, bool txs = false) {
   const size_t T = counts.size();
   const size_t bytes = leaf_off[L] - leaf_off[0];
   std::lock_guard<std::mutex> lk(c->mu);
@@ -256,13 +300,20 @@ int roots_from_host_leaves(tmed_ctx *c, const uint8_t *leaves, const uint64_t *l
   for (size_t i = 0; i <= L; i++) off[i] = leaf_off[i] - leaf_off[0];
   if (bytes) e = hipMemcpyAsync(c->d_msg.p, leaves + leaf_off[0], bytes, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipMemcpyAsync(c->d_off.p, off.data(), (L + 1) * 8, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && txs) e = hipEventRecord(c->ev0, s);
   if (e == hipSuccess && L) {
-    hipLaunchKernelGGL(merkle_leaf_kernel, dim3(blocks_for(L)), dim3(256), 0, s, (const uint8_t *)c->d_msg.p,
-                       (const uint64_t *)c->d_off.p, (uint32_t)L, (Digest *)c->d_merkle_a.p);
+    if (txs)
+      hipLaunchKernelGGL(txs_leaf_kernel, dim3(blocks_for(L)), dim3(256), 0, s, (const uint8_t *)c->d_msg.p,
+                         (const uint64_t *)c->d_off.p, (uint32_t)L, (Digest *)c->d_merkle_a.p);
+    else
+      hipLaunchKernelGGL(merkle_leaf_kernel, dim3(blocks_for(L)), dim3(256), 0, s, (const uint8_t *)c->d_msg.p,
+                         (const uint64_t *)c->d_off.p, (uint32_t)L, (Digest *)c->d_merkle_a.p);
     e = hipGetLastError();
   }
+  if (e == hipSuccess && txs) e = hipEventRecord(c->ev1, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   if (e != hipSuccess) return map_err(e);
+  if (txs) (void)hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1);
   int rc = reduce_trees(c, counts, L, (uint8_t *)c->d_out.p, s);
   if (rc != TMED_OK) return rc;
   e = hipMemcpyAsync(roots, c->d_out.p, T * 32, hipMemcpyDeviceToHost, s);
@@ -270,9 +321,198 @@ int roots_from_host_leaves(tmed_ctx *c, const uint8_t *leaves, const uint64_t *l
   return map_err(e);
 }
 
+// ---- Commit.Hash (types/block.go:894-912) ---------------------------------------------------
+// StdTimeMarshal's range (gogoproto timestamp.go validateTimestamp): outside it the reference's
+// Marshal fails and Commit.Hash panics.
+constexpr int64_t kMinTimeSeconds = -62135596800ll;  // 0001-01-01T00:00:00Z, Go's zero time
+constexpr int64_t kMaxTimeSeconds = 253402300800ll;  // 10000-01-01T00:00:00Z (exclusive)
+
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// The commits' arrays of one call, packed per kind: region offsets for N signatures.
+struct CsigLayout {
+  size_t sig, sec, meta, nanos, addr, roots, total;
+  CsigLayout(size_t N, size_t n_commits) {
+    sig = 0;
+    sec = align256(sig + 64 * N);
+    meta = align256(sec + 8 * N);
+    nanos = align256(meta + 4 * N);
+    addr = align256(nanos + 4 * N);
+    roots = align256(addr + 20 * N);
+    total = roots + 32 * n_commits;
+  }
+};
+
+// 0: this struct cannot reproduce the commit's hash (ok = 0); 1: it can; TMED_EINVAL: a missing array.
+int commit_scan(const tmed_commit &cm) {
+  const size_t n = cm.n_sigs;
+  if (n == 0) return 1;
+  if (!cm.flags || !cm.ts_seconds || !cm.ts_nanos) return TMED_EINVAL;
+  bool ok = true, any_addr = false, any_sig = false;
+  for (size_t j = 0; j < n; j++) {
+    const uint32_t sl = cm.sig_lens ? cm.sig_lens[j] : 64u;
+    const uint32_t al = cm.address_lens ? cm.address_lens[j] : 20u;
+    any_sig |= sl != 0;
+    any_addr |= al == 20;
+    ok &= sl <= 64 && (al == 0 || al == 20);
+    const int64_t s = cm.ts_seconds[j];
+    const int32_t ns = cm.ts_nanos[j];
+    ok &= s >= kMinTimeSeconds && s < kMaxTimeSeconds && ns >= 0 && ns < 1000000000;
+  }
+  if ((any_addr && !cm.addresses) || (ok && any_sig && !cm.sigs)) return TMED_EINVAL;
+  return ok ? 1 : 0;
+}
+
+// Commit cm's arrays into the staging regions at signature index base.
+void commit_pack(const tmed_commit &cm, uint8_t *h, const CsigLayout &lay, size_t base) {
+  const size_t n = cm.n_sigs;
+  if (n == 0) return;
+  if (cm.sigs) memcpy(h + lay.sig + 64 * base, cm.sigs, 64 * n);
+  memcpy(h + lay.sec + 8 * base, cm.ts_seconds, 8 * n);
+  memcpy(h + lay.nanos + 4 * base, cm.ts_nanos, 4 * n);
+  if (cm.addresses) memcpy(h + lay.addr + 20 * base, cm.addresses, 20 * n);
+  uint32_t *meta = reinterpret_cast<uint32_t *>(h + lay.meta) + base;
+  for (size_t j = 0; j < n; j++) {
+    const uint32_t sl = cm.sig_lens ? cm.sig_lens[j] : 64u;
+    const uint32_t al = cm.address_lens ? cm.address_lens[j] : 20u;
+    meta[j] = (uint32_t)cm.flags[j] | (al << 8) | (sl << 16);
+  }
+}
+
+// f(i) for i in [0, n) on up to `threads` host threads (contiguous shares).
+template <class F>
+void host_for(size_t n, unsigned threads, F &&f) {
+  if (threads <= 1 || n < 2) {
+    for (size_t i = 0; i < n; i++) f(i);
+    return;
+  }
+  threads = (unsigned)std::min<size_t>(threads, n);
+  std::vector<std::thread> ts;
+  ts.reserve(threads);
+  auto share = [&](unsigned t) {
+    for (size_t i = n * t / threads; i < n * (t + 1) / threads; i++) f(i);
+  };
+  for (unsigned t = 1; t < threads; t++) {
+    try {
+      ts.emplace_back(share, t);
+    } catch (...) {  // no thread to be had: the caller runs that share
+      share(t);
+    }
+  }
+  share(0);
+  for (auto &t : ts) t.join();
+}
+
+unsigned pack_threads(size_t sigs) {
+  if (sigs < (1u << 16)) return 1;
+  const char *v = getenv("TMED_HOST_THREADS");  // as the seam's host pool: 16 by default
+  const unsigned want = v ? (unsigned)std::max(1, atoi(v)) : 16u;
+  return std::min(want, std::max(1u, std::thread::hardware_concurrency()));
+}
+
+int commit_hashes_locked(tmed_ctx *c, const tmed_commit *commits, size_t n, const std::vector<uint32_t> &counts,
+                         const std::vector<size_t> &base, size_t N, uint8_t *out) {
+  (void)hipSetDevice(c->device);
+  hipStream_t s = c->stream;
+  const CsigLayout lay(N, n);
+  hipError_t e = c->h_csig.ensure(lay.total);
+  if (e == hipSuccess) e = c->d_csig.ensure(lay.total);
+  if (e == hipSuccess) e = c->d_merkle_a.ensure(std::max<size_t>(N, 1) * sizeof(Digest));
+  if (e != hipSuccess) return map_err(e);
+  uint8_t *h = (uint8_t *)c->h_csig.p, *d = (uint8_t *)c->d_csig.p;
+  host_for(n, pack_threads(N), [&](size_t i) {
+    if (counts[i]) commit_pack(commits[i], h, lay, base[i]);
+  });
+  if (N) {  // one copy per array kind
+    e = hipMemcpyAsync(d + lay.sig, h + lay.sig, 64 * N, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + lay.sec, h + lay.sec, 8 * N, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + lay.meta, h + lay.meta, 4 * N, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + lay.nanos, h + lay.nanos, 4 * N, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + lay.addr, h + lay.addr, 20 * N, hipMemcpyHostToDevice, s);
+  }
+  if (e == hipSuccess) e = hipEventRecord(c->ev0, s);
+  if (e == hipSuccess && N) {
+    hipLaunchKernelGGL(commit_leaf_kernel, dim3(blocks_for(N)), dim3(256), 0, s, (const uint32_t *)(d + lay.meta),
+                       (const int64_t *)(d + lay.sec), (const int32_t *)(d + lay.nanos), d + lay.addr, d + lay.sig,
+                       (uint32_t)N, (Digest *)c->d_merkle_a.p);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipEventRecord(c->ev1, s);
+  if (e != hipSuccess) return map_err(e);
+  int rc = reduce_trees(c, counts, N, d + lay.roots, s);
+  if (rc != TMED_OK) return rc;
+  e = hipMemcpyAsync(h + lay.roots, d + lay.roots, n * 32, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return map_err(e);
+  (void)hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1);
+  memcpy(out, h + lay.roots, n * 32);
+  return TMED_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int tmed_commit_hashes(tmed_ctx *c, const tmed_commit *commits, size_t n, uint8_t *out, uint8_t *ok) {
+  if (!c || (n && (!commits || !out || !ok))) return TMED_EINVAL;
+  if (n == 0) return TMED_OK;
+  int rc;
+  try {
+    std::vector<uint32_t> counts(n);
+    std::vector<size_t> base(n);
+    size_t N = 0, all = 0;
+    for (size_t i = 0; i < n; i++) all += commits[i].n_sigs;
+    std::vector<int> scan(n);
+    host_for(n, pack_threads(all), [&](size_t i) { scan[i] = commit_scan(commits[i]); });
+    for (size_t i = 0; i < n; i++) {
+      const int r = scan[i];
+      if (r < 0) return r;
+      ok[i] = (uint8_t)r;
+      base[i] = N;
+      if (commits[i].n_sigs > 0xffffffffu) return TMED_EINVAL;
+      counts[i] = r ? (uint32_t)commits[i].n_sigs : 0;  // a commit with ok = 0 contributes no leaves
+      N += counts[i];
+      if (N > 0xffffffffu) return TMED_EINVAL;
+    }
+    {
+      std::lock_guard<std::mutex> lk(c->mu);
+      rc = bs_collect_submitted(c);  // submitted blocksync windows are collected first (the seam's rule)
+      if (rc == TMED_OK) rc = commit_hashes_locked(c, commits, n, counts, base, N, out);
+    }
+    bs_release_collected(c);
+  } catch (const std::bad_alloc &) {
+    return TMED_ENOMEM;
+  } catch (...) {
+    return TMED_EINTERNAL;
+  }
+  if (rc != TMED_OK) return rc;
+  for (size_t i = 0; i < n; i++)
+    if (!ok[i]) memset(out + 32 * i, 0, 32);
+  return TMED_OK;
+}
+
+int tmed_txs_hashes(tmed_ctx *c, const uint8_t *txs, const uint64_t *tx_off, const uint32_t *block_off,
+                    size_t n_blocks, uint8_t *out) {
+  if (!c || (n_blocks && (!block_off || !out || !tx_off))) return TMED_EINVAL;
+  if (n_blocks == 0) return TMED_OK;
+  const size_t L = block_off[n_blocks];
+  if (block_off[0] != 0 || L > 0xffffffffu) return TMED_EINVAL;
+  try {
+    std::vector<uint32_t> counts(n_blocks);
+    for (size_t b = 0; b < n_blocks; b++) {
+      if (block_off[b + 1] < block_off[b]) return TMED_EINVAL;
+      counts[b] = block_off[b + 1] - block_off[b];
+    }
+    for (size_t i = 0; i < L; i++)
+      if (tx_off[i + 1] < tx_off[i] || tx_off[i + 1] - tx_off[i] > 0xffffffffu - 64) return TMED_EINVAL;
+    if (L && tx_off[L] > tx_off[0] && !txs) return TMED_EINVAL;
+    return roots_from_host_leaves(c, txs, tx_off, L, counts, out, /*txs=*/true);
+  } catch (const std::bad_alloc &) {
+    return TMED_ENOMEM;
+  } catch (...) {
+    return TMED_EINTERNAL;
+  }
+}
 
 int tmed_merkle_roots(tmed_ctx *c, const uint8_t *leaves, const uint64_t *leaf_off, const uint32_t *tree_off,
                       size_t n_trees, uint8_t *roots) {

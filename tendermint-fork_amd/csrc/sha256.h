@@ -158,4 +158,19 @@ TMED_HD void sha256_inner(uint32_t st[8], const uint32_t l[8], const uint32_t r[
   sha256_compress(st, w);
 }
 
+// leafHash(x) = SHA-256(0x00 || x) of a 32-byte x held as state words (a transaction's digest,
+// types/tx.go:47-55): one block, 00 || x || 80 || zeros || bit length 33 * 8 = 264.
+TMED_HD void sha256_leaf32(uint32_t st[8], const uint32_t x[8]) {
+  uint32_t w[16];
+  w[0] = x[0] >> 8;
+#pragma unroll
+  for (int i = 1; i < 8; i++) w[i] = (x[i - 1] << 24) | (x[i] >> 8);
+  w[8] = (x[7] << 24) | 0x00800000u;
+#pragma unroll
+  for (int i = 9; i < 15; i++) w[i] = 0;
+  w[15] = 264;
+  sha256_init(st);
+  sha256_compress(st, w);
+}
+
 }  // namespace tmed

@@ -786,6 +786,67 @@ func (e *Engine) MerkleRoots(trees [][][]byte) ([][32]byte, error) {
 	return append([][32]byte(nil), out...), nil
 }
 
+// CommitHashes returns Commit.Hash() (types/block.go:894-912) of every commit
+// (tmed_commit_hashes: the CommitSig protos are encoded and hashed on the device from the flat
+// arrays).  ok[i] is false where those arrays cannot reproduce the hash (a signature longer than 64
+// bytes, an address of another length than 0 or 20) or where the reference's Marshal fails and Hash
+// panics (timestamp out of range): the caller runs commit.Hash() itself for those.
+func (e *Engine) CommitHashes(commits []*CommitData) ([][32]byte, []bool, error) {
+	n := len(commits)
+	if n == 0 {
+		return nil, nil, nil
+	}
+	a := e.getArena()
+	defer e.putArena(a)
+	cs := (*[1 << 26]C.tmed_commit)(a.alloc(uintptr(n) * unsafe.Sizeof(C.tmed_commit{})))[:n:n]
+	for i, c := range commits {
+		cs[i] = a.commitC(c, nil)
+	}
+	out := (*[1 << 26][32]byte)(a.alloc(uintptr(n) * 32))[:n:n]
+	okc := (*[1 << 30]C.uint8_t)(a.alloc(uintptr(n)))[:n:n]
+	if rc := C.tmed_commit_hashes(e.ctx, &cs[0], C.size_t(n), (*C.uint8_t)(unsafe.Pointer(&out[0])), &okc[0]); rc != 0 {
+		return nil, nil, errors.New(C.GoString(C.tmed_strerror(rc)))
+	}
+	ok := make([]bool, n)
+	for i := range ok {
+		ok[i] = okc[i] != 0
+	}
+	return append([][32]byte(nil), out...), ok, nil
+}
+
+// TxsHashes returns Data.Hash() = Txs.Hash() (types/block.go:1004-1012 -> types/tx.go:47-55) of
+// every block's transactions (tmed_txs_hashes: SHA-256 of each transaction and the tree over those
+// digests both run on the device).
+func (e *Engine) TxsHashes(blocks [][][]byte) ([][32]byte, error) {
+	nb := len(blocks)
+	if nb == 0 {
+		return nil, nil
+	}
+	var flat []byte
+	txOff := []uint64{0}
+	blockOff := []uint32{0}
+	for _, b := range blocks {
+		for _, tx := range b {
+			flat = append(flat, tx...)
+			txOff = append(txOff, uint64(len(flat)))
+		}
+		blockOff = append(blockOff, uint32(len(txOff)-1))
+	}
+	flat = append(flat, make([]byte, 8)...) // the device reader may touch the last dword
+	a := e.getArena()
+	defer e.putArena(a)
+	to := (*[1 << 26]C.uint64_t)(a.alloc(uintptr(len(txOff)) * 8))[:len(txOff):len(txOff)]
+	for i, v := range txOff {
+		to[i] = C.uint64_t(v)
+	}
+	out := (*[1 << 26][32]byte)(a.alloc(uintptr(nb) * 32))[:nb:nb]
+	if rc := C.tmed_txs_hashes(e.ctx, a.bytes(flat), &to[0], a.u32(blockOff), C.size_t(nb),
+		(*C.uint8_t)(unsafe.Pointer(&out[0]))); rc != 0 {
+		return nil, errors.New(C.GoString(C.tmed_strerror(rc)))
+	}
+	return append([][32]byte(nil), out...), nil
+}
+
 // VoteSignBytes returns Commit.VoteSignBytes for n votes of one commit (tmed_vote_sign_bytes;
 // types/block.go:807-810 -> types/vote.go:93-101): vote i has flag flags[i] and timestamp
 // (tsSec[i], tsNanos[i]).  The seam builds these itself (on the device); this is for callers and

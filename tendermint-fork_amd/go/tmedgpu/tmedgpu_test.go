@@ -9,6 +9,7 @@ package tmedgpu
 import (
 	"crypto/ed25519"
 	"crypto/rand"
+	"crypto/sha256"
 	"testing"
 )
 
@@ -123,5 +124,104 @@ func TestFailedSubmitIsNilSafe(t *testing.T) {
 	var p *PendingWindow // what BlocksyncSubmit returns with an error
 	if p.Results() != nil {
 		t.Fatal("a nil window has no results")
+	}
+}
+
+func uvarint(b []byte, v uint64) []byte {
+	for v >= 0x80 {
+		b = append(b, byte(v)|0x80)
+		v >>= 7
+	}
+	return append(b, byte(v))
+}
+
+// CommitSig.ToProto().Marshal() restated (proto/tendermint/types/types.pb.go:1563-1596, gogoproto
+// StdTime): the leaves Commit.Hash feeds to merkle.HashFromByteSlices (types/block.go:894-912).
+func commitSigBytes(c *CommitData, i int) []byte {
+	var b []byte
+	if c.Flags[i] != 0 {
+		b = uvarint(append(b, 0x08), uint64(c.Flags[i]))
+	}
+	if c.AddrLens[i] > 0 {
+		b = uvarint(append(b, 0x12), uint64(c.AddrLens[i]))
+		b = append(b, c.Addresses[20*i:20*i+int(c.AddrLens[i])]...)
+	}
+	var ts []byte
+	if c.TsSeconds[i] != 0 {
+		ts = uvarint(append(ts, 0x08), uint64(c.TsSeconds[i]))
+	}
+	if c.TsNanos[i] != 0 {
+		ts = uvarint(append(ts, 0x10), uint64(c.TsNanos[i]))
+	}
+	b = uvarint(append(b, 0x1a), uint64(len(ts)))
+	b = append(b, ts...)
+	if c.SigLens[i] > 0 {
+		b = uvarint(append(b, 0x22), uint64(c.SigLens[i]))
+		b = append(b, c.Sigs[64*i:64*i+int(c.SigLens[i])]...)
+	}
+	return b
+}
+
+// CommitHashes against MerkleRoots over the marshalled CommitSigs (the route a caller had before),
+// with an absent entry (no address, Go's zero time, no signature) and a commit the flat arrays
+// cannot carry (a 65-byte signature).
+func TestCommitHashesMatchMarshalledLeaves(t *testing.T) {
+	eng := engineOrSkip(t)
+	b := eng.NewBatch()
+	defer b.Release()
+	_, c, _ := signedCommit(t, eng, b, 175, -1)
+	c.Flags[3], c.AddrLens[3], c.SigLens[3] = 1, 0, 0
+	c.TsSeconds[3], c.TsNanos[3] = -62135596800, 0
+	_, long, _ := signedCommit(t, eng, b, 4, -1)
+	long.SigLens[2] = 65
+	leaves := make([][]byte, len(c.Flags))
+	for i := range leaves {
+		leaves[i] = commitSigBytes(c, i)
+	}
+	want, err := eng.MerkleRoots([][][]byte{leaves})
+	if err != nil {
+		t.Fatal(err)
+	}
+	got, ok, err := eng.CommitHashes([]*CommitData{c, long})
+	if err != nil {
+		t.Fatal(err)
+	}
+	if !ok[0] || got[0] != want[0] {
+		t.Fatalf("Commit.Hash: engine %x (ok %v), marshalled leaves %x", got[0], ok[0], want[0])
+	}
+	if ok[1] {
+		t.Fatal("a 65-byte signature is not carried by the flat arrays: ok must be false")
+	}
+}
+
+func TestTxsHashesMatchDigestLeaves(t *testing.T) {
+	eng := engineOrSkip(t)
+	blocks := [][][]byte{{}, {[]byte("tx")}, {}}
+	for i := 0; i < 129; i++ {
+		tx := make([]byte, i)
+		if _, err := rand.Read(tx); err != nil {
+			t.Fatal(err)
+		}
+		blocks[2] = append(blocks[2], tx)
+	}
+	trees := make([][][]byte, len(blocks))
+	for k, blk := range blocks {
+		for _, tx := range blk {
+			d := sha256.Sum256(tx)
+			trees[k] = append(trees[k], d[:])
+		}
+	}
+	want, err := eng.MerkleRoots(trees)
+	if err != nil {
+		t.Fatal(err)
+	}
+	got, err := eng.TxsHashes(blocks)
+	if err != nil {
+		t.Fatal(err)
+	}
+	for k := range blocks {
+		if got[k] != want[k] {
+			t.Fatalf("block %d: engine %x, digest leaves %x", k, got[k], want[k])
+		}
 	}
 }

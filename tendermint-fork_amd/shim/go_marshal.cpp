@@ -547,4 +547,52 @@ const tmed_commit_request *gm_marshal_requests(gm_ctx *c, gm_heap *h, size_t n, 
   return c->reqs.data();
 }
 
+// ---- CommitSig protobuf marshal (the host route to Commit.Hash through tmed_merkle_roots) --------
+// cs.ToProto().Marshal() (proto/tendermint/types/types.pb.go:1563-1596, gogoproto StdTime) of n
+// CommitSigs given as the flat arrays of tmed_commit: what a caller had to do on the host, per
+// signature, before tmed_commit_hashes encoded the leaves on the device (bench_merkle.py times it
+// as the other route).  Leaf i is written to out[out_off[i] .. out_off[i+1]); out needs 109 bytes
+// per signature (MaxCommitSigBytes, types/block.go:591).  Returns the total size.  sig_lens <= 64,
+// addr_lens in {0, 20}.  Two passes (sizes, then bytes), OpenMP over signatures.
+static inline size_t uvarint_len(uint64_t v) {
+  size_t n = 1;
+  while (v >= 0x80) { v >>= 7; n++; }
+  return n;
+}
+static inline uint8_t *put_uvarint(uint8_t *p, uint64_t v) {
+  while (v >= 0x80) { *p++ = (uint8_t)(v | 0x80); v >>= 7; }
+  *p++ = (uint8_t)v;
+  return p;
+}
+static inline size_t ts_len(int64_t sec, int32_t nanos) {
+  return (sec ? 1 + uvarint_len((uint64_t)sec) : 0) + (nanos ? 1 + uvarint_len((uint64_t)(int64_t)nanos) : 0);
+}
+
+uint64_t gm_marshal_commitsigs(size_t n, const uint8_t *flags, const uint32_t *addr_lens, const uint8_t *addrs,
+                               const int64_t *sec, const int32_t *nanos, const uint8_t *sigs, const uint32_t *sig_lens,
+                               uint8_t *out, uint64_t *out_off, int threads) {
+  if (threads < 1) threads = 1;
+#pragma omp parallel for schedule(static) num_threads(threads)
+  for (size_t i = 0; i < n; i++) {
+    const uint32_t al = addr_lens ? addr_lens[i] : 20u, sl = sig_lens ? sig_lens[i] : 64u;
+    out_off[i + 1] = (flags[i] ? 1 + uvarint_len(flags[i]) : 0) + (al ? 2 + al : 0) + 2 + ts_len(sec[i], nanos[i]) +
+                     (sl ? 2 + sl : 0);
+  }
+  out_off[0] = 0;
+  for (size_t i = 0; i < n; i++) out_off[i + 1] += out_off[i];
+#pragma omp parallel for schedule(static) num_threads(threads)
+  for (size_t i = 0; i < n; i++) {
+    const uint32_t al = addr_lens ? addr_lens[i] : 20u, sl = sig_lens ? sig_lens[i] : 64u;
+    uint8_t *p = out + out_off[i];
+    if (flags[i]) { *p++ = 0x08; p = put_uvarint(p, flags[i]); }
+    if (al) { *p++ = 0x12; *p++ = (uint8_t)al; memcpy(p, addrs + 20 * i, al); p += al; }
+    *p++ = 0x1a;
+    *p++ = (uint8_t)ts_len(sec[i], nanos[i]);
+    if (sec[i]) { *p++ = 0x08; p = put_uvarint(p, (uint64_t)sec[i]); }
+    if (nanos[i]) { *p++ = 0x10; p = put_uvarint(p, (uint64_t)(int64_t)nanos[i]); }
+    if (sl) { *p++ = 0x22; *p++ = (uint8_t)sl; memcpy(p, sigs + 64 * i, sl); p += sl; }
+  }
+  return out_off[n];
+}
+
 }  // extern "C"

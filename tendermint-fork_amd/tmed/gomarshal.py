@@ -42,6 +42,8 @@ def _l():
         l.gm_marshal_window.argtypes = [P, P, I64, P, P, SZ, ctypes.c_char_p, U32, P, P]
         l.gm_marshal_requests.restype = ctypes.POINTER(T._RequestC)
         l.gm_marshal_requests.argtypes = [P, P, SZ, P, P, P, P, P, P, ctypes.c_char_p, U32, P]
+        l.gm_marshal_commitsigs.restype = ctypes.c_uint64
+        l.gm_marshal_commitsigs.argtypes = [SZ, P, P, P, P, P, P, P, P, P, ctypes.c_int]
         _lib = l
     return _lib
 
@@ -131,6 +133,22 @@ class Marshal:
             self.free()
         except Exception:
             pass
+
+
+def marshal_commitsigs(flags, addresses, ts_seconds, ts_nanos, sigs, sig_lens=None, address_lens=None, out=None,
+                       out_off=None, threads: int | None = None):
+    """cs.ToProto().Marshal() of every CommitSig of the flat arrays, in compiled code: the leaves of
+    Commit.Hash as a caller had to build them on the host for tmed_merkle_roots.  Returns (out u8
+    buffer, out_off u64[n+1]); out (>= 109 n + 8 bytes) and out_off may be passed in to be reused."""
+    n = flags.shape[0]
+    if out is None:
+        out = np.empty(109 * n + 8, np.uint8)
+    if out_off is None:
+        out_off = np.empty(n + 1, np.uint64)
+    t = threads or int(os.environ.get("TMED_HOST_THREADS", "16"))
+    _l().gm_marshal_commitsigs(n, _p(flags), _p(address_lens), _p(addresses), _p(ts_seconds), _p(ts_nanos), _p(sigs),
+                               _p(sig_lens), _p(out), _p(out_off), t)
+    return out, out_off
 
 
 def results(n: int):

@@ -3,7 +3,9 @@
 (types/validator_set.go:347-353), ``Header.Hash`` (types/block.go:440-475) and the
 ``PartSet`` root (types/part_set.go:166-194), each over many objects per call through the
 C ABI (csrc/merkle.hip).  Same inputs and outputs as the Go functions, one list entry per
-object; ``Header.Hash``'s nil is ``None``."""
+object; ``Header.Hash``'s nil is ``None``.  ``Commit.Hash`` (types/block.go:894-912) and
+``Data.Hash`` (types/block.go:1004-1012 -> ``Txs.Hash``, types/tx.go:47-55), the two hashes
+``Block.ValidateBasic`` recomputes per block, are ``commit_hashes`` and ``txs_hashes``."""
 from __future__ import annotations
 
 import ctypes
@@ -44,6 +46,10 @@ def _bind():
         l.tmed_header_hashes.argtypes = [P, ctypes.POINTER(_HeaderC), SZ, P, P]
         l.tmed_partset_roots.restype = ctypes.c_int
         l.tmed_partset_roots.argtypes = [P, P, P, SZ, ctypes.c_uint32, P]
+        l.tmed_commit_hashes.restype = ctypes.c_int
+        l.tmed_commit_hashes.argtypes = [P, P, SZ, P, P]
+        l.tmed_txs_hashes.restype = ctypes.c_int
+        l.tmed_txs_hashes.argtypes = [P, P, P, P, SZ, P]
     return l
 
 
@@ -71,6 +77,20 @@ def merkle_roots(engine, trees: Sequence[Sequence[bytes]]) -> list:
     if rc != TMED_OK:
         raise TmedError(rc, "tmed_merkle_roots")
     return [bytes(r) for r in roots[:len(trees)]]
+
+
+def merkle_roots_packed(engine, data: np.ndarray, leaf_off: np.ndarray, tree_off: np.ndarray) -> np.ndarray:
+    """HashFromByteSlices of trees [tree_off[t], tree_off[t+1]) over leaves data[leaf_off[i] ..
+    leaf_off[i+1]) (u8 array with 8 spare bytes at its end, u64 offsets, u32 tree offsets)."""
+    n = tree_off.shape[0] - 1
+    roots = np.zeros((max(n, 1), 32), np.uint8)
+    if n <= 0:
+        return roots[:0]
+    rc = _bind().tmed_merkle_roots(engine._h, _p(data), _p(np.ascontiguousarray(leaf_off, np.uint64)),
+                                   _p(np.ascontiguousarray(tree_off, np.uint32)), n, _p(roots))
+    if rc != TMED_OK:
+        raise TmedError(rc, "tmed_merkle_roots")
+    return roots[:n]
 
 
 def valset_hashes_arrays(engine, pubkeys: np.ndarray, powers: np.ndarray, set_off: np.ndarray) -> np.ndarray:
@@ -165,3 +185,79 @@ def partset_roots(engine, blocks: Sequence[bytes], part_size: int = BLOCK_PART_S
     np.cumsum(np.asarray([len(b) for b in blocks], np.uint64), out=off[1:])
     data = np.frombuffer(b"".join(bytes(b) for b in blocks) + b"\0" * 8, np.uint8)
     return [bytes(r) for r in partset_roots_packed(engine, data, off, part_size)]
+
+
+class CommitHashBatch:
+    """Commits (tmed.types.Commit or PackedCommit) held as tmed_commit structs over their arrays,
+    built once (repeated timing of the C call alone)."""
+
+    def __init__(self, commits: Sequence):
+        from .types import _CommitC, _commit_c
+        n = self.n = len(commits)
+        self.keep = []
+        self.cs = (_CommitC * max(n, 1))()
+        for i, c in enumerate(commits):
+            self.cs[i] = _commit_c(c, self.keep)
+        self.out = np.zeros((max(n, 1), 32), np.uint8)
+        self.ok = np.zeros(max(n, 1), np.uint8)
+
+    def run(self, engine):
+        """(hashes u8[n,32], ok u8[n])"""
+        if self.n:
+            rc = _bind().tmed_commit_hashes(engine._h, ctypes.cast(self.cs, ctypes.c_void_p), self.n, _p(self.out),
+                                            _p(self.ok))
+            if rc != TMED_OK:
+                raise TmedError(rc, "tmed_commit_hashes")
+        return self.out[:self.n], self.ok[:self.n]
+
+
+def commit_hashes_packed(engine, flags, addresses, ts_seconds, ts_nanos, sigs, sig_lens, commit_off,
+                         address_lens=None):
+    """Commit.Hash of commits [commit_off[c], commit_off[c+1]) over flat signature arrays (flags u8[N],
+    addresses u8[N,20], ts_seconds i64[N], ts_nanos i32[N], sigs u8[N,64], sig_lens u32[N] or None,
+    address_lens u32[N] or None): a CommitHashBatch whose structs point into those arrays."""
+    from .types import BlockID, PackedCommit
+    off = np.asarray(commit_off, np.int64)
+    cs = []
+    for c in range(off.shape[0] - 1):
+        a, b = int(off[c]), int(off[c + 1])
+        sl = np.full(b - a, 64, np.uint32) if sig_lens is None else sig_lens[a:b]
+        cs.append(PackedCommit(0, 0, BlockID(), flags[a:b], addresses[a:b], ts_seconds[a:b], ts_nanos[a:b],
+                               sigs[a:b], sl, None if address_lens is None else address_lens[a:b]))
+    return CommitHashBatch(cs)
+
+
+def commit_hashes(engine, commits: Sequence) -> list:
+    """Commit.Hash() of every commit (tmed.types.Commit or PackedCommit); None where the flat arrays
+    cannot reproduce it (a signature longer than 64 bytes, an address of another length than 0 or
+    20) or the reference's Marshal fails and Hash panics (timestamp out of range): the caller
+    runs the Go method for those."""
+    out, ok = CommitHashBatch(commits).run(engine)
+    return [bytes(out[i]) if ok[i] else None for i in range(len(commits))]
+
+
+def txs_hashes_packed(engine, txs: np.ndarray, tx_off: np.ndarray, block_off: np.ndarray) -> np.ndarray:
+    """Data.Hash of blocks [block_off[b], block_off[b+1]) over transactions txs[tx_off[i] .. tx_off[i+1])
+    (u8 array, u64 offsets, u32 block offsets): an n_blocks x 32 array."""
+    n = block_off.shape[0] - 1
+    out = np.zeros((max(n, 1), 32), np.uint8)
+    if n <= 0:
+        return out[:0]
+    rc = _bind().tmed_txs_hashes(engine._h, _p(txs), _p(np.ascontiguousarray(tx_off, np.uint64)),
+                                 _p(np.ascontiguousarray(block_off, np.uint32)), n, _p(out))
+    if rc != TMED_OK:
+        raise TmedError(rc, "tmed_txs_hashes")
+    return out[:n]
+
+
+def txs_hashes(engine, blocks: Sequence[Sequence[bytes]]) -> list:
+    """Data.Hash() = Txs.Hash() of every block's transactions."""
+    if not blocks:
+        return []
+    flat = [bytes(t) for b in blocks for t in b]
+    tx_off = np.zeros(len(flat) + 1, np.uint64)
+    np.cumsum(np.asarray([len(t) for t in flat], np.uint64), out=tx_off[1:])
+    block_off = np.zeros(len(blocks) + 1, np.uint32)
+    np.cumsum(np.asarray([len(b) for b in blocks], np.uint32), out=block_off[1:])
+    data = np.frombuffer(b"".join(flat) + b"\0" * 8, np.uint8)
+    return [bytes(r) for r in txs_hashes_packed(engine, data, tx_off, block_off)]
