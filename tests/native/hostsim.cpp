@@ -223,12 +223,12 @@ void hostsim_verify_batch_hs16(const uint8_t *pub, const uint8_t *sig, const uin
   verify_batch_hs_impl(pub, sig, msgs, off, n, out, wins, nullptr, true);
 }
 
-// The lattice step alone: c, |d| (32-byte LE each), dneg, window count.
-int hostsim_halfsize_impl(const uint8_t *k32, uint8_t *c32, uint8_t *d32, int *dneg, int fast) {
+// The lattice step alone: c, |d| (32-byte LE each), dneg, window count (and the tight count).
+int hostsim_halfsize_impl(const uint8_t *k32, uint8_t *c32, uint8_t *d32, int *dneg, int fast, int *tight = nullptr) {
   uint32_t k[8], c[8], dm[8];
   load_words8(k, k32);
   bool neg;
-  const int W = fast ? sc_halfsize<true>(c, dm, neg, k) : sc_halfsize<false>(c, dm, neg, k);
+  const int W = fast ? sc_halfsize<true>(c, dm, neg, k, tight) : sc_halfsize<false>(c, dm, neg, k, tight);
   for (int i = 0; i < 32; i++) {
     c32[i] = (uint8_t)(c[i / 4] >> (8 * (i % 4)));
     d32[i] = (uint8_t)(dm[i / 4] >> (8 * (i % 4)));
@@ -243,6 +243,11 @@ int hostsim_halfsize(const uint8_t *k32, uint8_t *c32, uint8_t *d32, int *dneg) 
 
 int hostsim_halfsize_plain(const uint8_t *k32, uint8_t *c32, uint8_t *d32, int *dneg) {
   return hostsim_halfsize_impl(k32, c32, d32, dneg, 0);
+}
+
+// The same with the tight window count out (fast = 0: the reference loop).
+int hostsim_halfsize_tight(const uint8_t *k32, uint8_t *c32, uint8_t *d32, int *dneg, int *tight, int fast) {
+  return hostsim_halfsize_impl(k32, c32, d32, dneg, fast, tight);
 }
 
 void hostsim_verify_batch(const uint8_t *pub, const uint8_t *sig, const uint8_t *msgs, const uint32_t *off,
@@ -421,18 +426,47 @@ void hostsim_fe_op(int op, const uint8_t *a, const uint8_t *b, uint8_t *out) {
   to_bytes(out, wo);
 }
 
-// mul / sq / sq2 on raw limbs (signed 32-bit; the caller keeps them inside the documented input
-// bounds), the product's limbs and its canonical encoding out.
+// The single products on raw limbs (signed 32-bit; the caller keeps them inside the documented
+// input bounds), the product's limbs and its canonical encoding out.  op: 0 fe_mul, 1 fe_sq,
+// 2 fe_sq2, 3 fe_sqc.
 void hostsim_fe_raw(int op, const int32_t *a, const int32_t *b, int32_t *out_limbs, uint8_t *out) {
   fe fa, fb, fo;
   for (int i = 0; i < 10; i++) { fa.v[i] = a[i]; fb.v[i] = b[i]; }
   if (op == 0) fe_mul(fo, fa, fb);
   else if (op == 1) fe_sq(fo, fa);
+  else if (op == 3) fe_sqc(fo, fa);
   else fe_sq2(fo, fa);
   for (int i = 0; i < 10; i++) out_limbs[i] = fo.v[i];
   uint32_t wo[8];
   fe_to_words(wo, fo);
   to_bytes(out, wo);
+}
+
+// The two-product schedules on raw limbs, two operand sets in, both products out.  op: 4 fe_mul_x2,
+// 5 fe_sq_x2, 6 fe_sqc_x2, 7 fe_sq2_sq.  alias: 0 = separate outputs, 1 = each output is its own
+// first input, 2 = each output is its own last input, 3 = each output is the OTHER product's
+// first input.
+void hostsim_fe_raw_x2(int op, int alias, const int32_t *a0, const int32_t *b0, const int32_t *a1, const int32_t *b1,
+                       int32_t *out0, uint8_t *enc0, int32_t *out1, uint8_t *enc1) {
+  fe f0, g0, f1, g1, h0, h1;
+  for (int i = 0; i < 10; i++) { f0.v[i] = a0[i]; g0.v[i] = b0[i]; f1.v[i] = a1[i]; g1.v[i] = b1[i]; }
+  fe *r0 = &h0, *r1 = &h1;
+  const bool mul = op == 4;
+  if (alias == 1) { r0 = &f0; r1 = &f1; }
+  if (alias == 2) { r0 = mul ? &g0 : &f0; r1 = mul ? &g1 : &f1; }
+  if (alias == 3) { r0 = &f1; r1 = &f0; }
+  switch (op) {
+    case 4: fe_mul_x2(*r0, f0, g0, *r1, f1, g1); break;
+    case 5: fe_sq_x2(*r0, f0, *r1, f1); break;
+    case 6: fe_sqc_x2(*r0, f0, *r1, f1); break;
+    default: fe_sq2_sq(*r0, f0, *r1, f1); break;
+  }
+  uint32_t wo[8];
+  for (int i = 0; i < 10; i++) { out0[i] = r0->v[i]; out1[i] = r1->v[i]; }
+  fe_to_words(wo, *r0);
+  to_bytes(enc0, wo);
+  fe_to_words(wo, *r1);
+  to_bytes(enc1, wo);
 }
 
 // fe_pack256 / fe_unpack256 on raw limbs (the main kernel's table storage form): unpacked limbs
@@ -465,6 +499,30 @@ void hostsim_sha512(const uint8_t *m, uint32_t n, uint8_t *out) {
   uint32_t z[8] = {0}, h[16];
   sha512_stream(h, z, z, 0, m, n);
   for (int i = 0; i < 64; i++) out[i] = (uint8_t)(h[i / 4] >> (8 * (i % 4)));
+}
+
+// SHA-512(p0 || p1 || m) with npre = 0, 32 or 64 bytes of register prefix.
+void hostsim_sha512_pre(int npre, const uint8_t *p0, const uint8_t *p1, const uint8_t *m, uint32_t n, uint8_t *out) {
+  uint32_t w0[8], w1[8], h[16];
+  load_words8(w0, p0);
+  load_words8(w1, p1);
+  sha512_stream(h, w0, w1, npre, m, n);
+  for (int i = 0; i < 64; i++) out[i] = (uint8_t)(h[i / 4] >> (8 * (i % 4)));
+}
+
+int hostsim_sc_is_canonical(const uint8_t *s32) {
+  uint32_t s[8];
+  load_words8(s, s32);
+  return sc_is_canonical(s) ? 1 : 0;
+}
+
+void hostsim_sc_muladd(const uint8_t *a32, const uint8_t *b32, const uint8_t *c32, uint8_t *out) {
+  uint32_t a[8], b[8], c[8], r[8];
+  load_words8(a, a32);
+  load_words8(b, b32);
+  load_words8(c, c32);
+  sc_muladd(r, a, b, c);
+  to_bytes(out, r);
 }
 
 void hostsim_sc_reduce(const uint8_t *h64, uint8_t *out) {

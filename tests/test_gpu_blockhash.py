@@ -141,3 +141,74 @@ def test_commit_hash_equals_old_route_gpu(engine):
     sigs = B.cycle_sigs()[200:375]
     assert len(sigs) == 175
     assert commit_hashes(engine, [B.packed_commit(sigs)]) == merkle_roots(engine, [B.commit_leaves(sigs)])
+
+
+_SWEEP = []
+
+
+def _full_sweep():
+    """The 57,330 cases of B.full_sweep(), generated once."""
+    if not _SWEEP:
+        _SWEEP.extend(B.full_sweep())
+    return _SWEEP
+
+
+def test_commit_hashes_full_sweep_gpu(engine):
+    """The whole CommitSig sweep through the device encoder (commitsig_leaf.h's device branches), in
+    one call: 234 PackedCommits of 245 signatures.  A mismatch names the commit index i; its cases
+    are full_sweep()[245 i : 245 i + 245], replayable through the host encoder."""
+    from tmed.merkle import commit_hashes
+    sweep = _full_sweep()
+    assert len(sweep) == 57330
+    lists = [sweep[at:at + 245] for at in range(0, len(sweep), 245)]
+    assert len(lists) == 234 and all(len(l) == 245 for l in lists)
+    got = commit_hashes(engine, [B.packed_commit(l) for l in lists])
+    wrong = [i for i, (g, l) in enumerate(zip(got, lists)) if g != B.commit_hash(l)]
+    assert not wrong, "commits (245 cases each, from case 245 * index) with another root: %s" % wrong
+
+
+def test_commit_hashes_threaded_pack_gpu(engine):
+    """One call of more than 65,536 signatures, where merkle.hip's pack_threads leaves 1 and the
+    scan and the packing run on the host threads: the sweep and a second pass over its first part,
+    cut into 400 commits of 0..400 signatures, as Commit objects, PackedCommits and PackedCommits
+    with address_lens=None; every 17th commit holds one signature the flat arrays cannot
+    reproduce (65-byte signature, 19-byte address, nanos 10^9 in rotation) and is None, the
+    others are exact, the empty ones the empty hash."""
+    from tmed.merkle import commit_hashes
+    sweep = _full_sweep()
+    rng = random.Random(17)
+    sizes = [rng.randint(0, 400) for _ in range(400)]
+    for i in (0, 34, 104, 399):
+        sizes[i] = 0
+    total = sum(sizes)
+    assert len(sweep) <= total <= 2 * len(sweep)
+    stream = sweep + sweep[:total - len(sweep)]
+    addr = bytes(range(20))
+    bad = [(2, addr, 1700000000, 5, bytes(65)), (2, addr[:19], 1700000000, 5, bytes(64)),
+           (2, addr, 1700000000, 10 ** 9, bytes(64))]
+    commits, exp, at, good_sigs, nbad = [], [], 0, 0, 0
+    for i, n in enumerate(sizes):
+        sigs = stream[at:at + n]
+        at += n
+        kind = i % 3
+        if kind == 2:  # address_lens=None: every address 20 bytes
+            sigs = [(f, a if len(a) == 20 else B._pattern(20, at + j), s, ns, sig)
+                    for j, (f, a, s, ns, sig) in enumerate(sigs)]
+        if i % 17 == 16:
+            b = bad[nbad % 3]
+            nbad += 1
+            sigs = sigs[:n // 2] + [b] + sigs[n // 2:]
+            if kind == 2 and len(b[1]) != 20:
+                kind = 1
+            exp.append(None)
+        else:
+            good_sigs += len(sigs)
+            exp.append(B.commit_hash(sigs))
+        commits.append(_product_commit(sigs) if kind == 0 else
+                       B.packed_commit(sigs, address_lens="explicit" if kind == 1 else None))
+    assert at == total and nbad >= 3
+    assert good_sigs >= 65536  # below it the single-threaded path would pass this test silently
+    got = commit_hashes(engine, commits)
+    wrong = [i for i, (g, e) in enumerate(zip(got, exp)) if g != e]
+    assert not wrong, wrong
+    assert all(got[i].hex() == B.EMPTY_HASH for i in (0, 34, 104, 399))

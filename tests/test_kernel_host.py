@@ -8,6 +8,7 @@ import random
 import numpy as np
 import pytest
 
+import prim_cases as PC
 from oracle import ed25519_go as E
 from oracle import port
 
@@ -25,29 +26,16 @@ def _fe(l, op, a, b):
 
 
 def test_field_ops_vs_bigint(hostsim):
-    P = E.P
-    rng = random.Random(11)
-    edge = [0, 1, 2, 19, P - 1, P, P + 1, P + 18, 2**255 - 1, 2**255 - 20, 2**254, 2**26 - 1, 2**51]
-    vals = edge + [rng.randrange(2**255) for _ in range(120)]
-    for a in vals:
-        for b in edge[:6] + [rng.randrange(2**255)]:
-            A, B = a % P, b % P
-            exp = {0: A * B % P, 1: A * A % P, 2: pow(A, P - 2, P), 3: pow(A, (P - 5) // 8, P), 4: (A + B) % P,
-                   5: (A - B) % P, 6: 2 * A * A % P, 7: (2 * A + B) ** 2 % P, 8: (2 * A + B) ** 2 % P,
-                   9: pow(A, P - 2, P)}
-            for op, e in exp.items():
-                assert _fe(hostsim, op, a, b) == e, (op, hex(a), hex(b))
+    for a, b in PC.field_byte_pairs():
+        for op, e in PC.field_byte_expected(a, b).items():
+            assert _fe(hostsim, op, a, b) == e, (op, hex(a), hex(b))
 
 
 def test_binary_gcd_inversion(hostsim):
     """fe25519.h fe_invert_bgcd (the batched finish's inversion): equal to z^(p-2) on random values,
     powers of two and their neighbours, values near p and 0 (0 -> 0, as z^(p-2))."""
     P = E.P
-    rng = random.Random(23)
-    vals = [0, 1, 2, 3, P - 1, P - 2, P, P + 1, 2**255 - 1, 2**254, 2**64, 2**64 - 1, 2**30, 2**30 - 1, 2**60 + 1]
-    vals += [2**rng.randrange(255) for _ in range(60)] + [(2**rng.randrange(255)) - 1 for _ in range(60)]
-    vals += [rng.randrange(2**rng.randrange(1, 256)) for _ in range(400)] + [P - rng.randrange(2**40) for _ in range(40)]
-    for a in vals:
+    for a in PC.bgcd_values():
         assert _fe(hostsim, 9, a, 0) == pow(a % P, P - 2, P), hex(a)
 
 
@@ -56,58 +44,50 @@ def test_pack256_roundtrip_at_the_limb_extremes(hostsim):
     for 2-sums of carried values at the ends of their limb ranges, the unpacked value is congruent
     mod p, its limbs sit in [0, 2^26) / [0, 2^25) (limb 9 in [-2, 2^25]), and it multiplies
     correctly as a fe_mul operand."""
-    P = E.P
-    off = [0, 26, 51, 77, 102, 128, 153, 179, 204, 230]
-    # carried ranges (fe_carry64): even [-2^25, 2^25), odd [-2^24, 2^24), limbs 1 and 5 one wider
-    lo = [-(2**25) if i % 2 == 0 else -(2**24) for i in range(10)]
-    hi = [2**25 - 1 if i % 2 == 0 else 2**24 - 1 for i in range(10)]
-    lo[1] -= 1; lo[5] -= 1; hi[1] += 1; hi[5] += 1
-    rng = random.Random(5)
-    cases = [[2 * lo[i] for i in range(10)], [2 * hi[i] for i in range(10)], [0] * 10,
-             [2 * lo[i] if i % 2 else 2 * hi[i] for i in range(10)], [2 * hi[i] if i % 2 else 2 * lo[i] for i in range(10)]]
-    for i in range(10):
-        for v in (2 * lo[i], 2 * hi[i]):
-            c = [0] * 10
-            c[i] = v
-            cases.append(c)
-    cases += [[rng.randint(2 * lo[i], 2 * hi[i]) for i in range(10)] for _ in range(800)]
-    g = rng.randrange(P)
+    cases, g = PC.pack256_cases()
     out = (ctypes.c_int32 * 10)()
     prod = ctypes.create_string_buffer(32)
     for c in cases:
         hostsim.hostsim_pack256((ctypes.c_int32 * 10)(*c), g.to_bytes(32, "little"), out, prod)
-        val = sum(x << o for x, o in zip(c, off))
-        u = list(out)
-        for i in range(9):
-            assert 0 <= u[i] < (2**25 if i % 2 else 2**26), (c, u)
-        assert -2 <= u[9] <= 2**25, (c, u)
-        assert sum(x << o for x, o in zip(u, off)) % P == val % P
-        assert int.from_bytes(prod.raw, "little") == val * g % P
+        PC.check_pack256(c, list(out), int.from_bytes(prod.raw, "little"), g)
 
 
 def test_sha512_and_reduce(hostsim):
-    rng = random.Random(5)
-    for n in [0, 1, 17, 111, 112, 113, 127, 128, 129, 200, 239, 240, 241, 300, 400]:
-        m = bytes(rng.randrange(256) for _ in range(n))
+    for m in PC.sha512_messages():
         o = ctypes.create_string_buffer(64)
-        hostsim.hostsim_sha512(m, n, o)
+        hostsim.hostsim_sha512(m, len(m), o)
         assert o.raw == hashlib.sha512(m).digest()
+    for x in PC.sc_reduce_values():
         r = ctypes.create_string_buffer(32)
-        hostsim.hostsim_sc_reduce(o.raw, r)
-        assert int.from_bytes(r.raw, "little") == int.from_bytes(o.raw, "little") % E.L
-    for x in [b"\xff" * 64, bytes(64), E.L.to_bytes(64, "little"), (E.L - 1).to_bytes(64, "little"),
-              (2 * E.L).to_bytes(64, "little"), (E.L * (2**259 - 1)).to_bytes(64, "little")]:
-        r = ctypes.create_string_buffer(32)
-        hostsim.hostsim_sc_reduce(x, r)
-        assert int.from_bytes(r.raw, "little") == int.from_bytes(x, "little") % E.L
+        hostsim.hostsim_sc_reduce(x.to_bytes(64, "little"), r)
+        assert int.from_bytes(r.raw, "little") == x % E.L, hex(x)
+
+
+def test_sha512_stream_prefixes_and_lengths(hostsim):
+    """sha512_stream of p0 || p1 || M with 0, 32 and 64 prefix bytes, every message length 0..300
+    (the cases of the device comparison)."""
+    p0, p1, buf, offs, lens = PC.sha512_stream_cases()
+    o = ctypes.create_string_buffer(64)
+    for npre in (0, 32, 64):
+        for a, b, at, n in zip(p0, p1, offs, lens):
+            m = buf[at:at + n]
+            hostsim.hostsim_sha512_pre(npre, a, b, m, n, o)
+            assert o.raw == hashlib.sha512((a + b)[:npre] + m).digest(), (npre, n)
+
+
+def test_sc_is_canonical_and_muladd(hostsim):
+    """sc_is_canonical (s < L) around L and at every word of its borrow chain; sc_muladd
+    (a b + c mod L) with all-ones words, L and its neighbours."""
+    for s in PC.sc_canonical_values():
+        assert bool(hostsim.hostsim_sc_is_canonical(s.to_bytes(32, "little"))) == (s < E.L), hex(s)
+    r = ctypes.create_string_buffer(32)
+    for a, b, c in PC.sc_muladd_cases():
+        hostsim.hostsim_sc_muladd(a.to_bytes(32, "little"), b.to_bytes(32, "little"), c.to_bytes(32, "little"), r)
+        assert int.from_bytes(r.raw, "little") == (a * b + c) % E.L, (hex(a), hex(b), hex(c))
 
 
 def test_decode_matches_go_rule(hostsim):
-    rng = random.Random(9)
-    cands = [bytes(32), bytes(31) + b"\x80"] + [rng.randbytes(32) for _ in range(80)]
-    cands += [E.encode(q) for q in E.small_order_points()]
-    cands += [(y + E.P).to_bytes(32, "little") for y in range(19)]
-    for p in cands:
+    for p in PC.decode_candidates():
         o = ctypes.create_string_buffer(32)
         ok = hostsim.hostsim_decode(p, o)
         pt = E.decode(p)
@@ -197,30 +177,42 @@ def test_comb_path_hostsim(hostsim, golden, fn):
     assert exp.sum() > 10 and (exp == 0).sum() > 10
 
 
+def _halfsize(fn, k):
+    c, d = ctypes.create_string_buffer(32), ctypes.create_string_buffer(32)
+    neg = ctypes.c_int()
+    W = fn(k.to_bytes(32, "little"), c, d, ctypes.byref(neg))
+    ci, di = int.from_bytes(c.raw, "little"), int.from_bytes(d.raw, "little")
+    return ci, -di if neg.value else di, W
+
+
 def test_halfsize_lattice(hostsim):
     """verify_hs.h sc_halfsize: c = d k (mod 8L), d odd, both within the window count's range
     (|x| < 2^(4W-1), the top digit taking the recoding's carry); W = 64 only for the (k, 1)
     fallback; typical W is 32..33."""
-    L = E.L
-    rng = random.Random(3)
-    ks = [0, 1, 2, 3, 8, 16, L - 1, L - 2, 2**127, 2**128 - 1, 2**128, 2**200, 2**252 - 1, 5 * 2**128 + 3]
-    ks += [rng.randrange(L) for _ in range(4000)]
+    ks, n_edge = PC.halfsize_lattice_ks()
     ws = []
     for k in ks:
-        c, d = ctypes.create_string_buffer(32), ctypes.create_string_buffer(32)
-        neg = ctypes.c_int()
-        W = hostsim.hostsim_halfsize(k.to_bytes(32, "little"), c, d, ctypes.byref(neg))
-        ci, di = int.from_bytes(c.raw, "little"), int.from_bytes(d.raw, "little")
-        if neg.value:
-            di = -di
-        assert (ci - di * k) % (8 * L) == 0, k
-        assert di % 2 == 1 and 0 < abs(di) < L, k
-        assert 29 <= W <= 64 and max(ci.bit_length(), abs(di).bit_length()) <= 4 * W - 1, (k, W)
-        if W == 64:
-            assert (ci, di) == (k, 1)
+        ci, di, W = _halfsize(hostsim.hostsim_halfsize, k)
+        PC.check_halfsize(k, ci, di, W)
         ws.append(W)
-    rand = ws[14:]
+    rand = ws[n_edge:]
     assert max(rand) <= 36 and sum(rand) / len(rand) < 32.8
+
+
+def test_halfsize_lattice_at_the_quotient_edges(hostsim):
+    """The same invariants where the Euclid steps are borderline: first quotients around the
+    2^32 - 2 limit of hs_euclid_step, tiny first remainders (an out-of-range second quotient, the
+    even-cofactor adjustment, the (k, 1) fallback) and long runs of quotients 1 and 2."""
+    assert len(PC.halfsize_quotient_ks()) == 41 and len(PC.halfsize_long_euclid_ks()) == 300
+    for k in PC.halfsize_long_euclid_ks():
+        q = PC.euclid_quotients(k)
+        assert q[0] >= 8 and all(x in (1, 2) for x in q[1:1 + PC.LONG_EUCLID_MIN]), k
+    fallbacks = 0
+    for k in PC.halfsize_edge_ks():
+        ci, di, W = _halfsize(hostsim.hostsim_halfsize, k)
+        PC.check_halfsize(k, ci, di, W)
+        fallbacks += W == 64
+    assert 0 < fallbacks < 41  # the fallback is reached, and only by quotient-edge values
 
 
 def test_halfsize_torsion_keys(hostsim):
@@ -270,22 +262,18 @@ def test_halfsize_torsion_keys(hostsim):
 
 def test_halfsize_fast_euclid_equals_reference_loop(hostsim):
     """verify_hs.h's two-steps-per-iteration Euclid phase (in-place, roles swapping) must stop at
-    exactly the same remainder as the round-1 loop, so (c, d, W) are equal on every k — random k
-    and the boundary values of the lattice test."""
-    L = E.L
-    rng = random.Random(11)
-    ks = [0, 1, 2, 3, 8, 16, L - 1, L - 2, 2**127, 2**128 - 1, 2**128, 2**128 + 1, 2**160, 2**200,
-          2**252 - 1, 5 * 2**128 + 3, (8 * L) // 3, (8 * L) // 5 + 1]
-    ks += [rng.randrange(L) for _ in range(6000)]
-    ks += [rng.randrange(2**129) for _ in range(300)] + [rng.randrange(2**170) for _ in range(300)]
-    for k in ks:
+    exactly the same remainder as the round-1 loop, so (c, d, W, tight W) are equal on every k —
+    random k, the boundary values of the lattice test and the quotient-edge / long-run families."""
+    for k in PC.halfsize_euclid_ks() + PC.halfsize_edge_ks():
         out = []
-        for fn in (hostsim.hostsim_halfsize, hostsim.hostsim_halfsize_plain):
+        for fast in (1, 0):
             c, d = ctypes.create_string_buffer(32), ctypes.create_string_buffer(32)
-            neg = ctypes.c_int()
-            W = fn(k.to_bytes(32, "little"), c, d, ctypes.byref(neg))
-            out.append((W, c.raw, d.raw, neg.value))
+            neg, tight = ctypes.c_int(), ctypes.c_int()
+            W = hostsim.hostsim_halfsize_tight(k.to_bytes(32, "little"), c, d, ctypes.byref(neg), ctypes.byref(tight),
+                                               fast)
+            out.append((W, c.raw, d.raw, neg.value, tight.value))
         assert out[0] == out[1], k
+        assert 29 <= out[0][4] <= out[0][0], k
 
 
 def test_halfsize_top_digit_and_wave_max(hostsim):
@@ -317,52 +305,72 @@ def test_halfsize_top_digit_and_wave_max(hostsim):
     assert wins.min() >= 29 and (wins == 32).sum() > n * 3 // 4 and wins.max() <= 34, np.bincount(wins)
 
 
-def test_fused_carry_at_the_limb_extremes(hostsim):
-    """fe_mul / fe_sq (3-sum inputs) and fe_sq2 (carried input) at the ends of the carried limb
-    ranges (fe25519.h: even limbs [-2^25, 2^25), odd [0, 2^25), limb 1 [-2^16, 2^25 + 2^16), and
-    fe_carry's odd [-2^24, 2^24]): the result is the product mod p and its limbs are carried."""
-    P = E.P
-    off = [0, 26, 51, 77, 102, 128, 153, 179, 204, 230]
-    lo = [-(2**25) if i % 2 == 0 else -(2**24) for i in range(10)]
-    hi = [2**25 - 1 if i % 2 == 0 else 2**25 - 1 for i in range(10)]
-    lo[1], hi[1] = -(2**24) - 2**16, 2**25 + 2**16
-    rng = random.Random(23)
-
-    def val(c):
-        return sum(x << o for x, o in zip(c, off))
-
-    def carried():
-        r = rng.random()
-        if r < 0.3:
-            return [lo[i] if rng.random() < 0.5 else hi[i] for i in range(10)]
-        return [rng.randint(lo[i], hi[i]) for i in range(10)]
-
-    def nsum(n):
-        cs = [carried() for _ in range(n)]
-        return [sum(c[i] for c in cs) for i in range(10)]
-
-    cases = [([3 * hi[i] for i in range(10)], [3 * hi[i] for i in range(10)]),
-             ([3 * lo[i] for i in range(10)], [3 * lo[i] for i in range(10)]),
-             ([3 * hi[i] for i in range(10)], [3 * lo[i] for i in range(10)])]
-    cases += [(nsum(3), nsum(3)) for _ in range(600)] + [(nsum(1), nsum(2)) for _ in range(300)]
-    out = (ctypes.c_int32 * 10)()
-    enc = ctypes.create_string_buffer(32)
+def _fe_raw(l, op, a0, b0, a1=None, b1=None, alias=0):
+    """(limbs, value) of hostsim_fe_raw (the single products), or that pair for both products of
+    hostsim_fe_raw_x2 (the two-product schedules)."""
     A = lambda c: (ctypes.c_int32 * 10)(*c)
-    for a, b in cases:
-        for op, exp, inputs_ok in ((0, val(a) * val(b), True), (1, val(a) ** 2, True),
-                                   (2, 2 * val(a) ** 2, all(lo[i] <= a[i] <= hi[i] for i in range(10)))):
-            if not inputs_ok:
-                continue
-            hostsim.hostsim_fe_raw(op, A(a), A(b), out, enc)
-            assert int.from_bytes(enc.raw, "little") == exp % P, (op, a, b)
-            u = list(out)
-            for i in range(10):
-                assert lo[i] <= u[i] <= hi[i] or (i % 2 == 1 and 0 <= u[i] < 2**25), (op, i, u[i])
-    # fe_sq2 on carried inputs at the extremes
-    for _ in range(400):
-        a = carried()
-        hostsim.hostsim_fe_raw(2, A(a), A(a), out, enc)
-        assert int.from_bytes(enc.raw, "little") == 2 * val(a) ** 2 % P
+    o0, o1 = (ctypes.c_int32 * 10)(), (ctypes.c_int32 * 10)()
+    e0, e1 = ctypes.create_string_buffer(32), ctypes.create_string_buffer(32)
+    if op < PC.FE_MUL_X2:
+        l.hostsim_fe_raw(op, A(a0), A(b0), o0, e0)
+        return list(o0), int.from_bytes(e0.raw, "little")
+    l.hostsim_fe_raw_x2(op, alias, A(a0), A(b0), A(a1), A(b1), o0, e0, o1, e1)
+    return (list(o0), int.from_bytes(e0.raw, "little")), (list(o1), int.from_bytes(e1.raw, "little"))
+
+
+def _check_product(got, exp, what):
+    limbs, value = got
+    assert value == exp % E.P, what
+    for i in range(10):
+        assert PC.in_carried_output_range(i, limbs[i]), (what, i, limbs[i])
+
+
+def test_fused_carry_at_the_limb_extremes(hostsim):
+    """fe_mul / fe_sq (3-sum inputs), fe_sq2 and fe_sqc (carried input) at the ends of the carried
+    limb ranges (fe25519.h: even limbs [-2^25, 2^25), odd [0, 2^25), limb 1 [-2^16, 2^25 + 2^16),
+    and fe_carry's odd [-2^24, 2^24]): the result is the product mod p and its limbs are carried."""
+    val = PC.limb_val
+    for a, b in PC.fused_pairs():
+        ops = [(PC.FE_MUL, val(a) * val(b)), (PC.FE_SQ, val(a) ** 2)]
+        if PC.is_carried(a):
+            ops += [(PC.FE_SQ2, 2 * val(a) ** 2), (PC.FE_SQC, val(a) ** 2)]
+        for op, exp in ops:
+            got = _fe_raw(hostsim, op, a, b)
+            _check_product(got, exp, (op, a, b))
+    # fe_sq2 and fe_sqc on carried inputs at the extremes
+    for a in PC.fused_carried():
+        for op, exp in ((PC.FE_SQ2, 2 * val(a) ** 2), (PC.FE_SQC, val(a) ** 2)):
+            got = _fe_raw(hostsim, op, a, a)
+            _check_product(got, exp, (op, a))
+
+
+@pytest.mark.parametrize("alias", [0, 1, 2, 3])
+def test_fused_pair_schedules_at_the_limb_extremes(hostsim, alias):
+    """The two-product schedules at the same extremes, within the input bounds fe25519.h states:
+    fe_mul_x2 and fe_sq_x2 on 3-sums, fe_sqc_x2 on carried values, fe_sq2_sq on a carried and a
+    3-sum operand; one operand set all-low beside the other all-high, and both sets equal.  Each
+    result is its product mod p with carried limbs, with separate outputs (alias 0) and with the
+    outputs written over the inputs (1: own first input, 2: own last input, 3: the other product's
+    first input), which fe25519.h promises to work."""
+    val = PC.limb_val
+    for a0, b0, a1, b1 in PC.fused_pair_sets():
+        what = (alias, a0, b0, a1, b1)
+        r0, r1 = _fe_raw(hostsim, PC.FE_MUL_X2, a0, b0, a1, b1, alias)
+        _check_product(r0, val(a0) * val(b0), ("fe_mul_x2", 0) + what)
+        _check_product(r1, val(a1) * val(b1), ("fe_mul_x2", 1) + what)
+        r0, r1 = _fe_raw(hostsim, PC.FE_SQ_X2, a0, b0, a1, b1, alias)
+        _check_product(r0, val(a0) ** 2, ("fe_sq_x2", 0) + what)
+        _check_product(r1, val(a1) ** 2, ("fe_sq_x2", 1) + what)
+    carried = PC.carried_pair_sets()
+    sums = PC.fused_pair_sets()
+    for j, (a0, a1) in enumerate(carried):
+        r0, r1 = _fe_raw(hostsim, PC.FE_SQC_X2, a0, a0, a1, a1, alias)
+        _check_product(r0, val(a0) ** 2, ("fe_sqc_x2", 0, alias, a0, a1))
+        _check_product(r1, val(a1) ** 2, ("fe_sqc_x2", 1, alias, a0, a1))
+        s = sums[j % len(sums)][2 * (j % 2)]  # a 3-sum second operand (the extremes come first)
+        r0, r1 = _fe_raw(hostsim, PC.FE_SQ2_SQ, a0, a0, s, s, alias)
+        _check_product(r0, 2 * val(a0) ** 2, ("fe_sq2_sq", 0, alias, a0, s))
+        _check_product(r1, val(s) ** 2, ("fe_sq2_sq", 1, alias, a0, s))
 
 
 @pytest.mark.parametrize("B", [10, 11, 12])
