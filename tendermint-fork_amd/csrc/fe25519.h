@@ -54,13 +54,6 @@ TMED_HD int32_t dbl32(int32_t x) {
 #endif
 }
 
-#ifndef TMED_FE_FUSED
-#define TMED_FE_FUSED 2  // A/B knob: 0 = column sums + separate carry pass, 1 = fused carry one product
-                         // at a time, 2 = independent pairs in one schedule (fe_mul_x2 / fe_sq_x2)
-#endif
-
-
-
 TMED_HD void fe_0(fe &h) {
 #pragma unroll
   for (int i = 0; i < 10; i++) h.v[i] = 0;
@@ -95,8 +88,10 @@ TMED_HD void fe_select(fe &h, const fe &f, const fe &g, bool b) {
 // one 64-bit shift, one 32-bit and, one 64-bit add per carry (+ one 32-bit sub per limb).
 TMED_HD int64_t fe_bias(int k) { return (k & 1) ? ((int64_t)1 << 24) : ((int64_t)1 << 25); }
 
-// The column sums of fe_mul / fe_sq / fe_sq2 as explicit v_mad_i64_i32 schedules, bias in
-// each column's first mad (generated: tools/gen_fe_asm.py).
+// The products of fe_mul / fe_sq / fe_sq2 as explicit v_mad_i64_i32 schedules with the carry
+// chain fused in (generated: tools/gen_fe_asm.py).  Column sums with a separate carry pass cost
+// ~8 % more instructions and were slower even for a lone wave (C1 keyed 0.0840 against 0.0801 ms,
+// profiles/r04/s20/).
 #include "fe_cols.h"
 
 // Carry pass over BIASED 64-bit column sums H_k = h_k + B_k -> carried limbs.  Two
@@ -153,7 +148,7 @@ TMED_HD void fe_fused_fin(fe &h, const int64_t H[10]) {
 }
 
 // h = f * g  (100 v_mad_i64_i32; operand pairs (i, j) carry x2 when both are odd and x19 on g_j
-// when i + j >= 10 — fe_mul_cols / fe_mul_fused)
+// when i + j >= 10 — fe_mul_fused)
 TMED_HD void fe_mul(fe &h, const fe &f, const fe &g) {
   int32_t g19[10], f2[10];
 #pragma unroll
@@ -161,13 +156,8 @@ TMED_HD void fe_mul(fe &h, const fe &f, const fe &g) {
 #pragma unroll
   for (int i = 0; i < 10; i++) f2[i] = dbl32(f.v[i]);
   int64_t acc[10];
-#if TMED_FE_FUSED
   fe_mul_fused(acc, f.v, f2, g.v, g19);
   fe_fused_fin(h, acc);
-#else
-  fe_mul_cols(acc, f.v, f2, g.v, g19);
-  fe_carry64(h, acc);
-#endif
 }
 
 // Column sums of D f^2, D = 1 (square) or 2 (the doubling's 2 Z^2): 55 products.  Pair (i, j),
@@ -195,21 +185,13 @@ struct fe_premul {
 TMED_HD void fe_sq(fe &h, const fe &f) {
   const fe_premul p(f);
   int64_t acc[10];
-#if TMED_FE_FUSED
   fe_sq1_fused(acc, p.x, p.x2, p.x4, p.x19, p.x38);
   fe_fused_fin(h, acc);
-#else
-  fe_sq1_cols(acc, p.x, p.x2, p.x4, p.x19, p.x38);
-  fe_carry64(h, acc);
-#endif
 }
 
 // h = f^2 for a CARRIED f (one carried value, e.g. any mul / sq output, not a sum):
 // fe_sq1c_fused's 13 premultiplied copies (x2 of limbs 0, 1, 2, 3, 5, 7, x19 of 6, 8, x38 of
 // 5..9; x38 of 6, 8 as 2 * x19) instead of fe_sq's 19.
-#ifndef TMED_FE_SQC
-#define TMED_FE_SQC 1  // A/B knob: 0 = carried inputs take the general fe_sq
-#endif
 struct fe_premul_c {
   int32_t x[10], x2[10], x19[10], x38[10];
   TMED_HDM explicit fe_premul_c(const fe &f) {
@@ -224,27 +206,18 @@ struct fe_premul_c {
 };
 
 TMED_HD void fe_sqc(fe &h, const fe &f) {
-#if TMED_FE_SQC
   const fe_premul_c p(f);
   int64_t acc[10];
   fe_sq1c_fused(acc, p.x, p.x2, p.x19, p.x38);
   fe_fused_fin(h, acc);
-#else
-  fe_sq(h, f);
-#endif
 }
 
 // h = 2 f^2 (f carried)
 TMED_HD void fe_sq2(fe &h, const fe &f) {
   const fe_premul p(f);
   int64_t acc[10];
-#if TMED_FE_FUSED
   fe_sq2_fused(acc, p.x, p.x2, p.x4, p.x19, p.x38);
   fe_fused_fin(h, acc);
-#else
-  fe_sq2_cols(acc, p.x, p.x2, p.x4, p.x19, p.x38);
-  fe_carry64(h, acc);
-#endif
 }
 
 // Two independent products / squares in one schedule (fe_mul_fused_x2, fe_sq1_fused_x2,
@@ -252,7 +225,6 @@ TMED_HD void fe_sq2(fe &h, const fe &f) {
 // a time leaves them 2 apart (~5 % per mad: profiles/r02/micro/mad_dep_probe.jsonl).  Outputs may
 // alias inputs (everything is read before anything is written).
 TMED_HD void fe_mul_x2(fe &h0, const fe &f0, const fe &g0, fe &h1, const fe &f1, const fe &g1) {
-#if TMED_FE_FUSED >= 2
   int32_t a19[10], a2[10], b19[10], b2[10];
 #pragma unroll
   for (int j = 0; j < 10; j++) { a19[j] = mul19(g0.v[j]); b19[j] = mul19(g1.v[j]); }
@@ -262,56 +234,32 @@ TMED_HD void fe_mul_x2(fe &h0, const fe &f0, const fe &g0, fe &h1, const fe &f1,
   fe_mul_fused_x2(H0, H1, f0.v, a2, g0.v, a19, f1.v, b2, g1.v, b19);
   fe_fused_fin(h0, H0);
   fe_fused_fin(h1, H1);
-#else
-  fe t;
-  fe_mul(t, f0, g0);
-  fe_mul(h1, f1, g1);
-  fe_copy(h0, t);
-#endif
 }
 
 TMED_HD void fe_sq_x2(fe &h0, const fe &f0, fe &h1, const fe &f1) {
-#if TMED_FE_FUSED >= 2
   const fe_premul a(f0), b(f1);
   int64_t H0[10], H1[10];
   fe_sq1_fused_x2(H0, H1, a.x, a.x2, a.x4, a.x19, a.x38, b.x, b.x2, b.x4, b.x19, b.x38);
   fe_fused_fin(h0, H0);
   fe_fused_fin(h1, H1);
-#else
-  fe t;
-  fe_sq(t, f0);
-  fe_sq(h1, f1);
-  fe_copy(h0, t);
-#endif
 }
 
 // h0 = f0^2, h1 = f1^2 for carried f0, f1 (fe_sqc)
 TMED_HD void fe_sqc_x2(fe &h0, const fe &f0, fe &h1, const fe &f1) {
-#if TMED_FE_SQC && TMED_FE_FUSED >= 2
   const fe_premul_c a(f0), b(f1);
   int64_t H0[10], H1[10];
   fe_sq1c_fused_x2(H0, H1, a.x, a.x2, a.x19, a.x38, b.x, b.x2, b.x19, b.x38);
   fe_fused_fin(h0, H0);
   fe_fused_fin(h1, H1);
-#else
-  fe_sq_x2(h0, f0, h1, f1);
-#endif
 }
 
 // h0 = 2 f0^2 (f0 carried), h1 = f1^2
 TMED_HD void fe_sq2_sq(fe &h0, const fe &f0, fe &h1, const fe &f1) {
-#if TMED_FE_FUSED >= 2
   const fe_premul a(f0), b(f1);
   int64_t H0[10], H1[10];
   fe_sq2_sq1_fused(H0, H1, a.x, a.x2, a.x4, a.x19, a.x38, b.x, b.x2, b.x4, b.x19, b.x38);
   fe_fused_fin(h0, H0);
   fe_fused_fin(h1, H1);
-#else
-  fe t;
-  fe_sq2(t, f0);
-  fe_sq(h1, f1);
-  fe_copy(h0, t);
-#endif
 }
 
 // f carried (every caller squares a product output)
@@ -497,7 +445,7 @@ TMED_HD void fe_const_sqrtm1(fe &h) {
 // v = 2^540 / z, so one multiplication by 2^-540 finishes.  z = 0 gives 0, like z^(p-2).  About
 // 15k VALU instructions, a third of them mads, against ~24k (15k mads) for the exponentiation;
 // the branch-free inner loop keeps every lane of a wave on one instruction stream.
-// (Replaces fe_invert in the batched finish: TMED_FIN_BGCD, verify_core.h finish_group.)
+// (Replaces fe_invert in the batched finish: verify_core.h finish_group.)
 constexpr uint32_t kM30 = 0x3fffffffu;
 constexpr int kBgcdOuter = 18;
 

@@ -35,17 +35,13 @@ TMED_HD void ge_niels_0(ge_niels &h) { fe_1(h.YpX); fe_1(h.YmX); fe_0(h.XY2d); }
 // f's odd limbs by 2: the operands are ordered so that only T and Y are ever g (and X, Z f),
 // and the compiler shares those copies between the products: 18 instead of 27 x19 copies in
 // p1p1 -> p3, 10 instead of 15 x2 copies in p1p1 -> p2.
-#ifndef TMED_P1P1_VC
-#define TMED_P1P1_VC 1  // A/B knob: 0 = Y * Z with Y as f (the round-2 order)
-#endif
+// (Y * Z with Y as f, the round-2 order, makes Z a g as well: nine more x19 copies.)
 TMED_HD void ge_p1p1_to_p2(ge_p2 &r, const ge_p1p1 &p) {
-  if (TMED_P1P1_VC) fe_mul_x2(r.X, p.X, p.T, r.Y, p.Z, p.Y);
-  else fe_mul_x2(r.X, p.X, p.T, r.Y, p.Y, p.Z);
+  fe_mul_x2(r.X, p.X, p.T, r.Y, p.Z, p.Y);
   fe_mul(r.Z, p.Z, p.T);
 }
 TMED_HD void ge_p1p1_to_p3(ge_p3 &r, const ge_p1p1 &p) {
-  if (TMED_P1P1_VC) fe_mul_x2(r.X, p.X, p.T, r.Y, p.Z, p.Y);
-  else fe_mul_x2(r.X, p.X, p.T, r.Y, p.Y, p.Z);
+  fe_mul_x2(r.X, p.X, p.T, r.Y, p.Z, p.Y);
   fe_mul(r.Z, p.Z, p.T);
   fe_mul(r.T, p.X, p.Y);
 }

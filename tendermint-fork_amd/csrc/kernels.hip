@@ -1,4 +1,9 @@
-// kernels.hip — gfx950 kernels: batch ed25519 verify and RFC 8032 sign.
+// kernels.hip — gfx950 kernels: batch ed25519 verify (the generic throughput path, then the
+// key-cached path) and RFC 8032 sign.  The kernels that build the tables these read, once per
+// context or per key set, are in kernels_tables.hip.
+// Every kernel that hashes stays in this one unit: sha512_stream is compiled once per unit, and
+// how the compiler shapes its block loop depends on the set of prefix lengths the unit's callers
+// pass (the verify kernels 64, the signer 32).  Apart, the verify kernels' code changes.
 //
 // One signature per lane (64 per wave) on the throughput paths.  The work per signature
 // is ~2.2e5 32x32->64 integer multiply-adds, entirely VALU; the
@@ -12,13 +17,10 @@
 //   b16   32769 niels multiples of B in 128-B rows in HBM (4.2 MB; the full-length fallback, variant 5)
 //   combs key-set combs [key][window][entry] and the shared combs of B (radix 256, radix 2^16)
 #include "kernels.h"
-#ifndef TMED_SLAB_PF
-#define TMED_SLAB_PF 1  // per-lane table rows loaded ahead (verify_hs.h hs_straus): the -A row before
-                        // the last doubling, the R row before the -A addition (0: right before use)
-#endif
 #include "verify_core.h"
 #include "verify_hs.h"
 #include "kernel_util.h"
+#include "rows.h"
 #include "votes_dev.h"
 
 namespace tmed {
@@ -62,23 +64,10 @@ struct SlabTab {
       slab_st(r + 2 * f + 1, make_int4((int)w[4], (int)w[5], (int)w[6], (int)w[7]));
     }
   }
-  __device__ __forceinline__ void load(int j, ge_cached &c) const {
-    fe *fs[4] = {&c.YpX, &c.YmX, &c.Z, &c.T2d};
-    const int4 *r = row(j);
-    int4 v[8];
-#pragma unroll
-    for (int q = 0; q < 8; q++) v[q] = r[q];
-#pragma unroll
-    for (int f = 0; f < 4; f++) {
-      const uint32_t w[8] = {(uint32_t)v[2 * f].x, (uint32_t)v[2 * f].y, (uint32_t)v[2 * f].z,
-                             (uint32_t)v[2 * f].w, (uint32_t)v[2 * f + 1].x, (uint32_t)v[2 * f + 1].y,
-                             (uint32_t)v[2 * f + 1].z, (uint32_t)v[2 * f + 1].w};
-      fe_unpack256(*fs[f], w);
-    }
-  }
-#if TMED_SLAB_PF
   // prefetch issues the row's eight 16-B loads into registers (swap: Y+X and Y-X exchanged by
-  // the load addresses — a negative digit's entry, ge_add_cached_pre); take unpacks them
+  // the load addresses — a negative digit's entry, ge_add_cached_pre); take unpacks them.
+  // hs_straus (verify_hs.h) prefetches the -A row before the last doubling and the R row before
+  // the -A addition, not right before use.
   int4 pv[8];
   __device__ __forceinline__ void prefetch(int j, bool swap = false) {
     const int4 *r = row(j);
@@ -96,19 +85,6 @@ struct SlabTab {
       fe_unpack256(*fs[f], w);
     }
   }
-#else
-  int pf = 0;
-  bool sw = false;
-  __device__ __forceinline__ void prefetch(int j, bool swap = false) { pf = j; sw = swap; }
-  __device__ __forceinline__ void take(ge_cached &c) const {
-    ge_cached t;
-    load(pf, t);
-    fe_select(c.YpX, t.YpX, t.YmX, sw);
-    fe_select(c.YmX, t.YmX, t.YpX, sw);
-    fe_copy(c.Z, t.Z);
-    fe_copy(c.T2d, t.T2d);
-  }
-#endif
 };
 
 typedef __attribute__((address_space(1))) void global_void;
@@ -130,66 +106,8 @@ struct BPf {
     for (int q = 0; q < 8; q++)
       __builtin_amdgcn_global_load_lds((global_void *)(tab + (size_t)j * 8 + q), (lds_void *)(buf + q * 64), 16, 0, 0);
   }
-  __device__ __forceinline__ void take(ge_niels &e) const {
-    fe *fs[3] = {&e.YpX, &e.YmX, &e.XY2d};
-#pragma unroll
-    for (int q = 0; q < 8; q++) {
-      const int4 v = buf[q * 64 + lane];
-      const int32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int c = 0; c < 4; c++) {
-        const int f = 4 * q + c;
-        if (f < 30) fs[f / 10]->v[f % 10] = w[c];
-      }
-    }
-  }
+  __device__ __forceinline__ void take(ge_niels &e) const { niels_load(e, buf + lane, 64); }
 };
-
-// Per-signature hand-off from the prep to the main kernel: k, s, A.x, A.y, ok
-// (37 words padded to 10 x int4), stored [chunk q][slot] for coalescing.
-constexpr int kPrepInt4 = 10;
-
-__device__ __forceinline__ void prep_store(int4 *prep, uint32_t stride, uint32_t slot, const uint32_t k[8],
-                                           const uint32_t s[8], const ge_p3 &A, bool ok) {
-  int32_t w[40];
-#pragma unroll
-  for (int i = 0; i < 8; i++) { w[i] = (int32_t)k[i]; w[8 + i] = (int32_t)s[i]; }
-#pragma unroll
-  for (int i = 0; i < 10; i++) { w[16 + i] = A.X.v[i]; w[26 + i] = A.Y.v[i]; }
-  w[36] = ok ? 1 : 0;
-  w[37] = w[38] = w[39] = 0;
-#pragma unroll
-  for (int q = 0; q < kPrepInt4; q++)
-    prep[(size_t)q * stride + slot] = make_int4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
-}
-
-// The key-cached hand-off: only what verify_keyset_main_kernel reads (k, s in int4 0..3, ok at
-// word 36 = int4 9): 80 B per signature instead of the generic prep's 160 B.
-__device__ __forceinline__ void prep_store_ks(int4 *prep, uint32_t stride, uint32_t slot, const uint32_t k[8],
-                                              const uint32_t s[8], bool ok) {
-  prep[slot] = make_int4((int)k[0], (int)k[1], (int)k[2], (int)k[3]);
-  prep[(size_t)stride + slot] = make_int4((int)k[4], (int)k[5], (int)k[6], (int)k[7]);
-  prep[(size_t)2 * stride + slot] = make_int4((int)s[0], (int)s[1], (int)s[2], (int)s[3]);
-  prep[(size_t)3 * stride + slot] = make_int4((int)s[4], (int)s[5], (int)s[6], (int)s[7]);
-  prep[(size_t)9 * stride + slot] = make_int4(ok ? 1 : 0, 0, 0, 0);
-}
-
-__device__ __forceinline__ bool prep_load(const int4 *prep, uint32_t stride, uint32_t slot, uint32_t k[8],
-                                          uint32_t s[8], ge_p3 &A) {
-  int32_t w[40];
-#pragma unroll
-  for (int q = 0; q < kPrepInt4; q++) {
-    const int4 v = prep[(size_t)q * stride + slot];
-    w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
-  }
-#pragma unroll
-  for (int i = 0; i < 8; i++) { k[i] = (uint32_t)w[i]; s[i] = (uint32_t)w[8 + i]; }
-#pragma unroll
-  for (int i = 0; i < 10; i++) { A.X.v[i] = w[16 + i]; A.Y.v[i] = w[26 + i]; }
-  fe_1(A.Z);
-  fe_mul(A.T, A.X, A.Y);
-  return w[36] != 0;
-}
 
 // Phase 1: SHA-512(R||A||M) mod L, S < L, A = Point.SetBytes(pub)  (one lane per signature
 // of the chunk [base, base + count)).
@@ -198,20 +116,14 @@ __device__ __forceinline__ bool prep_load(const int4 *prep, uint32_t stride, uin
 // 4 % slower per C2 step: profiles/r05/s32/.)
 constexpr uint32_t kHsBlock = kThreadsPerBlock;
 
-#ifndef TMED_PREP_WAVES
-#define TMED_PREP_WAVES 3  // 152 VGPRs, no spills (4 waves with a leaner decode: no faster, profiles/r03/prep_joint)
-#endif
-__global__ __launch_bounds__(kHsBlock, TMED_PREP_WAVES) void verify_prep_kernel(
+constexpr int kPrepWaves = 3;  // 152 VGPRs, no spills (4 waves with a leaner decode: no faster, profiles/r03/prep_joint)
+__global__ __launch_bounds__(kHsBlock, kPrepWaves) void verify_prep_kernel(
     const uint8_t *__restrict__ pub, const uint8_t *__restrict__ sig, MsgSrc ms, uint32_t base, uint32_t count,
     int4 *__restrict__ prep, uint32_t stride, uint32_t *__restrict__ place) {
   const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
   if (place && slot == 0) place[0] = place[1] = 0;  // the half-size placement counters (verify_prep_r_kernel)
   if (slot >= count) return;
   const uint32_t i = base + slot;
-#ifndef TMED_PREP_SHA_FIRST
-#define TMED_PREP_SHA_FIRST 1
-#endif
-#if TMED_PREP_SHA_FIRST
   // verify_prep's steps with the hash first and k, s handed over at once, so the decode of A
   // runs with only the key's words live (s keeps S when only A fails to decode: the verdict
   // is false either way and S < L after the S checks).
@@ -247,17 +159,6 @@ __global__ __launch_bounds__(kHsBlock, TMED_PREP_WAVES) void verify_prep_kernel(
 #pragma unroll
   for (int q = 0; q < 6; q++)  // words 16..39: A.x, A.y, ok
     prep[(size_t)(4 + q) * stride + slot] = make_int4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
-#else
-  uint32_t pw[8], sw[16], k[8], s[8];
-  load_row_words(pw, pub + 32 * (size_t)i, 2);
-  load_row_words(sw, sig + 64 * (size_t)i, 4);
-  const uint8_t *m;
-  uint32_t mlen;
-  ms.get(i, m, mlen);
-  ge_p3 A;
-  const bool ok = verify_prep(pw, sw, m, mlen, k, s, A);
-  prep_store(prep, stride, slot, k, s, A, ok);
-#endif
 }
 
 // ---- f1: CanonicalVote sign-bytes assembled on the device ----------
@@ -287,18 +188,6 @@ __global__ __launch_bounds__(kAsmLanes) void assemble_votes_kernel(VoteAsm va, u
     const uint32_t c = q * kAsmLanes + lane;  // int4 index in the wave's 16-KB run of slots
     if (c / (kVoteSlot / 16) < nslots) dst[c] = src[c];
   }
-}
-
-// Projective R' of signature slot (X, Y, Z: 30 limbs + 2 pad = 8 int4), stored [q][slot].
-__device__ __forceinline__ void fin_store(int4 *fin, uint32_t stride, uint32_t slot, const fe &X, const fe &Y,
-                                          const fe &Z) {
-  int32_t w[32];
-#pragma unroll
-  for (int i = 0; i < 10; i++) { w[i] = X.v[i]; w[10 + i] = Y.v[i]; w[20 + i] = Z.v[i]; }
-  w[30] = w[31] = 0;
-#pragma unroll
-  for (int q = 0; q < kFinInt4; q++)
-    fin[(size_t)q * stride + slot] = make_int4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
 }
 
 // Phase 2 of the full-length fallback (TMED_MAIN_WAVES=5): table of -A, Straus [k](-A) + [s]B
@@ -341,10 +230,8 @@ constexpr int kPrepHsInt4 = 16;
 constexpr int kHsWSmall = 32;
 static_assert((kPrepInt4 + kPrepHsInt4) * 16 <= kPrepSlotBytes, "prep slot too small for the half-size hand-off");
 
-#ifndef TMED_PREP_R_WAVES
-#define TMED_PREP_R_WAVES 3  // 168 VGPRs, 6 spilled: -0.06 ms per 2^20 against 2 waves (the Euclid loop hides its memory waits)
-#endif
-__global__ __launch_bounds__(kHsBlock, TMED_PREP_R_WAVES) void verify_prep_r_kernel(
+constexpr int kPrepRWaves = 3;  // 168 VGPRs, 6 spilled: -0.06 ms per 2^20 against 2 waves (the Euclid loop hides its memory waits)
+__global__ __launch_bounds__(kHsBlock, kPrepRWaves) void verify_prep_r_kernel(
     const uint8_t *__restrict__ sig, uint32_t base, uint32_t count, const int4 *__restrict__ prep,
     int4 *__restrict__ prep2, uint32_t stride, uint32_t *__restrict__ place, int zip215) {
   const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
@@ -433,22 +320,16 @@ struct HsDigitsDev {
 // radix-2^16 comb (each entry fetched into LDS 16 doublings ahead), identity test.  Every
 // lane of the grid stays to the end (the wave maximum of W is a shuffle reduction); lanes
 // past count run on the identity and store nothing.
-#ifndef TMED_HS_WAVES
-#define TMED_HS_WAVES 2  // waves per SIMD of the half-size main kernel (248 VGPRs at 2)
-#endif
+constexpr int kHsWaves = 2;  // waves per SIMD of the half-size main kernel (248 VGPRs at 2)
 // BB: radix of the B windows — 26 (the default: btab, two 2^25-entry tables, ten B additions) or
 // 16 (windows 0 and 8 of the 2^16 comb, sixteen; when the 8.6-GB tables are unavailable).  The
 // hand-off carries e unrecoded (hs_prep_r raw_e); radix 16 recodes it here.
 template <int BB>
-__global__ __launch_bounds__(kHsBlock, TMED_HS_WAVES) void verify_main_hs_kernel(
+__global__ __launch_bounds__(kHsBlock, kHsWaves) void verify_main_hs_kernel(
     uint32_t base, uint32_t count, const int4 *__restrict__ prep, const int4 *__restrict__ prep2, uint32_t stride,
     int4 *__restrict__ slab, const int4 *__restrict__ btab, uint8_t *__restrict__ out, int zip215) {
   __shared__ int4 sbl[kHsBlock / 64][8 * 64];
-#if TMED_B16_ONEBUF
-  auto &sbh = sbl;
-#else
-  __shared__ int4 sbh[kHsBlock / 64][8 * 64];
-#endif
+  __shared__ int4 sbh[kHsBlock / 64][8 * 64];  // BL and BH prefetch into a buffer each
   const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;  // position in the placed hand-off
   const bool active = slot < count;
   int32_t w[64];
@@ -632,36 +513,6 @@ hipError_t launch_finish(const int4 *fin, int4 *pre, const uint8_t *sig, uint8_t
   return hipGetLastError();
 }
 
-struct GlobalComb;  // defined with the key-set kernels below
-__device__ void comb_sign_one(uint32_t sg[16], uint32_t pb[8], const uint32_t seed[8], const uint8_t *m,
-                              uint32_t mlen, const int4 *bcomb);
-
-// RFC 8032 signer for synthetic commits: [a]B and [r]B from the shared comb of B.
-__global__ __launch_bounds__(kThreadsPerBlock) void sign_kernel(
-    const uint8_t *__restrict__ seeds, const uint8_t *__restrict__ msgs, const uint32_t *__restrict__ off,
-    uint32_t n, uint8_t *__restrict__ sig_out, uint8_t *__restrict__ pub_out, const int4 *__restrict__ bcomb) {
-  const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x;
-  for (uint32_t i = gtid; i < n; i += gridDim.x * blockDim.x) {
-    uint32_t seed[8], sg[16], pb[8];
-    load_row_words(seed, seeds + 32 * (size_t)i, 2);
-    const uint32_t o0 = off[i], o1 = off[i + 1];
-    comb_sign_one(sg, pb, seed, msgs + o0, o1 - o0, bcomb);
-    uint4 *so = reinterpret_cast<uint4 *>(sig_out + 64 * (size_t)i);
-#pragma unroll
-    for (int q = 0; q < 4; q++) so[q] = make_uint4(sg[4 * q], sg[4 * q + 1], sg[4 * q + 2], sg[4 * q + 3]);
-    uint4 *po = reinterpret_cast<uint4 *>(pub_out + 32 * (size_t)i);
-#pragma unroll
-    for (int q = 0; q < 2; q++) po[q] = make_uint4(pb[4 * q], pb[4 * q + 1], pb[4 * q + 2], pb[4 * q + 3]);
-  }
-}
-
-uint32_t grid_for(size_t n, uint32_t max_blocks) {
-  size_t b = (n + kThreadsPerBlock - 1) / kThreadsPerBlock;
-  if (b > max_blocks) b = max_blocks;
-  if (b == 0) b = 1;
-  return (uint32_t)b;
-}
-
 hipError_t launch_verify(const uint8_t *pub, const uint8_t *sig, const uint8_t *msgs, const uint32_t *off,
                          uint32_t n, uint8_t *out, int4 *slab, uint32_t slab_stride, BTabs btab,
                          int4 *prep, int4 *fin, int4 *fin_pre, hipStream_t stream, uint32_t chunk, int main_waves,
@@ -724,365 +575,23 @@ hipError_t launch_verify_prep(const uint8_t *pub, const uint8_t *sig, const uint
   return hipGetLastError();
 }
 
-hipError_t launch_sign(const uint8_t *seeds, const uint8_t *msgs, const uint32_t *off, uint32_t n, uint8_t *sig_out,
-                       uint8_t *pub_out, const int4 *bcomb, hipStream_t stream) {
-  const uint32_t grid = grid_for(n, 4096);
-  hipLaunchKernelGGL(sign_kernel, dim3(grid), dim3(kThreadsPerBlock), 0, stream, seeds, msgs, off, n, sig_out,
-                     pub_out, bcomb);
+hipError_t launch_assemble_votes(const uint8_t *tmpl, const uint32_t *tmpl_idx, const uint8_t *flags,
+                                 const int64_t *ts_sec, const int32_t *ts_nanos, uint32_t n, uint8_t *out,
+                                 uint32_t *out_len, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(assemble_votes_kernel, dim3((n + kAsmLanes - 1) / kAsmLanes), dim3(kAsmLanes), 0, stream,
+                     VoteAsm{tmpl, tmpl_idx, flags, ts_sec, ts_nanos}, n, out, out_len);
   return hipGetLastError();
 }
 
-// j*B for j = 0..kB16Entries-1 into 128-B rows (one lane per entry; once per context).
-__global__ __launch_bounds__(256) void b16_fill_kernel(int4 *__restrict__ tab) {
-  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= kB16Entries) return;
-  ge_niels e;
-  if (j == 0) {
-    ge_niels_0(e);
-  } else {
-    ge_p3 B;
-    ge_base_point(B);
-    comb_entry(e, B, j, 16);
-  }
-  const fe *fs[3] = {&e.YpX, &e.YmX, &e.XY2d};
-#pragma unroll
-  for (int q = 0; q < 8; q++) {
-    int32_t w[4];
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-      const int f = 4 * q + c;
-      w[c] = f < 30 ? fs[f / 10]->v[f % 10] : 0;
-    }
-    tab[(size_t)j * 8 + q] = make_int4(w[0], w[1], w[2], w[3]);
-  }
-}
+// ============================================================ key-cached path
+// The keyed prep and main kernels (throughput), the key-grouped visiting order, and the latency
+// mode for small batches.  The signatures' keys are indices into a key set whose combs
+// kernels_tables.hip built; the batched finish is launch_finish above.
 
-hipError_t launch_build_b16(int4 *tab, hipStream_t stream) {
-  hipLaunchKernelGGL(b16_fill_kernel, dim3((kB16Entries + 255) / 256), dim3(256), 0, stream, tab);
-  return hipGetLastError();
-}
-
-// ============================================================ fixed-base combs
-
-__device__ __forceinline__ void p3_store(int32_t *dst, const ge_p3 &p) {
-  const fe *fs[4] = {&p.X, &p.Y, &p.Z, &p.T};
-#pragma unroll
-  for (int f = 0; f < 40; f++) dst[f] = fs[f / 10]->v[f % 10];
-}
-__device__ __forceinline__ void p3_load(ge_p3 &p, const int32_t *src) {
-  fe *fs[4] = {&p.X, &p.Y, &p.Z, &p.T};
-#pragma unroll
-  for (int f = 0; f < 40; f++) fs[f / 10]->v[f % 10] = src[f];
-}
-
-__global__ __launch_bounds__(64) void comb_bases_kernel(const uint8_t *__restrict__ pubs, uint32_t n, int negate,
-                                                       uint8_t *__restrict__ ok_out, int32_t *__restrict__ bases) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  uint32_t pw[8];
-  load_row_words(pw, pubs + 32 * (size_t)i, 2);
-  ge_p3 P;
-  const bool ok = ge_frombytes_go(P, pw);
-  ok_out[i] = ok ? 1 : 0;
-  if (negate) { fe_neg(P.X, P.X); fe_neg(P.T, P.T); }
-#pragma unroll 1
-  for (int w = 0; w < kCombWindows; w++) {
-    p3_store(bases + ((size_t)i * kCombWindows + w) * 40, P);
-    ge_mul256(P);
-  }
-}
-
-__device__ __forceinline__ void niels_store(int4 *dst, const ge_niels &e) {
-  const fe *fs[3] = {&e.YpX, &e.YmX, &e.XY2d};
-#pragma unroll
-  for (int q = 0; q < kCombEntryInt4; q++) {
-    int32_t w[4];
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-      const int f = 4 * q + c;
-      w[c] = f < 30 ? fs[f / 10]->v[f % 10] : 0;
-    }
-    dst[q] = make_int4(w[0], w[1], w[2], w[3]);
-  }
-}
-__device__ __forceinline__ void niels_load(ge_niels &e, const int4 *src) {
-  fe *fs[3] = {&e.YpX, &e.YmX, &e.XY2d};
-#pragma unroll
-  for (int q = 0; q < kCombEntryInt4; q++) {
-    const int4 v = src[q];
-    const int32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-      const int f = 4 * q + c;
-      if (f < 30) fs[f / 10]->v[f % 10] = w[c];
-    }
-  }
-}
-
-// Comb entries in runs of kCombARun consecutive j per lane: the run's first entry j0 * base by
-// double-and-add over nbits bits of j0, the next ones by one cached addition each (8 M), the run's
-// projective points parked in their own comb rows (X, Y, Z: 30 of the row's 32 words) and their
-// prefix products of Z in LDS, ONE inversion per run (Montgomery's trick: 3 M per entry), then
-// each row rewritten in affine niels form.  ~6k mads per entry against ~34k for a double-and-add
-// and an inversion per entry (the round-5 radix-2^12 comb of 10k keys: 1.6 s of device time that
-// way, 98 ms like this — profiles/r05/final/ and s14/ kernel_stats.csv).
-constexpr uint32_t kCombARun = 8;
-__device__ __forceinline__ void row_store_xyz(int4 *row, const ge_p3 &P) {
-  const fe *fs[3] = {&P.X, &P.Y, &P.Z};
-#pragma unroll
-  for (int q = 0; q < kCombEntryInt4; q++) {
-    int32_t w[4];
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-      const int f = 4 * q + c;
-      w[c] = f < 30 ? fs[f / 10]->v[f % 10] : 0;
-    }
-    row[q] = make_int4(w[0], w[1], w[2], w[3]);
-  }
-}
-__device__ __forceinline__ void row_load_xyz(const int4 *row, fe &X, fe &Y, fe &Z) {
-  fe *fs[3] = {&X, &Y, &Z};
-#pragma unroll
-  for (int q = 0; q < kCombEntryInt4; q++) {
-    const int4 v = row[q];
-    const int32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-      const int f = 4 * q + c;
-      if (f < 30) fs[f / 10]->v[f % 10] = w[c];
-    }
-  }
-}
-// rows[j] = j * base for j = j0 .. j0 + kCombARun - 1 (rows: the window's entry 0; base: p3 words;
-// pre: this block's LDS, 64 lanes)
-__device__ __forceinline__ void comb_fill_run(int4 *rows, const int32_t *base, uint32_t j0, int nbits,
-                              fe (*pre)[64], uint32_t lane) {
-  ge_p3 B, P;
-  p3_load(B, base);
-  ge_cached cB;
-  ge_p3_to_cached(cB, B);
-  {  // P = j0 * B, double-and-add over j0's bits
-    ge_p3 sum;
-    ge_p1p1 t;
-    ge_p2 q;
-    ge_p3_0(P);
-#pragma unroll 1
-    for (int b = nbits - 1; b >= 0; b--) {
-      ge_p3_to_p2(q, P);
-      ge_p2_dbl(t, q);
-      ge_p1p1_to_p3(P, t);
-      ge_add_cached(t, P, cB, false);
-      ge_p1p1_to_p3(sum, t);
-      const bool bit = (j0 >> b) & 1u;
-      fe_select(P.X, P.X, sum.X, bit);
-      fe_select(P.Y, P.Y, sum.Y, bit);
-      fe_select(P.Z, P.Z, sum.Z, bit);
-      fe_select(P.T, P.T, sum.T, bit);
-    }
-  }
-  fe acc;
-#pragma unroll 1
-  for (uint32_t t = 0; t < kCombARun; t++) {
-    if (t) {
-      ge_p1p1 s;
-      ge_add_cached(s, P, cB, false);
-      ge_p1p1_to_p3(P, s);
-      fe_mul(acc, acc, P.Z);
-    } else {
-      fe_copy(acc, P.Z);
-    }
-    row_store_xyz(rows + (size_t)(j0 + t) * kCombEntryInt4, P);
-    pre[t][lane] = acc;
-  }
-  fe inv, d2;
-  fe_invert_bgcd(inv, acc);
-  fe_const_d2(d2);
-#pragma unroll 1
-  for (int t = (int)kCombARun - 1; t >= 0; t--) {
-    int4 *r = rows + (size_t)(j0 + t) * kCombEntryInt4;
-    fe X, Y, Z, zi, x, y, xy;
-    row_load_xyz(r, X, Y, Z);
-    if (t) {
-      fe_mul(zi, inv, pre[t - 1][lane]);
-      fe_mul(inv, inv, Z);
-    } else {
-      fe_copy(zi, inv);
-    }
-    fe_mul_x2(x, X, zi, y, Y, zi);
-    ge_niels e;
-    fe_add(e.YpX, y, x); fe_carry(e.YpX, e.YpX);
-    fe_sub(e.YmX, y, x); fe_carry(e.YmX, e.YmX);
-    fe_mul(xy, x, y);
-    fe_mul(e.XY2d, xy, d2);
-    niels_store(r, e);
-  }
-}
-// the bit length of a run's largest start 1 + kCombARun (runs - 1)
-constexpr int comb_start_bits(uint32_t runs) {
-  int b = 0;
-  for (uint32_t v = 1 + kCombARun * (runs - 1); v; v >>= 1) b++;
-  return b;
-}
-
-// The radix-256 comb: 16 runs of 8 per (key, window) (j = 1..128), four windows per 64-lane block.
-constexpr uint32_t kCombRuns = (kCombEntries - 1) / kCombARun;  // 16
-static_assert((kCombEntries - 1) % kCombARun == 0 && 64 % kCombRuns == 0, "radix-256 comb runs");
-__global__ __launch_bounds__(64) void comb_fill_kernel(const int32_t *__restrict__ bases, uint32_t n,
-                                                       int4 *__restrict__ comb) {
-  __shared__ fe pre[kCombARun][64];
-  const uint32_t kw = blockIdx.x * (64 / kCombRuns) + threadIdx.x / kCombRuns;  // key * 32 + window
-  const uint32_t run = threadIdx.x % kCombRuns;
-  if (kw >= n * kCombWindows) return;
-  int4 *rows = comb + (size_t)kw * kCombEntries * kCombEntryInt4;
-  if (run == 0) {
-    ge_niels id;
-    ge_niels_0(id);
-    niels_store(rows, id);
-  }
-  comb_fill_run(rows, bases + (size_t)kw * 40, 1u + kCombARun * run, comb_start_bits(kCombRuns), pre, threadIdx.x);
-}
-
-struct GlobalComb {
-  static constexpr int kBits = 8;
-  const int4 *base;  // 32 windows x 129 entries x 8 int4
-  __device__ __forceinline__ void load(int w, int j, ge_niels &e) const {
-    niels_load(e, base + ((size_t)w * kCombEntries + j) * kCombEntryInt4);
-  }
-};
-
-// Radix-2^16 comb of +B for the key-cached throughput kernel: 16 windows x 32769 entries
-// (j * 2^(16w) * B) x 8 int4 = 67 MB in HBM, built once per context.
-struct GlobalComb16 {
-  static constexpr int kBits = 16;
-  const int4 *base;
-  __device__ __forceinline__ void load(int w, int j, ge_niels &e) const {
-    niels_load(e, base + ((size_t)w * kB16Entries + j) * kCombEntryInt4);
-  }
-};
-
-// Lane (w, j) of the radix-2^16 B comb: j * bases[w] (bases[w] = 2^(16w) B, p3 words).
-__global__ __launch_bounds__(256) void bcomb16_fill_kernel(const int32_t *__restrict__ bases, int4 *__restrict__ comb) {
-  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= 16u * kB16Entries) return;
-  const uint32_t w = g / kB16Entries, j = g % kB16Entries;
-  ge_niels e;
-  if (j == 0) {
-    ge_niels_0(e);
-  } else {
-    ge_p3 P;
-    p3_load(P, bases + (size_t)w * 40);
-    comb_entry(e, P, j, 16);
-  }
-  niels_store(comb + (size_t)g * kCombEntryInt4, e);
-}
-
-void host_bcomb16_bases(int32_t out[16 * 40]) {
-  ge_p3 P;
-  ge_base_point(P);
-  for (int w = 0; w < 16; w++) {
-    const fe *fs[4] = {&P.X, &P.Y, &P.Z, &P.T};
-    for (int f = 0; f < 40; f++) out[w * 40 + f] = fs[f / 10]->v[f % 10];
-    ge_mul256(P);
-    ge_mul256(P);
-  }
-}
-
-hipError_t launch_build_bcomb16(const int32_t *d_bases, int4 *comb, hipStream_t stream) {
-  hipLaunchKernelGGL(bcomb16_fill_kernel, dim3((16u * kB16Entries + 255) / 256), dim3(256), 0, stream, d_bases, comb);
-  return hipGetLastError();
-}
-
-// Entry (t, j) of the radix-2^26 B tables: j * 2^(128 t) B for j = 0..2^25 (t = 0, 1), from
-// windows 8t and 8t + 1 of the radix-2^16 comb (j = d0 + 2^16 d1, d0 signed: two mixed
-// additions), then affine niels with one inversion (per entry: ~15k mads, 2^26 entries, once
-// per device).
-__global__ __launch_bounds__(256) void b26_fill_kernel(const int4 *__restrict__ comb16, int4 *__restrict__ tab) {
-  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= 2u * kB26Entries) return;
-  const uint32_t t = g / kB26Entries, j = g % kB26Entries;
-  ge_niels e;
-  if (j == 0) {
-    ge_niels_0(e);
-  } else {
-    int d0 = (int)(j & 0xffffu);
-    uint32_t d1 = j >> 16;
-    if (d0 >= 32768) { d0 -= 65536; d1++; }
-    const GlobalComb16 bc{comb16};
-    ge_p3 P;
-    ge_p1p1 q;
-    ge_niels n;
-    ge_p3_0(P);
-    bc.load(8 * (int)t, d0 < 0 ? -d0 : d0, n);
-    niels_apply_sign(n, d0 < 0);
-    ge_madd_niels(q, P, n, false);
-    ge_p1p1_to_p3(P, q);
-    bc.load(8 * (int)t + 1, (int)d1, n);
-    ge_madd_niels(q, P, n, false);
-    ge_p1p1_to_p3(P, q);
-    ge_p3_to_niels(e, P);
-  }
-  niels_store(tab + (size_t)g * kCombEntryInt4, e);
-}
-
-hipError_t launch_build_b26(const int4 *comb16, int4 *tab, hipStream_t stream) {
-  hipLaunchKernelGGL(b26_fill_kernel, dim3((2u * kB26Entries + 255) / 256), dim3(256), 0, stream, comb16, tab);
-  return hipGetLastError();
-}
-
-// Entry (w, j) of the radix-2^24 comb: j * 2^(24w) B for j = 0..2^23.  24w = 16v + r (r = 0 or 8):
-// J = j 2^r < 2^31 as two signed 16-bit digits at windows v, v + 1 of the radix-2^16 comb (two mixed
-// additions), then affine niels with one inversion.  Window 10 (bits 240..263) only ever needs
-// j <= 2^16 (S < 2^256); its entries whose second digit would fall past the comb's last window are
-// left as the identity.
-__global__ __launch_bounds__(256) void b24_fill_kernel(const int4 *__restrict__ comb16, int4 *__restrict__ tab) {
-  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= (uint32_t)kB24Windows * kB24Entries) return;
-  const uint32_t w = g / kB24Entries, j = g % kB24Entries;
-  const uint32_t v = (24u * w) >> 4, r = (24u * w) & 15u;
-  const uint32_t J = j << r;
-  int d0 = (int)(J & 0xffffu);
-  uint32_t d1 = J >> 16;
-  if (d0 >= 32768) { d0 -= 65536; d1++; }
-  ge_niels e;
-  if (j == 0 || (v + 1 >= 16 && d1 != 0)) {
-    ge_niels_0(e);
-  } else {
-    const GlobalComb16 bc{comb16};
-    ge_p3 P;
-    ge_p1p1 q;
-    ge_niels n;
-    ge_p3_0(P);
-    bc.load((int)v, d0 < 0 ? -d0 : d0, n);
-    niels_apply_sign(n, d0 < 0);
-    ge_madd_niels(q, P, n, false);
-    ge_p1p1_to_p3(P, q);
-    if (d1) {
-      bc.load((int)v + 1, (int)d1, n);
-      ge_madd_niels(q, P, n, false);
-      ge_p1p1_to_p3(P, q);
-    }
-    ge_p3_to_niels(e, P);
-  }
-  niels_store(tab + (size_t)g * kCombEntryInt4, e);
-}
-
-hipError_t launch_build_b24(const int4 *comb16, int4 *tab, hipStream_t stream) {
-  const uint32_t n = (uint32_t)kB24Windows * kB24Entries;
-  hipLaunchKernelGGL(b24_fill_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, comb16, tab);
-  return hipGetLastError();
-}
-
-__device__ void comb_sign_one(uint32_t sg[16], uint32_t pb[8], const uint32_t seed[8], const uint8_t *m,
-                              uint32_t mlen, const int4 *bcomb) {
-  const GlobalComb bc{bcomb};
-  sign_one_bm(sg, pb, seed, m, mlen, [&](uint32_t enc[8], const uint32_t s[8]) { comb_base_mult(enc, s, bc); });
-}
-
-#ifndef TMED_KS_PREP_WAVES
-#define TMED_KS_PREP_WAVES 4  // 128 VGPRs, 4 spilled: keyed prep 0.347 -> 0.337 ms per 2^20 against 3 waves
-                              // (130 VGPRs), three alternating runs each (profiles/r04/s22)
-#endif
-__global__ __launch_bounds__(kThreadsPerBlock, TMED_KS_PREP_WAVES) void verify_keyset_prep_kernel(
+constexpr int kKsPrepWaves = 4;  // 128 VGPRs, 4 spilled: keyed prep 0.347 -> 0.337 ms per 2^20 against 3 waves
+                                 // (130 VGPRs), three alternating runs each (profiles/r04/s22)
+__global__ __launch_bounds__(kThreadsPerBlock, kKsPrepWaves) void verify_keyset_prep_kernel(
     const uint32_t *__restrict__ val_idx, uint32_t nkeys, const uint8_t *__restrict__ key_pub,
     const uint8_t *__restrict__ key_ok, const uint8_t *__restrict__ sig, MsgSrc ms, uint32_t base, uint32_t count,
     int4 *__restrict__ prep, uint32_t stride) {
@@ -1102,7 +611,7 @@ __global__ __launch_bounds__(kThreadsPerBlock, TMED_KS_PREP_WAVES) void verify_k
   prep_store_ks(prep, stride, slot, k, s, ok);
 }
 
-// Key-cached Straus with the next comb row in flight (TMED_KS_PF): the 48 rows a signature
+// Key-cached Straus with the next comb row in flight: the 48 rows a signature
 // reads (32 from its key's radix-256 comb, 16 from the shared radix-2^16 comb of B) are random
 // 128-B lines of a multi-GB table, so a row loaded right before its addition leaves the wave
 // parked on HBM latency for most of it (rocprof: 0.35 of the mad peak, round 2).  Here the row
@@ -1110,13 +619,8 @@ __global__ __launch_bounds__(kThreadsPerBlock, TMED_KS_PREP_WAVES) void verify_k
 // of the recodings: A(4q), A(4q+1), B(2q), A(4q+2), A(4q+3), B(2q+1) — the same sum as
 // verify_main_comb_point<16>.  The first addition starts from the identity, so it is replaced
 // by the niels -> extended conversion (1 M instead of 7 M), and the last one stops at
-// projective (X, Y, Z) (3 M instead of 4 M for p1p1 -> p3).
-#ifndef TMED_KS_PF
-#define TMED_KS_PF 1
-#endif
-#ifndef TMED_KS_ROLL
-#define TMED_KS_ROLL 0  // 1: one addition per loop iteration (A/B of the loop body's code size)
-#endif
+// projective (X, Y, Z) (3 M instead of 4 M for p1p1 -> p3).  The six additions of a word stay
+// unrolled: each step's role is then fixed at compile time.
 struct CombRowPf {
   int4 pv[8];
   bool neg;
@@ -1126,16 +630,7 @@ struct CombRowPf {
     neg = n;
   }
   __device__ __forceinline__ void take(ge_niels &e) const {
-    fe *fs[3] = {&e.YpX, &e.YmX, &e.XY2d};
-#pragma unroll
-    for (int q = 0; q < 8; q++) {
-      const int32_t w[4] = {pv[q].x, pv[q].y, pv[q].z, pv[q].w};
-#pragma unroll
-      for (int c = 0; c < 4; c++) {
-        const int f = 4 * q + c;
-        if (f < 30) fs[f / 10]->v[f % 10] = w[c];
-      }
-    }
+    niels_load(e, pv);
     niels_apply_sign(e, neg);
   }
 };
@@ -1178,40 +673,6 @@ __device__ __forceinline__ void keyset_straus_pf(ge_p2 &out, const uint32_t k[8]
   ge_p3 acc;
   ge_p1p1 t;
   ge_niels e;
-#if TMED_KS_ROLL
-  // one addition per iteration (small loop body); the step's role comes from uniform branches
-  uint32_t kc = kr[0], sc = sr[0];
-#pragma unroll 1
-  for (int tt = 0; tt < 48; tt++) {
-    const int q = tt / 6, st = tt - 6 * (tt / 6);
-    pf.take(e);
-    const int nx = st + 1;
-    if (nx == 6) {
-#pragma unroll
-      for (int m = 0; m < 7; m++) { kr[m] = kr[m + 1]; sr[m] = sr[m + 1]; }
-      kc = kr[0];
-      sc = sr[0];
-    }
-    const int4 *row;
-    if (nx == 6) {
-      row = ks_arow(ak, 4 * q + 4 < 32 ? 4 * q + 4 : 0, kc & 0xffu, ng);
-    } else if (nx == 2 || nx == 5) {
-      row = ks_brow(bc, 2 * q + (nx == 5), (sc >> (nx == 5 ? 16 : 0)) & 0xffffu, ng);
-    } else {
-      const int b = nx < 2 ? nx : nx - 1;
-      row = ks_arow(ak, 4 * q + b, (kc >> (8 * b)) & 0xffu, ng);
-    }
-    if (tt < 47) pf.fetch(row, ng);
-    if (tt == 0) {
-      ge_niels_to_p3(acc, e);
-    } else {
-      ge_madd_niels(t, acc, e, false);
-      if (tt == 47) ge_p1p1_to_p2(out, t);
-      else ge_p1p1_to_p3(acc, t);
-    }
-  }
-  return;
-#endif
 #pragma unroll 1
   for (int q = 0; q < 8; q++) {
     const uint32_t kc = kr[0], sc = sr[0];
@@ -1402,17 +863,10 @@ __global__ __launch_bounds__(kThreadsPerBlock, WAVES) void verify_keyset_main_ke
   const bool ok = prep[(size_t)9 * stride + ps].x != 0;
 #pragma unroll
   for (int j = 0; j < 8; j++) { k[j] = (uint32_t)w[j]; s[j] = (uint32_t)w[8 + j]; }
-#if TMED_KS_PF
   ge_p2 R;
   if (ACOMB) keyset_straus_ab24(R, k, s, key_rows(acomb, v, kCombARowsPerKey * kCombEntryInt4), bcomb);
   else if (B24) keyset_straus_b24(R, k, s, key_rows(acomb, v, (size_t)kCombWindows * kCombEntries * kCombEntryInt4), bcomb);
   else keyset_straus_pf(R, k, s, key_rows(acomb, v, (size_t)kCombWindows * kCombEntries * kCombEntryInt4), bcomb);
-#else
-  const GlobalComb ac{key_rows(acomb, v, (size_t)kCombWindows * kCombEntries * kCombEntryInt4)};
-  const GlobalComb16 bc{bcomb};
-  ge_p3 R;
-  verify_main_comb_point(R, k, s, ac, bc);
-#endif
   fin_store(fin, kFinCap, pos - fin_base, R.X, R.Y, R.Z);
   out[i] = ok ? 1 : 0;
 }
@@ -1516,79 +970,6 @@ hipError_t launch_key_order(const uint32_t *val_idx, uint32_t n, uint32_t nkeys,
   hipLaunchKernelGGL(key_scan_kernel, dim3(1), dim3(1024), 0, stream, scratch, nbins);
   hipLaunchKernelGGL(key_scatter_kernel, dim3(ntiles), dim3(256), 0, stream, val_idx, n, nkeys, shift, nbins, scratch,
                      index_base, perm);
-  return hipGetLastError();
-}
-
-hipError_t launch_comb_bases(const uint8_t *pubs, uint32_t n, int negate, uint8_t *ok, int32_t *bases,
-                             hipStream_t stream) {
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(comb_bases_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, pubs, n, negate, ok, bases);
-  return hipGetLastError();
-}
-
-hipError_t launch_comb_fill(const int32_t *bases, uint32_t n, int4 *comb, hipStream_t stream) {
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(comb_fill_kernel, dim3((n * kCombWindows + 64 / kCombRuns - 1) / (64 / kCombRuns)), dim3(64), 0,
-                     stream, bases, n, comb);
-  return hipGetLastError();
-}
-
-
-// ---- radix-2^B comb of -A (kernels.h kCombA*) -------------------------------------------
-__global__ __launch_bounds__(64) void comba_bases_kernel(const uint8_t *__restrict__ pubs, uint32_t n,
-                                                        int32_t *__restrict__ bases) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  uint32_t pw[8];
-  load_row_words(pw, pubs + 32 * (size_t)i, 2);
-  ge_p3 P;
-  (void)ge_frombytes_go(P, pw);  // the identity when the key does not decode (key_ok rejects it)
-  fe_neg(P.X, P.X);
-  fe_neg(P.T, P.T);
-#pragma unroll 1
-  for (int w = 0; w < kCombAWindows; w++) {
-    p3_store(bases + ((size_t)i * kCombAWindows + w) * 40, P);
-    ge_mul256(P);  // x 2^B: B - 8 more doublings
-    ge_p1p1 t;
-    ge_p2 q;
-    ge_p3_to_p2(q, P);
-#pragma unroll 1
-    for (int d = 0; d < kCombABits - 8; d++) {
-      ge_p2_dbl(t, q);
-      if (d + 1 < kCombABits - 8) ge_p1p1_to_p2(q, t);
-    }
-    ge_p1p1_to_p3(P, t);
-  }
-}
-
-// The radix-2^B comb of -A: runs of 8 (comb_fill_run), 64 runs per block, each block within one
-// (key, window).
-constexpr uint32_t kCombARunsReg = (kCombAEntries - 1) / kCombARun;     // 256: j = 1..2048
-constexpr uint32_t kCombARunsTop = (kCombATopEntries - 1) / kCombARun;  // 528: j = 1..4224
-static_assert((kCombAEntries - 1) % kCombARun == 0 && (kCombATopEntries - 1) % kCombARun == 0, "runs");
-constexpr uint32_t kCombABlocksReg = (kCombARunsReg + 63) / 64, kCombABlocksTop = (kCombARunsTop + 63) / 64;
-constexpr uint32_t kCombABlocksPerKey = (kCombAWindows - 1) * kCombABlocksReg + kCombABlocksTop;
-__global__ __launch_bounds__(64) void comba_fill_kernel(const int32_t *__restrict__ bases, int4 *__restrict__ comb) {
-  __shared__ fe pre[kCombARun][64];
-  const uint32_t key = blockIdx.x / kCombABlocksPerKey, g = blockIdx.x % kCombABlocksPerKey;
-  const bool top = g >= (kCombAWindows - 1) * kCombABlocksReg;
-  const uint32_t w = top ? kCombAWindows - 1 : g / kCombABlocksReg;
-  const uint32_t run = (g - w * kCombABlocksReg) * 64u + threadIdx.x;
-  int4 *rows = comb + ((size_t)key * kCombARowsPerKey + comba_row((int)w, 0)) * kCombEntryInt4;
-  if (run == 0) {
-    ge_niels id;
-    ge_niels_0(id);
-    niels_store(rows, id);
-  }
-  if (run >= (top ? kCombARunsTop : kCombARunsReg)) return;
-  comb_fill_run(rows, bases + ((size_t)key * kCombAWindows + w) * 40, 1u + kCombARun * run,
-                top ? comb_start_bits(kCombARunsTop) : comb_start_bits(kCombARunsReg), pre, threadIdx.x);
-}
-
-hipError_t launch_build_comba(const uint8_t *pubs, uint32_t n, int32_t *bases, int4 *comba, hipStream_t stream) {
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(comba_bases_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, pubs, n, bases);
-  hipLaunchKernelGGL(comba_fill_kernel, dim3(n * kCombABlocksPerKey), dim3(64), 0, stream, bases, comba);
   return hipGetLastError();
 }
 
@@ -1779,16 +1160,44 @@ hipError_t launch_verify_keyset(const uint32_t *val_idx, uint32_t nkeys, const u
   return hipSuccess;
 }
 
-}  // namespace tmed
+// ============================================================ signer
+__device__ void comb_sign_one(uint32_t sg[16], uint32_t pb[8], const uint32_t seed[8], const uint8_t *m,
+                              uint32_t mlen, const int4 *bcomb) {
+  const GlobalComb bc{bcomb};
+  sign_one_bm(sg, pb, seed, m, mlen, [&](uint32_t enc[8], const uint32_t s[8]) { comb_base_mult(enc, s, bc); });
+}
 
-namespace tmed {
+// RFC 8032 signer for synthetic commits: [a]B and [r]B from the shared comb of B.
+__global__ __launch_bounds__(kThreadsPerBlock) void sign_kernel(
+    const uint8_t *__restrict__ seeds, const uint8_t *__restrict__ msgs, const uint32_t *__restrict__ off,
+    uint32_t n, uint8_t *__restrict__ sig_out, uint8_t *__restrict__ pub_out, const int4 *__restrict__ bcomb) {
+  const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x;
+  for (uint32_t i = gtid; i < n; i += gridDim.x * blockDim.x) {
+    uint32_t seed[8], sg[16], pb[8];
+    load_row_words(seed, seeds + 32 * (size_t)i, 2);
+    const uint32_t o0 = off[i], o1 = off[i + 1];
+    comb_sign_one(sg, pb, seed, msgs + o0, o1 - o0, bcomb);
+    uint4 *so = reinterpret_cast<uint4 *>(sig_out + 64 * (size_t)i);
+#pragma unroll
+    for (int q = 0; q < 4; q++) so[q] = make_uint4(sg[4 * q], sg[4 * q + 1], sg[4 * q + 2], sg[4 * q + 3]);
+    uint4 *po = reinterpret_cast<uint4 *>(pub_out + 32 * (size_t)i);
+#pragma unroll
+    for (int q = 0; q < 2; q++) po[q] = make_uint4(pb[4 * q], pb[4 * q + 1], pb[4 * q + 2], pb[4 * q + 3]);
+  }
+}
 
-hipError_t launch_assemble_votes(const uint8_t *tmpl, const uint32_t *tmpl_idx, const uint8_t *flags,
-                                 const int64_t *ts_sec, const int32_t *ts_nanos, uint32_t n, uint8_t *out,
-                                 uint32_t *out_len, hipStream_t stream) {
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(assemble_votes_kernel, dim3((n + kAsmLanes - 1) / kAsmLanes), dim3(kAsmLanes), 0, stream,
-                     VoteAsm{tmpl, tmpl_idx, flags, ts_sec, ts_nanos}, n, out, out_len);
+static uint32_t grid_for(size_t n, uint32_t max_blocks) {
+  size_t b = (n + kThreadsPerBlock - 1) / kThreadsPerBlock;
+  if (b > max_blocks) b = max_blocks;
+  if (b == 0) b = 1;
+  return (uint32_t)b;
+}
+
+hipError_t launch_sign(const uint8_t *seeds, const uint8_t *msgs, const uint32_t *off, uint32_t n, uint8_t *sig_out,
+                       uint8_t *pub_out, const int4 *bcomb, hipStream_t stream) {
+  const uint32_t grid = grid_for(n, 4096);
+  hipLaunchKernelGGL(sign_kernel, dim3(grid), dim3(kThreadsPerBlock), 0, stream, seeds, msgs, off, n, sig_out,
+                     pub_out, bcomb);
   return hipGetLastError();
 }
 

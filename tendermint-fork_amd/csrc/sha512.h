@@ -85,10 +85,7 @@ TMED_HD void sha512_init(uint64_t st[8]) {
 // three-way xors and Maj are one v_bitop3_b32 per half (gfx950; LUT 0x96 = a ^ b ^ c, 0xE8 =
 // majority — both symmetric, so the operand order is immaterial).  Host builds use the plain
 // 64-bit expressions below.
-#ifndef TMED_SHA_BITOP3
-#define TMED_SHA_BITOP3 1  // A/B knob: 0 = the plain 64-bit expressions on the device too
-#endif
-#if defined(__HIP_DEVICE_COMPILE__) && TMED_SHA_BITOP3
+#if defined(__HIP_DEVICE_COMPILE__)
 __device__ __forceinline__ uint32_t sha_xor3(uint32_t a, uint32_t b, uint32_t c) {
   uint32_t r;
   asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96" : "=v"(r) : "v"(a), "v"(b), "v"(c));

@@ -35,14 +35,6 @@
 
 #include "verify_core.h"
 
-#ifndef TMED_SLAB_PF
-#define TMED_SLAB_PF 1  // the default of kernels.hip (host builds follow the same order)
-#endif
-#ifndef TMED_B16_ONEBUF
-#define TMED_B16_ONEBUF 0  // 1: BL and BH share one prefetch buffer (the high row is fetched after the
-                           // low row is taken, the next low row after the high row is taken)
-#endif
-
 namespace tmed {
 
 // N = 8L (little-endian words).
@@ -368,7 +360,7 @@ TMED_HD void words4_shl16(uint32_t x[4]) {
 // of 26 bits, d_m = bits [26m, 26m + 26) + bit (26m - 1) - 2^26 * bit (26m + 25), in [-2^25, 2^25]
 // (every digit from the bits alone, no carry chain; the halves are < 2^128, so bits 128, 129
 // are 0 and the top digit needs no carry out).  The tables hold j * B and j * 2^128 B for
-// j = 0..2^25 (kernels.hip b26_fill_kernel, 8.6 GB).  Digit m is added when 26m doublings remain:
+// j = 0..2^25 (kernels_tables.hip b26_fill_kernel, 8.6 GB).  Digit m is added when 26m doublings remain:
 // at the end of windows 0, 13, 26 and after the second doubling of windows 6 and 19 — ten B
 // additions instead of the sixteen of radix 2^16 (-42 field multiplications per signature).
 TMED_HD int hs_b26_digit(const uint32_t x[4], int m) {
@@ -424,7 +416,7 @@ TMED_HD void hs_straus(ge_p2 &out, const DS &ds, const uint32_t er[8], int W, TA
   } else {
     const int dl = (int)(el[3] >> 16) - 32768, dh = (int)(eh[3] >> 16) - 32768;
     bl.prefetch(dl < 0 ? -dl : dl);
-    if (!TMED_B16_ONEBUF) bh.prefetch(dh < 0 ? -dh : dh);
+    bh.prefetch(dh < 0 ? -dh : dh);
   }
   ge_p2 q;
   ge_p1p1 t;
@@ -469,15 +461,13 @@ TMED_HD void hs_straus(ge_p2 &out, const DS &ds, const uint32_t er[8], int W, TA
         if (b26 && k == 1 && (n == 6 || n == 19)) hs_b26_add(t, r, n == 19 ? 3 : 1, d26l, d26h, bl, bh);  // 26m left
         ge_p1p1_to_p2(q, t);
       }
-      if (TMED_SLAB_PF) ta.prefetch(dc < 0 ? -dc : dc, dc < 0);  // the row load overlaps the last doubling
+      ta.prefetch(dc < 0 ? -dc : dc, dc < 0);  // the row load overlaps the last doubling
       ge_p2_dbl(t, q);
       ge_p1p1_to_p3(r, t);
-      if (!TMED_SLAB_PF) ta.prefetch(dc < 0 ? -dc : dc, dc < 0);
       ta.take(ca);
-      if (TMED_SLAB_PF) tr.prefetch(dd < 0 ? -dd : dd, dd < 0);  // the row load overlaps the A addition
+      tr.prefetch(dd < 0 ? -dd : dd, dd < 0);  // the row load overlaps the A addition
       ge_add_cached_pre(t, r, ca, dc < 0);
       ge_p1p1_to_p3(r, t);
-      if (!TMED_SLAB_PF) tr.prefetch(dd < 0 ? -dd : dd, dd < 0);
       tr.take(ca);
       ge_add_cached_pre(t, r, ca, dd < 0);
     }
@@ -489,21 +479,14 @@ TMED_HD void hs_straus(ge_p2 &out, const DS &ds, const uint32_t er[8], int W, TA
       words4_shl16(eh);
       ge_p1p1_to_p3(r, t);
       bl.take(nb);
-      if (TMED_B16_ONEBUF) {  // one LDS row per wave: this window's high row goes where the low one was
-        bh.prefetch(dh < 0 ? -dh : dh);
-      } else {
-        const int dn = (int)(el[3] >> 16) - 32768;
-        bl.prefetch(dn < 0 ? -dn : dn);
-      }
+      const int nl = (int)(el[3] >> 16) - 32768;  // BL and BH each own a prefetch buffer: the next
+      bl.prefetch(nl < 0 ? -nl : nl);             // low row is in flight from here
       niels_apply_sign(nb, dl < 0);
       ge_madd_niels(t, r, nb, false);
       ge_p1p1_to_p3(r, t);
       bh.take(nb);
-      {
-        const int dn = (int)((TMED_B16_ONEBUF ? el[3] : eh[3]) >> 16) - 32768;
-        if (TMED_B16_ONEBUF) bl.prefetch(dn < 0 ? -dn : dn);
-        else bh.prefetch(dn < 0 ? -dn : dn);
-      }
+      const int nh = (int)(eh[3] >> 16) - 32768;
+      bh.prefetch(nh < 0 ? -nh : nh);
       niels_apply_sign(nb, dh < 0);
       ge_madd_niels(t, r, nb, false);
     }

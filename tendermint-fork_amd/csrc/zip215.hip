@@ -125,10 +125,8 @@ __device__ __forceinline__ void zip_scalar_z(uint32_t z[8], const uint32_t seed[
 // One lane per signature of the chunk (after verify_prep_kernel wrote k, S, A, ok).  Point rows:
 // [0, cnt) = -A_i, [cnt, 2 cnt) = -R_i; digits dig[w][row] (int16, signed radix 2^16); cs = z S.
 // Invalid signatures (A or R not on the curve, S >= L) get z = 0: no contribution, out[i] = 0.
-#ifndef TMED_ZIP_PREP_WAVES
-#define TMED_ZIP_PREP_WAVES 2
-#endif
-__global__ __launch_bounds__(kThreadsPerBlock, TMED_ZIP_PREP_WAVES) void zip_prep_r_kernel(
+constexpr int kZipPrepWaves = 2;
+__global__ __launch_bounds__(kThreadsPerBlock, kZipPrepWaves) void zip_prep_r_kernel(
     const uint8_t *__restrict__ sig, uint32_t base, uint32_t cnt, const int4 *__restrict__ prep, uint32_t stride,
     const uint32_t *__restrict__ seed, uint64_t index_base, int4 *__restrict__ pts, int16_t *__restrict__ dig,
     int4 *__restrict__ cs, uint32_t cs_stride, uint8_t *__restrict__ out) {
@@ -461,14 +459,12 @@ struct ZipRowPf {
   }
 };
 
-#ifndef TMED_ZIP_ACC_WAVES
-#define TMED_ZIP_ACC_WAVES 2
-#endif
+constexpr int kZipAccWaves = 2;
 // The bucket sums of a lane go to bsum ([point][q][w][lane] rows) as each is finished, so the
 // accumulation loop keeps only the accumulator, the prefetched row and the next entry live; the
 // weighted sums S = sum_q B_q, T = sum_q q B_q of the lane's g buckets are formed afterwards.
 // Row i + 1 and entry i + 2 are loaded while addition i runs.
-__global__ __launch_bounds__(256, TMED_ZIP_ACC_WAVES) void zip_accum_kernel(const uint16_t *__restrict__ keys,
+__global__ __launch_bounds__(256, kZipAccWaves) void zip_accum_kernel(const uint16_t *__restrict__ keys,
                                                            const uint32_t *__restrict__ vals, uint32_t cap,
                                                            uint32_t cnt, const int4 *__restrict__ pts,
                                                            ZipItems bsum, ZipItems out) {

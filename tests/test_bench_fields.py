@@ -105,12 +105,15 @@ def test_dump_outputs_whole_and_sampled(tmp_path):
 
 
 def test_kernel_digest_tracks_device_sources(tmp_path):
-    """The digest covers kernels.hip and every csrc header, nothing else."""
+    """The digest covers kernels.hip, the kernels_*.hip units and every csrc header, nothing else."""
     from tmed.srcdigest import kernel_src_digest
-    for f in ("kernels.hip", "a.h", "b.h"):
+    for f in ("kernels.hip", "kernels_tables.hip", "a.h", "b.h"):
         (tmp_path / f).write_text(f)
     d0 = kernel_src_digest(str(tmp_path))
     (tmp_path / "commit.hip").write_text("host only")
     assert kernel_src_digest(str(tmp_path)) == d0
     (tmp_path / "b.h").write_text("changed")
-    assert kernel_src_digest(str(tmp_path)) != d0
+    d1 = kernel_src_digest(str(tmp_path))
+    assert d1 != d0
+    (tmp_path / "kernels_tables.hip").write_text("changed")
+    assert kernel_src_digest(str(tmp_path)) != d1

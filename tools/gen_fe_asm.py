@@ -1,13 +1,12 @@
 #!/usr/bin/env python3
 """Generates tendermint-fork_amd/csrc/fe_cols.h: the column accumulation of the GF(2^255-19) field
-multiplication and squaring (fe25519.h) as explicit v_mad_i64_i32 schedules.
+multiplication and squaring (fe25519.h), carry chain included, as explicit v_mad_i64_i32 schedules.
 
 Why: written in C++, LLVM re-associates every column sum and adds the carry-rounding bias with a
 separate 64-bit v_lshl_add_u64 at the end (10 per square, ~7 per multiplication; see
 tools/micro/fe_micro.hip), and pinning the partial sums instead serialises the columns.  Here each
-column starts with ONE mad whose 64-bit addend is the bias, and the mads are issued round-robin
-over the ten columns, so consecutive mads never depend on each other (the nearest dependency is
->= 5 instructions away: no hazard wait states are needed inside the block).
+column's first mad takes its constant or the carry from below as its 64-bit addend, and a list
+schedule keeps dependent instructions at least 2 slots apart (3 in the paired schedules).
 
 The same schedule is emitted as plain C++ for the host build (tests/native/hostsim.cpp), so the
 CPU test-suite checks exactly the operand choice the device code uses.
@@ -18,8 +17,6 @@ import os
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "tendermint-fork_amd", "csrc", "fe_cols.h")
-
-MULT = ["", "2", "4", "19", "38"]  # x[m][i] = f_i * {1, 2, 4, 19, 38}[m]
 
 
 def mul_products():
@@ -32,97 +29,6 @@ def mul_products():
             b = ("g19", j) if k >= 10 else ("g", j)
             cols[k % 10].append((a, b))
     return cols
-
-
-def sq_products(D):
-    """(column, a, b) of D * f^2: the operand split of fe_sq_acc (fe25519.h)."""
-    cols = {k: [] for k in range(10)}
-    for i in range(10):
-        for j in range(i, 10):
-            k = i + j
-            wrap = k >= 10
-            oo = (i & 1) and (j & 1)
-            off = i < j
-            c2 = (1 if off else 0) + (1 if oo else 0) + (1 if D == 2 else 0)
-            if not wrap:
-                ma, mb = {0: (0, 0), 1: (1, 0), 2: (1, 1), 3: (2, 1)}[c2]
-            else:
-                on_b = (j & 1) or not (i & 1)
-                idx19 = j if on_b else i
-                rest, m19 = c2, 3
-                if (idx19 & 1) and rest > 0:
-                    m19, rest = 4, rest - 1
-                mo = rest
-                ma, mb = (mo, m19) if on_b else (m19, mo)
-            cols[k % 10].append((("x%s" % MULT[ma], i), ("x%s" % MULT[mb], j)))
-    return cols
-
-
-def schedule(cols):
-    order = []
-    r = 0
-    while any(len(c) > r for c in cols.values()):
-        for k in range(10):
-            if len(cols[k]) > r:
-                order.append((k, r, cols[k][r]))
-        r += 1
-    return order
-
-
-def check_distance(order):
-    last = {}
-    for pos, (k, r, _) in enumerate(order):
-        if k in last:
-            assert pos - last[k] >= 2, "dependent mads too close"
-        last[k] = pos
-
-
-def cname(op):
-    arr, i = op
-    if arr in ("f", "g"):
-        return "%s[%d]" % (arr, i)
-    return "%s[%d]" % (arr, i)
-
-
-def emit(fn_sig, order, inputs, doc):
-    idx = {}
-    operands_out = ['"=&v"(acc[%d])' % k for k in range(10)]
-    operands_in = []
-    for op in inputs:
-        idx[op] = 10 + len(operands_in)
-        operands_in.append('"v"(%s)' % cname(op))
-    ib_e = 10 + len(operands_in)
-    operands_in.append('"s"(be)')
-    ib_o = ib_e + 1
-    operands_in.append('"s"(bo)')
-    lines = []
-    for k, r, (a, b) in order:
-        addend = ("%%%d" % (ib_e if k % 2 == 0 else ib_o)) if r == 0 else "%%%d" % k
-        lines.append("v_mad_i64_i32 %%%d, vcc, %%%d, %%%d, %s" % (k, idx[a], idx[b], addend))
-    host = []
-    for k, r, (a, b) in order:
-        prod = "(int64_t)%s * (int64_t)%s" % (cname(a), cname(b))
-        if r == 0:
-            host.append("  acc[%d] = %s + %s;" % (k, "be" if k % 2 == 0 else "bo", prod))
-        else:
-            host.append("  acc[%d] += %s;" % (k, prod))
-    asm = "\n".join('      "%s\\n"' % l for l in lines)
-    return """%s
-%s {
-  const int64_t be = (int64_t)1 << 25, bo = (int64_t)1 << 24;  // column biases (fe_bias)
-#if defined(__HIP_DEVICE_COMPILE__)
-  asm(
-%s
-      : %s
-      : %s
-      : "vcc");
-#else
-%s
-#endif
-}
-""" % (doc, fn_sig, asm, ",\n        ".join(", ".join(operands_out[i:i + 5]) for i in range(0, 10, 5)),
-       ",\n        ".join(", ".join(operands_in[i:i + 6]) for i in range(0, len(operands_in), 6)),
-       "\n".join(host))
 
 
 # ---------------------------------------------------------------- fused column sums + carries
@@ -389,38 +295,13 @@ def main():
     parts = ["""// fe_cols.h — GENERATED by tools/gen_fe_asm.py (do not edit): the column sums of the field
 // multiplication and squaring of fe25519.h as explicit v_mad_i64_i32 schedules (gfx950).
 //
-// Each column k of the 64-bit accumulators starts with one mad whose addend is the rounding
-// bias of fe_carry64 (2^25 even / 2^24 odd column), then takes the column's remaining products;
-// the mads go round-robin over the ten columns, so no mad depends on one of the previous four.
-// LLVM, given the same sums in C++, adds the bias with an extra 64-bit v_lshl_add_u64 per
-// column (re-association; tools/micro/fe_micro.hip).  The host build compiles the identical
-// schedule as C++ (the CPU test-suite's simulation of the kernels).
+// Fused forms (fe25519.h "Fused carry"): the column sums AND the carry chain up to column 9 in
+// one schedule.  H[0] is column 0 before the wrap, H[1..9] are final; fe_fused_fin does the x19
+// wrap and extracts the limbs.  LLVM, given the same sums in C++, adds each column's constant
+// with an extra 64-bit v_lshl_add_u64 (re-association; tools/micro/fe_micro.hip).  The host build
+// compiles the identical schedule as C++ (the CPU test-suite's simulation of the kernels).
 #pragma once
 """]
-    order = schedule(mul_products())
-    check_distance(order)
-    ins = [("f", i) for i in range(10)] + [("f2", i) for i in (1, 3, 5, 7, 9)] + \
-          [("g", j) for j in range(10)] + [("g19", j) for j in range(1, 10)]
-    parts.append(emit("TMED_HD void fe_mul_cols(int64_t acc[10], const int32_t f[10], const int32_t f2[10], "
-                      "const int32_t g[10], const int32_t g19[10])", order, ins,
-                      "// acc[k] = bias_k + sum_{i+j = k mod 10} f_i g_j (x2 odd-odd, x19 wrapped): 100 mads"))
-    for D in (1, 2):
-        cols = sq_products(D)
-        order = schedule(cols)
-        check_distance(order)
-        used = []
-        for k, r, (a, b) in order:
-            for op in (a, b):
-                if op not in used:
-                    used.append(op)
-        used.sort(key=lambda o: (MULT.index(o[0][1:]), o[1]))
-        parts.append(emit("TMED_HD void fe_sq%d_cols(int64_t acc[10], const int32_t x[10], const int32_t x2[10], "
-                          "const int32_t x4[10], const int32_t x19[10], const int32_t x38[10])" % D, order, used,
-                          "// acc[k] = bias_k + the column sums of %s: 55 mads" % ("f^2" if D == 1 else "2 f^2")))
-    parts.append('''
-// ---- fused forms (the default; fe25519.h "Fused carry"): the column sums AND the carry chain up
-// to column 9 in one schedule.  H[0] is column 0 before the wrap, H[1..9] are final; fe_fused_fin
-// does the x19 wrap and extracts the limbs.''')
     check_bounds({k: [(("x" + a[0][1:], a[1]), ("x" + b[0][1:], b[1])) for a, b in v]
                   for k, v in mul_products().items()}, 3, 3)
     cols = mul_products()
