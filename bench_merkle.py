@@ -15,6 +15,12 @@ the leaves built on the host (the CommitSig protos marshalled by compiled code, 
 the transaction digests by hashlib) and passed through tmed_merkle_roots, in the same run, with
 both rates and their ratio in the line.  --legs a,b,... runs a subset.
 
+  partset_proofs  the whole of NewPartSetFromData (root AND every part's merkle.Proof, what
+           MakePartSet returns and store.SaveBlock persists) for 1,000 blocks x 1 MiB in 64 KiB
+           parts, next to tmed_partset_roots (the root alone: the capability there was) on the
+           same data in the same run: both rates, their ratio, the aunt kernel's device time
+  proofs_verify   Proof.Verify (PartSet.AddPart's check) of every proof the first leg produced
+
 Each line: objects/s and hashed bytes/s end to end through the C ABI (host buffers in, roots
 out: staging + H2D + kernels + D2H), next to the same work on one host core with hashlib
 (OpenSSL SHA-256) through oracle/merkle.py on a bounded sample ("port", cpu_baseline only)."""
@@ -55,7 +61,67 @@ def cpu_rate(fn, items, budget_s=3.0):
     return (n // 2) / dt, n // 2
 
 
-LEGS = ("valset", "headers", "partset", "commit_hash", "txs_hash")
+LEGS = ("valset", "headers", "partset", "commit_hash", "txs_hash", "partset_proofs", "proofs_verify")
+
+
+def proofs_legs(eng, TM, rng, legs, NB=1000, SZ=1 << 20, PART=65536):
+    """The lines of partset_proofs and proofs_verify (the second verifies the first one's proofs, so
+    the proofs are generated for either)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import proof_cases as P  # the restatement (checker only)
+    data = rng.integers(0, 256, NB * SZ + 8, dtype=np.uint8)
+    off = (np.arange(NB + 1, dtype=np.uint64) * SZ)
+    per = SZ // PART
+    kms, lines = [], []
+
+    def new():
+        out = TM.partset_proofs_packed(eng, data, off, PART)
+        kms.append(eng.last_kernel_ms())
+        return out
+
+    dt_new, (roots, part_off, lh, ao, au) = timed(new, reps=3)
+    dt_old, ref = timed(lambda: TM.partset_roots_packed(eng, data, off, PART), reps=3)
+    assert (roots == ref).all(), "roots of tmed_partset_proofs != tmed_partset_roots"
+    assert part_off.tolist() == list(range(0, NB * per + 1, per)) and int(ao[-1]) == au.shape[0]
+    for b in (0, NB - 1):
+        eroot, eproofs = P.partset_proofs(bytes(data[b * SZ:(b + 1) * SZ]), PART)
+        assert bytes(roots[b]) == eroot
+        for i, (_, _, elh, eau) in enumerate(eproofs):
+            k = b * per + i
+            assert bytes(lh[k]) == elh and [bytes(x) for x in au[int(ao[k]):int(ao[k + 1])]] == eau
+    if "partset_proofs" in legs:
+        lines.append({"metric": "PartSet with proofs: bytes/s (NewPartSetFromData)", "value": round(NB * SZ / dt_new, 1),
+                      "unit": "B/s", "blocks_per_s": round(NB / dt_new, 1), "seconds": round(dt_new, 4),
+                      "proofs": NB * per, "aunt_bytes": int(au.size), "aunt_kernel_ms": round(min(kms[1:]), 3),
+                      "note": "sizing call (host) + C call: H2D + leaf, level, aunt kernels + D2H of roots, leaf "
+                              "hashes and aunts",
+                      "roots_only": {"value": round(NB * SZ / dt_old, 1), "unit": "B/s",
+                                     "blocks_per_s": round(NB / dt_old, 1), "seconds": round(dt_old, 4),
+                                     "kind": "tmed_partset_roots on the same data"},
+                      "ratio_vs_roots_only": round(dt_old / dt_new, 3),
+                      "config": {"workload": "partset_proofs: %d blocks x %d B, %d B parts" % (NB, SZ, PART)}})
+    if "proofs_verify" in legs:
+        n = NB * per
+        leaf_off = (np.arange(n + 1, dtype=np.uint64) * PART)
+        totals = np.full(n, per, np.int64)
+        indexes = (np.arange(n, dtype=np.int64) % per)
+        root_of = (np.arange(n) // per).astype(np.uint32)
+        vms = []
+
+        def ver():
+            out = TM.verify_proofs_packed(eng, roots, data, leaf_off, lh, totals, indexes, ao, au, root_of)
+            vms.append(eng.last_kernel_ms())
+            return out
+
+        dt, codes = timed(ver, reps=3)
+        assert not codes.any(), "a generated proof does not verify"
+        lines.append({"metric": "Proof.Verify proofs/s (64 KiB parts)", "value": round(n / dt, 1), "unit": "proofs/s",
+                      "leaf_bytes_per_s": round(NB * SZ / dt, 1), "seconds": round(dt, 4),
+                      "verify_kernel_ms": round(min(vms[1:]), 3),
+                      "note": "C call: H2D of the parts and the proofs + merkle_verify_kernel + D2H of the codes",
+                      "config": {"workload": "proofs_verify: %d proofs of %d aunts over %d B parts"
+                                             % (n, int(ao[1]), PART)}})
+    return lines
 
 
 def commit_hash_leg(eng, TM, rng, C=1000, V=10_000):
@@ -173,8 +239,11 @@ def main():
             "partset": lambda: partset_leg(eng, TM, M, rng), "commit_hash": lambda: commit_hash_leg(eng, TM, rng),
             "txs_hash": lambda: txs_hash_leg(eng, TM, rng)}
     for leg in LEGS:
-        if leg in legs:
+        if leg in legs and leg in runs:
             print(json.dumps(runs[leg]()), flush=True)
+    if "partset_proofs" in legs or "proofs_verify" in legs:
+        for line in proofs_legs(eng, TM, rng, legs):
+            print(json.dumps(line), flush=True)
     eng.close()
 
 

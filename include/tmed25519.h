@@ -524,6 +524,75 @@ int tmed_commit_hashes(tmed_ctx *ctx, const tmed_commit *commits, size_t n, uint
 int tmed_txs_hashes(tmed_ctx *ctx, const uint8_t *txs, const uint64_t *tx_off, const uint32_t *block_off,
                     size_t n_blocks, uint8_t *out);
 
+/*
+ * Merkle proofs: merkle.ProofsFromByteSlices (crypto/merkle/proof.go:35-48, trailsFromByteSlices
+ * :216-237) and Proof.Verify (:52-68, computeHashFromAunts :151-181) for many trees per call.
+ *
+ * The three generators take the inputs of their root call and return, besides roots, every
+ * leaf's proof.  L = the call's leaf count; leaf i of the call is leaf (i - first leaf of its tree)
+ * of its tree, so Proof.Total and Proof.Index are implied by the tree's leaf count and the leaf's
+ * position.
+ *   roots        n_trees x 32, as the root call writes them (SHA-256("") for an empty tree, which
+ *                has no proofs)
+ *   leaf_hashes  L x 32: Proof.LeafHash = leafHash(leaf)
+ *   aunt_off     L + 1 entries, in units of hashes: leaf i's aunts are hashes
+ *                [aunt_off[i], aunt_off[i+1]) of aunts; a one-leaf tree gives none
+ *   aunts        32-byte hashes back to back, each leaf's in Proof.Aunts order (FlattenAunts,
+ *                proof.go:197-212): the leaf's sibling first, the root's child last
+ *   aunts_cap    bytes available at aunts; *aunts_len receives the bytes needed, 32 * aunt_off[L]
+ * Sizing follows tmed_vote_sign_bytes: with aunts == NULL the call fills aunt_off (and part_off)
+ * and *aunts_len on the host, touches no device (roots and leaf_hashes may be NULL) and returns
+ * TMED_OK (so a full call passes a non-NULL aunts even where no leaf has an aunt); with aunts_cap
+ * smaller than the bytes needed it returns TMED_ENOMEM and writes nothing.  TMED_EINVAL as
+ * the root calls.  The trees are built level by level as the root calls build them, every level
+ * kept; merkle_aunts_kernel then copies each leaf's siblings out.  After a generator
+ * tmed_last_kernel_ms reports that kernel's device time.  Submitted blocksync windows are
+ * collected first, as by every seam call.
+ *
+ * tmed_merkle_proofs: ProofsFromByteSlices over byte-slice trees (inputs of tmed_merkle_roots).
+ * tmed_partset_proofs: the whole of NewPartSetFromData (types/part_set.go:166-194) for n_blocks
+ * byte strings (inputs of tmed_partset_roots): part_off (n_blocks + 1 entries) receives block b's
+ * range of leaf indices, [part_off[b], part_off[b+1]); part p of block b is leaf part_off[b] + p
+ * and its bytes are the p-th part_size chunk of the block.
+ * tmed_txs_proofs: the tree of Txs.Proof (types/tx.go:80-93), whose leaves are SHA-256(tx) (inputs
+ * of tmed_txs_hashes); leaf_hashes[i] = leafHash(tx.Hash()).
+ */
+int tmed_merkle_proofs(tmed_ctx *ctx, const uint8_t *leaves, const uint64_t *leaf_off, const uint32_t *tree_off,
+                       size_t n_trees, uint8_t *roots, uint8_t *leaf_hashes, uint64_t *aunt_off, uint8_t *aunts,
+                       size_t aunts_cap, size_t *aunts_len);
+int tmed_partset_proofs(tmed_ctx *ctx, const uint8_t *data, const uint64_t *data_off, size_t n_blocks,
+                        uint32_t part_size, uint8_t *roots, uint32_t *part_off, uint8_t *leaf_hashes,
+                        uint64_t *aunt_off, uint8_t *aunts, size_t aunts_cap, size_t *aunts_len);
+int tmed_txs_proofs(tmed_ctx *ctx, const uint8_t *txs, const uint64_t *tx_off, const uint32_t *block_off,
+                    size_t n_blocks, uint8_t *roots, uint8_t *leaf_hashes, uint64_t *aunt_off, uint8_t *aunts,
+                    size_t aunts_cap, size_t *aunts_len);
+
+/* out_code of tmed_merkle_proofs_verify, in the order Proof.Verify checks (proof.go:52-68) */
+#define TMED_PROOF_OK 0
+#define TMED_PROOF_NEGATIVE_TOTAL 1 /* "proof total must be positive" (Total < 0) */
+#define TMED_PROOF_NEGATIVE_INDEX 2 /* "proof index cannot be negative" */
+#define TMED_PROOF_LEAF_HASH 3      /* leafHash(leaf) differs from the proof's LeafHash */
+#define TMED_PROOF_ROOT_HASH 4      /* the computed root differs, or computeHashFromAunts returns nil */
+
+/*
+ * Proof.Verify(rootHash, leaf) for n proofs, one lane each.  Proof i: Total = totals[i], Index =
+ * indexes[i], LeafHash = leaf_hashes[32 i ..), Aunts = hashes [aunt_off[i], aunt_off[i+1]) of aunts
+ * (units of hashes, as the generators write them); its leaf is leaves[leaf_off[i] .. leaf_off[i+1])
+ * and its root is roots[32 r ..) with r = root_of[i] (root_of == NULL: r = i); roots holds n_roots
+ * hashes.  out_code[i] is one of TMED_PROOF_*.  TMED_PROOF_ROOT_HASH also covers every case in
+ * which computeHashFromAunts returns nil: index >= total, total == 0, or an aunt count other than
+ * the path length of (index, total), in which case no aunt is read.  Any aunt count is accepted;
+ * Proof.ValidateBasic's limit of 100 aunts (proof.go:16, :108-110) is the caller's check, and a path
+ * is at most 63 long.  On a non-zero code the caller runs the Go method for the error's text.
+ * TMED_EINVAL for malformed calls only: a NULL array, offsets that decrease, a leaf longer than
+ * 2^32 - 65 bytes, a root index >= n_roots.  After the call tmed_last_kernel_ms reports
+ * merkle_verify_kernel's device time.
+ */
+int tmed_merkle_proofs_verify(tmed_ctx *ctx, size_t n, const uint8_t *roots, size_t n_roots, const uint32_t *root_of,
+                              const uint8_t *leaves, const uint64_t *leaf_off, const uint8_t *leaf_hashes,
+                              const int64_t *totals, const int64_t *indexes, const uint64_t *aunt_off,
+                              const uint8_t *aunts, uint8_t *out_code);
+
 /* ------------------------------------------------- blocksync replay (f4) */
 
 /*

@@ -19,6 +19,12 @@
 // tree.go equals pairing adjacent nodes level by level and promoting an odd last node
 // (HashFromByteSlicesIterative, tree.go:57-101, is asserted equal by tree_test.go:104-116),
 // which is what the level kernel does.  Work per inner node: 2 SHA-256 blocks.
+//
+// Proofs (crypto/merkle/proof.go:35-68, 151-181, 216-237; types/part_set.go:166-194 keeps every
+// part's proof, types/tx.go:80-93 builds one per transaction): the proof route runs the same leaf
+// and level kernels into one buffer that keeps every level, then merkle_aunts_kernel copies each
+// leaf's siblings out (no hashing); merkle_verify_kernel is Proof.Verify, one lane per proof.  The
+// path arithmetic both share with the host sizing is merkle_path.h.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -30,6 +36,7 @@
 #include "../../include/tmed25519.h"
 #include "commitsig_leaf.h"
 #include "ctx.h"
+#include "merkle_path.h"
 #include "sha256.h"
 
 namespace tmed {
@@ -180,6 +187,106 @@ __global__ __launch_bounds__(256) void merkle_emit_kernel(const Digest *__restri
   uint32_t *o = reinterpret_cast<uint32_t *>(roots + 32 * (size_t)t);
 #pragma unroll
   for (int k = 0; k < 8; k++) o[k] = bswap32(st[k]);
+}
+
+// ---- Merkle proofs (crypto/merkle/proof.go) ------------------------------------------------------
+// The proof route keeps every level: level l of all trees lies tree-contiguous at nodes + lvl_off[l]
+// (tree t's nodes at tab[l * (ntrees + 1) + t] ..), built by merkle_level_kernel from level l - 1.
+// A tree that is down to one node carries it through the remaining levels, so the last level holds
+// every root.
+
+// Proof.Aunts and Proof.LeafHash of every leaf, no hashing: eight lanes per leaf, lane w of a leaf
+// copies digest word w.  The leaf at position p of its tree walks the kept levels: at a level of c
+// nodes its node's sibling p ^ 1 is the next aunt if it exists (p ^ 1 < c; an odd last node is
+// promoted and contributes nothing), then p >>= 1, until c = 1 (merkle_path.h merkle_aunt_count is
+// the same walk and sized aunt_off).  Each group of eight lanes reads one whole 32-byte digest and
+// writes one whole 32-byte hash per step, so every store instruction fills 32-byte sectors.
+__global__ __launch_bounds__(256) void merkle_aunts_kernel(const Digest *__restrict__ nodes,
+                                                           const uint64_t *__restrict__ lvl_off,
+                                                           const uint32_t *__restrict__ tab, uint32_t ntrees,
+                                                           uint32_t nlevels, uint32_t nleaves,
+                                                           const uint64_t *__restrict__ aunt_off,
+                                                           uint32_t *__restrict__ aunts,
+                                                           uint32_t *__restrict__ leaf_hashes) {
+  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t i = (uint32_t)(j >> 3), w = (uint32_t)j & 7u;
+  if ((j >> 3) >= nleaves) return;
+  uint32_t lo = 0, hi = ntrees;  // last t with tab[t] <= i (empty trees are skipped)
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (tab[mid] <= i) lo = mid; else hi = mid;
+  }
+  const uint32_t t = lo;
+  uint32_t p = i - tab[t];
+  leaf_hashes[8 * (size_t)i + w] = bswap32(nodes[i].w[w]);
+  const uint64_t a0 = aunt_off[i], a1 = aunt_off[i + 1];
+  uint64_t a = a0;
+  for (uint32_t l = 0; l < nlevels && a < a1; l++) {
+    const uint32_t *tb = tab + (size_t)l * (ntrees + 1);
+    const uint32_t base = tb[t], c = tb[t + 1] - base;
+    if (c <= 1) break;
+    const uint32_t sib = p ^ 1u;
+    if (sib < c) {
+      aunts[8 * a + w] = bswap32(nodes[lvl_off[l] + base + sib].w[w]);
+      a++;
+    }
+    p >>= 1;
+  }
+}
+
+__device__ __forceinline__ void load_hash_be(uint32_t st[8], const uint8_t *h) {
+  const uint4 *p = reinterpret_cast<const uint4 *>(h);  // hashes lie at multiples of 32 bytes
+  const uint4 a = p[0], b = p[1];
+  st[0] = bswap32(a.x); st[1] = bswap32(a.y); st[2] = bswap32(a.z); st[3] = bswap32(a.w);
+  st[4] = bswap32(b.x); st[5] = bswap32(b.y); st[6] = bswap32(b.z); st[7] = bswap32(b.w);
+}
+
+// Proof.Verify (proof.go:52-68), one lane per proof; code[i] = TMED_PROOF_*.  The checks in the
+// reference's order; computeHashFromAunts (:151-181) as merkle_path's top-down walk (path length
+// and side mask, no aunt read unless the count fits) and a bottom-up fold of the aunts.
+__global__ __launch_bounds__(256) void merkle_verify_kernel(const uint8_t *__restrict__ leaves,
+                                                            const uint64_t *__restrict__ leaf_off,
+                                                            const uint8_t *__restrict__ leaf_hashes,
+                                                            const int64_t *__restrict__ totals,
+                                                            const int64_t *__restrict__ indexes,
+                                                            const uint64_t *__restrict__ aunt_off,
+                                                            const uint8_t *__restrict__ aunts,
+                                                            const uint8_t *__restrict__ roots,
+                                                            const uint32_t *__restrict__ root_of, uint32_t n,
+                                                            uint8_t *__restrict__ code) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t total = totals[i], index = indexes[i];
+  if (total < 0) { code[i] = TMED_PROOF_NEGATIVE_TOTAL; return; }
+  if (index < 0) { code[i] = TMED_PROOF_NEGATIVE_INDEX; return; }
+  const uint64_t o0 = leaf_off[i], o1 = leaf_off[i + 1];
+  uint32_t h[8], x[8];
+  sha256_prefixed(h, 1, 0x00, leaves + o0, (uint32_t)(o1 - o0));
+  load_hash_be(x, leaf_hashes + 32 * (size_t)i);
+  bool same = true;
+#pragma unroll
+  for (int k = 0; k < 8; k++) same &= h[k] == x[k];
+  if (!same) { code[i] = TMED_PROOF_LEAF_HASH; return; }
+  uint32_t d;
+  uint64_t mask;
+  const uint64_t a0 = aunt_off[i];
+  if (!merkle_path(index, total, &d, &mask) || aunt_off[i + 1] - a0 != d) {
+    code[i] = TMED_PROOF_ROOT_HASH;
+    return;
+  }
+#pragma unroll 1
+  for (uint32_t k = 0; k < d; k++) {
+    uint32_t st[8];
+    load_hash_be(x, aunts + 32 * (a0 + k));
+    if ((mask >> k) & 1) sha256_inner(st, x, h);
+    else sha256_inner(st, h, x);
+#pragma unroll
+    for (int q = 0; q < 8; q++) h[q] = st[q];
+  }
+  load_hash_be(x, roots + 32 * (size_t)(root_of ? root_of[i] : i));
+#pragma unroll
+  for (int k = 0; k < 8; k++) same &= h[k] == x[k];
+  code[i] = same ? TMED_PROOF_OK : TMED_PROOF_ROOT_HASH;
 }
 
 static uint32_t blocks_for(size_t n) { return (uint32_t)((n + 255) / 256); }
@@ -449,6 +556,190 @@ int commit_hashes_locked(tmed_ctx *c, const tmed_commit *commits, size_t n, cons
   return TMED_OK;
 }
 
+// ---- Merkle proofs --------------------------------------------------------------------------
+// The caller's output arrays of a generator (include/tmed25519.h).
+struct ProofOut {
+  uint8_t *roots, *leaf_hashes;
+  uint64_t *aunt_off;
+  uint8_t *aunts;
+  size_t aunts_cap;
+  size_t *aunts_len;
+};
+
+// Every level of every tree on the device, then the aunts: leaves (host) -> o (host).  ao: the
+// leaves' aunt offsets (sized by the caller).  ctx->mu held.
+int proofs_locked(tmed_ctx *c, const uint8_t *leaves, const uint64_t *leaf_off, size_t L,
+                  const std::vector<uint32_t> &counts, bool txs, const std::vector<uint64_t> &ao, const ProofOut &o) {
+  const size_t T = counts.size();
+  const size_t bytes = leaf_off[L] - leaf_off[0];
+  const size_t need = 32 * (size_t)ao[L];
+  // the per-level base tables, all of them before the first launch
+  std::vector<uint32_t> cnt(counts), tab;
+  std::vector<uint64_t> lvl;
+  uint64_t nodes = 0;
+  for (;;) {
+    const size_t at = tab.size();
+    tab.resize(at + T + 1);
+    lvl.push_back(nodes);
+    tab[at] = 0;
+    bool more = false;
+    for (size_t t = 0; t < T; t++) {
+      tab[at + t + 1] = tab[at + t] + cnt[t];
+      if (cnt[t] > 1) more = true;
+      cnt[t] = (cnt[t] + 1) / 2;  // 0 -> 0, 1 -> 1
+    }
+    nodes += tab[at + T];
+    if (!more) break;
+  }
+  const size_t nlev = lvl.size();
+  const size_t o_tab = align256(nlev * 8), o_leaf = align256(need), o_root = align256(o_leaf + 32 * L);
+  (void)hipSetDevice(c->device);
+  hipStream_t s = c->stream;
+  hipError_t e = c->d_msg.ensure(bytes + 16);
+  if (e == hipSuccess) e = c->d_off.ensure((L + 1) * 8);
+  if (e == hipSuccess) e = c->d_merkle_lv.ensure(std::max<uint64_t>(nodes, 1) * sizeof(Digest));
+  if (e == hipSuccess) e = c->d_merkle_tab.ensure(o_tab + tab.size() * 4);
+  if (e == hipSuccess) e = c->d_proof_off.ensure((L + 1) * 8);
+  if (e == hipSuccess) e = c->d_proof_out.ensure(o_root + 32 * T);
+  if (e != hipSuccess) return map_err(e);
+  Digest *lv = (Digest *)c->d_merkle_lv.p;
+  uint8_t *d_tab = (uint8_t *)c->d_merkle_tab.p, *d_res = (uint8_t *)c->d_proof_out.p;
+  const uint64_t *d_lvl = (const uint64_t *)d_tab;
+  const uint32_t *d_t = (const uint32_t *)(d_tab + o_tab);
+  std::vector<uint64_t> off(L + 1);
+  for (size_t i = 0; i <= L; i++) off[i] = leaf_off[i] - leaf_off[0];
+  if (bytes) e = hipMemcpyAsync(c->d_msg.p, leaves + leaf_off[0], bytes, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(c->d_off.p, off.data(), (L + 1) * 8, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_tab, lvl.data(), nlev * 8, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_tab + o_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(c->d_proof_off.p, ao.data(), (L + 1) * 8, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && L) {
+    if (txs)
+      hipLaunchKernelGGL(txs_leaf_kernel, dim3(blocks_for(L)), dim3(256), 0, s, (const uint8_t *)c->d_msg.p,
+                         (const uint64_t *)c->d_off.p, (uint32_t)L, lv);
+    else
+      hipLaunchKernelGGL(merkle_leaf_kernel, dim3(blocks_for(L)), dim3(256), 0, s, (const uint8_t *)c->d_msg.p,
+                         (const uint64_t *)c->d_off.p, (uint32_t)L, lv);
+    e = hipGetLastError();
+  }
+  for (size_t l = 0; e == hipSuccess && l + 1 < nlev; l++) {
+    const uint32_t nout = tab[(l + 1) * (T + 1) + T];
+    hipLaunchKernelGGL(merkle_level_kernel, dim3(blocks_for(nout)), dim3(256), 0, s, lv + lvl[l], d_t + l * (T + 1),
+                       d_t + (l + 1) * (T + 1), (uint32_t)T, nout, lv + lvl[l + 1]);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(merkle_emit_kernel, dim3(blocks_for(T)), dim3(256), 0, s, lv + lvl[nlev - 1],
+                       d_t + (nlev - 1) * (T + 1), (uint32_t)T, d_res + o_root);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipEventRecord(c->ev0, s);
+  if (e == hipSuccess && L) {
+    hipLaunchKernelGGL(merkle_aunts_kernel, dim3(blocks_for(8 * L)), dim3(256), 0, s, lv, d_lvl, d_t, (uint32_t)T,
+                       (uint32_t)nlev, (uint32_t)L, (const uint64_t *)c->d_proof_off.p, (uint32_t *)d_res,
+                       (uint32_t *)(d_res + o_leaf));
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipEventRecord(c->ev1, s);
+  if (e == hipSuccess && need) e = hipMemcpyAsync(o.aunts, d_res, need, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && L) e = hipMemcpyAsync(o.leaf_hashes, d_res + o_leaf, 32 * L, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(o.roots, d_res + o_root, 32 * T, hipMemcpyDeviceToHost, s);
+  // (a failed call still waits: the host vectors above are the sources of queued copies)
+  const hipError_t es = hipStreamSynchronize(s);
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return map_err(e);
+  (void)hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1);
+  return TMED_OK;
+}
+
+// The common tail of the three generators: size the aunts on the host (merkle_path.h), answer a
+// sizing call or a too small buffer there, else run the device route.
+int proofs_from_host_leaves(tmed_ctx *c, const uint8_t *leaves, const uint64_t *leaf_off, size_t L,
+                            const std::vector<uint32_t> &counts, bool txs, const ProofOut &o) {
+  std::vector<uint64_t> ao(L + 1);
+  size_t i = 0;
+  ao[0] = 0;
+  for (const uint32_t n : counts)
+    for (uint32_t p = 0; p < n; p++, i++) ao[i + 1] = ao[i] + merkle_aunt_count(p, n);
+  const size_t need = 32 * (size_t)ao[L];
+  if (o.aunts && o.aunts_cap < need) return TMED_ENOMEM;
+  if (o.aunts) {
+    if (!o.roots || (L && !o.leaf_hashes)) return TMED_EINVAL;
+    int rc;
+    {
+      std::lock_guard<std::mutex> lk(c->mu);
+      rc = bs_collect_submitted(c);  // submitted blocksync windows are collected first (the seam's rule)
+      if (rc == TMED_OK) rc = proofs_locked(c, leaves, leaf_off, L, counts, txs, ao, o);
+    }
+    bs_release_collected(c);
+    if (rc != TMED_OK) return rc;
+  }
+  memcpy(o.aunt_off, ao.data(), (L + 1) * 8);
+  *o.aunts_len = need;
+  return TMED_OK;
+}
+
+// The caller's arrays of tmed_merkle_proofs_verify: leaves and aunts from their first used byte.
+struct ProofIn {
+  size_t n;
+  const uint8_t *roots;
+  size_t n_roots;
+  const uint32_t *root_of;
+  const uint8_t *leaves;
+  size_t leaf_bytes;
+  const uint8_t *leaf_hashes;
+  const int64_t *totals, *indexes;
+  const uint8_t *aunts;
+  size_t n_aunts;
+};
+
+// Proofs (host) -> codes (host).  off: the n + 1 leaf offsets, then the n + 1 aunt offsets, both
+// from 0.  The aunts lie in d_merkle_lv (the generators' digest buffer).  ctx->mu held.
+int verify_proofs_locked(tmed_ctx *c, const ProofIn &in, const std::vector<uint64_t> &off, uint8_t *out_code) {
+  const size_t n = in.n;
+  // d_proof_in: leaf hashes | roots | totals | indexes | root indexes
+  const size_t o_root = align256(32 * n), o_tot = align256(o_root + 32 * in.n_roots),
+               o_idx = align256(o_tot + 8 * n), o_rof = align256(o_idx + 8 * n);
+  (void)hipSetDevice(c->device);
+  hipStream_t s = c->stream;
+  hipError_t e = c->d_msg.ensure(in.leaf_bytes + 16);
+  if (e == hipSuccess) e = c->d_off.ensure((n + 1) * 8);
+  if (e == hipSuccess) e = c->d_proof_off.ensure((n + 1) * 8);
+  if (e == hipSuccess) e = c->d_merkle_lv.ensure(std::max<size_t>(in.n_aunts, 1) * sizeof(Digest));
+  if (e == hipSuccess) e = c->d_proof_in.ensure(o_rof + (in.root_of ? 4 * n : 0));
+  if (e == hipSuccess) e = c->d_proof_out.ensure(n);
+  if (e != hipSuccess) return map_err(e);
+  uint8_t *d_in = (uint8_t *)c->d_proof_in.p;
+  if (in.leaf_bytes) e = hipMemcpyAsync(c->d_msg.p, in.leaves, in.leaf_bytes, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(c->d_off.p, off.data(), (n + 1) * 8, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(c->d_proof_off.p, off.data() + n + 1, (n + 1) * 8, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && in.n_aunts)
+    e = hipMemcpyAsync(c->d_merkle_lv.p, in.aunts, 32 * in.n_aunts, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_in, in.leaf_hashes, 32 * n, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_in + o_root, in.roots, 32 * in.n_roots, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_in + o_tot, in.totals, 8 * n, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_in + o_idx, in.indexes, 8 * n, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && in.root_of) e = hipMemcpyAsync(d_in + o_rof, in.root_of, 4 * n, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipEventRecord(c->ev0, s);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(merkle_verify_kernel, dim3(blocks_for(n)), dim3(256), 0, s, (const uint8_t *)c->d_msg.p,
+                       (const uint64_t *)c->d_off.p, (const uint8_t *)d_in, (const int64_t *)(d_in + o_tot),
+                       (const int64_t *)(d_in + o_idx), (const uint64_t *)c->d_proof_off.p,
+                       (const uint8_t *)c->d_merkle_lv.p, (const uint8_t *)(d_in + o_root),
+                       in.root_of ? (const uint32_t *)(d_in + o_rof) : nullptr, (uint32_t)n,
+                       (uint8_t *)c->d_proof_out.p);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipEventRecord(c->ev1, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(out_code, c->d_proof_out.p, n, hipMemcpyDeviceToHost, s);
+  // (a failed call still waits: off is the source of queued copies)
+  const hipError_t es = hipStreamSynchronize(s);
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return map_err(e);
+  (void)hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1);
+  return TMED_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -605,6 +896,142 @@ int tmed_partset_roots(tmed_ctx *c, const uint8_t *data, const uint64_t *data_of
   const size_t L = off.size() - 1;
   if (L > 0xffffffffu || (L && !data)) return TMED_EINVAL;
   return roots_from_host_leaves(c, data, off.data(), L, counts, roots);
+}
+
+// ---- Merkle proofs (the generators share proofs_from_host_leaves; arguments checked as the root calls)
+
+int tmed_merkle_proofs(tmed_ctx *c, const uint8_t *leaves, const uint64_t *leaf_off, const uint32_t *tree_off,
+                       size_t n_trees, uint8_t *roots, uint8_t *leaf_hashes, uint64_t *aunt_off, uint8_t *aunts,
+                       size_t aunts_cap, size_t *aunts_len) {
+  if (!c || !aunt_off || !aunts_len || (n_trees && (!tree_off || !leaf_off))) return TMED_EINVAL;
+  if (n_trees == 0) {
+    aunt_off[0] = 0;
+    *aunts_len = 0;
+    return TMED_OK;
+  }
+  const size_t L = tree_off[n_trees];
+  if (tree_off[0] != 0 || L > 0xffffffffu) return TMED_EINVAL;
+  try {
+    std::vector<uint32_t> counts(n_trees);
+    for (size_t t = 0; t < n_trees; t++) {
+      if (tree_off[t + 1] < tree_off[t]) return TMED_EINVAL;
+      counts[t] = tree_off[t + 1] - tree_off[t];
+    }
+    for (size_t i = 0; i < L; i++)
+      if (leaf_off[i + 1] < leaf_off[i] || leaf_off[i + 1] - leaf_off[i] > 0xffffffffu - 64) return TMED_EINVAL;
+    if (L && leaf_off[L] > leaf_off[0] && !leaves) return TMED_EINVAL;
+    return proofs_from_host_leaves(c, leaves, leaf_off, L, counts, /*txs=*/false,
+                                   ProofOut{roots, leaf_hashes, aunt_off, aunts, aunts_cap, aunts_len});
+  } catch (const std::bad_alloc &) {
+    return TMED_ENOMEM;
+  } catch (...) {
+    return TMED_EINTERNAL;
+  }
+}
+
+int tmed_txs_proofs(tmed_ctx *c, const uint8_t *txs, const uint64_t *tx_off, const uint32_t *block_off,
+                    size_t n_blocks, uint8_t *roots, uint8_t *leaf_hashes, uint64_t *aunt_off, uint8_t *aunts,
+                    size_t aunts_cap, size_t *aunts_len) {
+  if (!c || !aunt_off || !aunts_len || (n_blocks && (!block_off || !tx_off))) return TMED_EINVAL;
+  if (n_blocks == 0) {
+    aunt_off[0] = 0;
+    *aunts_len = 0;
+    return TMED_OK;
+  }
+  const size_t L = block_off[n_blocks];
+  if (block_off[0] != 0 || L > 0xffffffffu) return TMED_EINVAL;
+  try {
+    std::vector<uint32_t> counts(n_blocks);
+    for (size_t b = 0; b < n_blocks; b++) {
+      if (block_off[b + 1] < block_off[b]) return TMED_EINVAL;
+      counts[b] = block_off[b + 1] - block_off[b];
+    }
+    for (size_t i = 0; i < L; i++)
+      if (tx_off[i + 1] < tx_off[i] || tx_off[i + 1] - tx_off[i] > 0xffffffffu - 64) return TMED_EINVAL;
+    if (L && tx_off[L] > tx_off[0] && !txs) return TMED_EINVAL;
+    return proofs_from_host_leaves(c, txs, tx_off, L, counts, /*txs=*/true,
+                                   ProofOut{roots, leaf_hashes, aunt_off, aunts, aunts_cap, aunts_len});
+  } catch (const std::bad_alloc &) {
+    return TMED_ENOMEM;
+  } catch (...) {
+    return TMED_EINTERNAL;
+  }
+}
+
+int tmed_partset_proofs(tmed_ctx *c, const uint8_t *data, const uint64_t *data_off, size_t n_blocks,
+                        uint32_t part_size, uint8_t *roots, uint32_t *part_off, uint8_t *leaf_hashes,
+                        uint64_t *aunt_off, uint8_t *aunts, size_t aunts_cap, size_t *aunts_len) {
+  if (!c || part_size == 0 || !aunt_off || !aunts_len || !part_off || (n_blocks && !data_off)) return TMED_EINVAL;
+  if (n_blocks == 0) {
+    aunt_off[0] = 0;
+    part_off[0] = 0;
+    *aunts_len = 0;
+    return TMED_OK;
+  }
+  try {
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> counts(n_blocks), poff(n_blocks + 1);
+    off.push_back(data_off[0]);
+    for (size_t b = 0; b < n_blocks; b++) {
+      if (data_off[b + 1] < data_off[b]) return TMED_EINVAL;
+      const uint64_t len = data_off[b + 1] - data_off[b];
+      const uint64_t parts = (len + part_size - 1) / part_size;  // types/part_set.go:168
+      if (parts > 0xffffffffu || off.size() - 1 + parts > 0xffffffffu) return TMED_EINVAL;
+      counts[b] = (uint32_t)parts;
+      poff[b] = (uint32_t)(off.size() - 1);
+      for (uint64_t p = 0; p < parts; p++) off.push_back(std::min(data_off[b] + (p + 1) * part_size, data_off[b + 1]));
+    }
+    const size_t L = off.size() - 1;
+    poff[n_blocks] = (uint32_t)L;
+    if (L && !data) return TMED_EINVAL;
+    const int rc = proofs_from_host_leaves(c, data, off.data(), L, counts, /*txs=*/false,
+                                           ProofOut{roots, leaf_hashes, aunt_off, aunts, aunts_cap, aunts_len});
+    if (rc == TMED_OK) memcpy(part_off, poff.data(), (n_blocks + 1) * 4);
+    return rc;
+  } catch (const std::bad_alloc &) {
+    return TMED_ENOMEM;
+  } catch (...) {
+    return TMED_EINTERNAL;
+  }
+}
+
+int tmed_merkle_proofs_verify(tmed_ctx *c, size_t n, const uint8_t *roots, size_t n_roots, const uint32_t *root_of,
+                              const uint8_t *leaves, const uint64_t *leaf_off, const uint8_t *leaf_hashes,
+                              const int64_t *totals, const int64_t *indexes, const uint64_t *aunt_off,
+                              const uint8_t *aunts, uint8_t *out_code) {
+  if (!c) return TMED_EINVAL;
+  if (n == 0) return TMED_OK;
+  if (!roots || !leaf_off || !leaf_hashes || !totals || !indexes || !aunt_off || !out_code || n > 0xffffffffu)
+    return TMED_EINVAL;
+  for (size_t i = 0; i < n; i++) {
+    if (leaf_off[i + 1] < leaf_off[i] || leaf_off[i + 1] - leaf_off[i] > 0xffffffffu - 64) return TMED_EINVAL;
+    if (aunt_off[i + 1] < aunt_off[i]) return TMED_EINVAL;
+    if ((root_of ? root_of[i] : i) >= n_roots) return TMED_EINVAL;
+  }
+  const size_t bytes = leaf_off[n] - leaf_off[0];
+  const uint64_t A = aunt_off[n] - aunt_off[0];
+  if ((bytes && !leaves) || (A && !aunts) || A > (~(size_t)0 >> 5)) return TMED_EINVAL;
+  int rc;
+  try {
+    std::vector<uint64_t> off(2 * (n + 1));  // leaf offsets, then aunt offsets, both from 0
+    for (size_t i = 0; i <= n; i++) {
+      off[i] = leaf_off[i] - leaf_off[0];
+      off[n + 1 + i] = aunt_off[i] - aunt_off[0];
+    }
+    const ProofIn in{n, roots, n_roots, root_of, bytes ? leaves + leaf_off[0] : nullptr, bytes, leaf_hashes, totals,
+                     indexes, A ? aunts + 32 * aunt_off[0] : nullptr, (size_t)A};
+    {
+      std::lock_guard<std::mutex> lk(c->mu);
+      rc = bs_collect_submitted(c);  // submitted blocksync windows are collected first (the seam's rule)
+      if (rc == TMED_OK) rc = verify_proofs_locked(c, in, off, out_code);
+    }
+    bs_release_collected(c);
+  } catch (const std::bad_alloc &) {
+    return TMED_ENOMEM;
+  } catch (...) {
+    return TMED_EINTERNAL;
+  }
+  return rc;
 }
 
 }  // extern "C"

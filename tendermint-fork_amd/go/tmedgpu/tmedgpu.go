@@ -847,6 +847,243 @@ func (e *Engine) TxsHashes(blocks [][][]byte) ([][32]byte, error) {
 	return append([][32]byte(nil), out...), nil
 }
 
+// Proof mirrors merkle.Proof (crypto/merkle/proof.go:24-29).  LeafHash and every aunt are 32-byte
+// slices of the buffers one proofs call returns: nothing is allocated per proof or per aunt.
+type Proof struct {
+	Total    int64
+	Index    int64
+	LeafHash []byte
+	Aunts    [][]byte
+}
+
+// TreeProofs is merkle.ProofsFromByteSlices' result for one tree: its root and one proof per leaf.
+type TreeProofs struct {
+	Root   [32]byte
+	Proofs []Proof
+}
+
+// Codes of VerifyProofs, in the order Proof.Verify checks (crypto/merkle/proof.go:52-68).
+const (
+	ProofOK            = C.TMED_PROOF_OK
+	ProofNegativeTotal = C.TMED_PROOF_NEGATIVE_TOTAL
+	ProofNegativeIndex = C.TMED_PROOF_NEGATIVE_INDEX
+	ProofLeafHash      = C.TMED_PROOF_LEAF_HASH
+	ProofRootHash      = C.TMED_PROOF_ROOT_HASH
+)
+
+func (a *arena) u64(v []uint64) *C.uint64_t {
+	if len(v) == 0 {
+		return nil
+	}
+	p := a.alloc(uintptr(len(v)) * 8)
+	copy(unsafe.Slice((*uint64)(p), len(v)), v)
+	return (*C.uint64_t)(p)
+}
+
+// flatten concatenates the byte slices of every group: the bytes (8 spare at the end: the device
+// reader may touch the last dword), the slices' offsets and the groups' ranges of slice indices.
+func flatten(groups [][][]byte) ([]byte, []uint64, []uint32) {
+	var flat []byte
+	itemOff := []uint64{0}
+	groupOff := []uint32{0}
+	for _, g := range groups {
+		for _, x := range g {
+			flat = append(flat, x...)
+			itemOff = append(itemOff, uint64(len(flat)))
+		}
+		groupOff = append(groupOff, uint32(len(itemOff)-1))
+	}
+	return append(flat, make([]byte, 8)...), itemOff, groupOff
+}
+
+// runProofs drives one generator: the sizing call (aunts = NULL: the aunt offsets and the byte
+// count, computed on the host), then the real call into Go buffers of exactly that size.  The
+// buffers hold no Go pointers and are only used during the call (cgo pointer rules).
+func runProofs(a *arena, nt, nl int, call func(roots, lh *C.uint8_t, ao *C.uint64_t, au *C.uint8_t, room C.size_t,
+	need *C.size_t) C.int) ([][32]byte, []byte, []uint64, []byte, error) {
+	ao := (*[1 << 26]C.uint64_t)(a.alloc(uintptr(nl+1) * 8))[: nl+1 : nl+1]
+	var need C.size_t
+	if rc := call(nil, nil, &ao[0], nil, 0, &need); rc != 0 {
+		return nil, nil, nil, nil, errors.New(C.GoString(C.tmed_strerror(rc)))
+	}
+	roots := make([][32]byte, nt)
+	leafHashes := make([]byte, 32*nl+32)
+	aunts := make([]byte, int(need)+32)
+	if rc := call((*C.uint8_t)(unsafe.Pointer(&roots[0])), (*C.uint8_t)(unsafe.Pointer(&leafHashes[0])), &ao[0],
+		(*C.uint8_t)(unsafe.Pointer(&aunts[0])), need, &need); rc != 0 {
+		return nil, nil, nil, nil, errors.New(C.GoString(C.tmed_strerror(rc)))
+	}
+	auntOff := make([]uint64, nl+1)
+	for i := range auntOff {
+		auntOff[i] = uint64(ao[i])
+	}
+	return roots, leafHashes[:32*nl], auntOff, aunts[:int(need)], nil
+}
+
+// treeProofs cuts a generator's flat outputs into per-tree proofs: tree t holds leaves
+// [off[t], off[t+1]).  Three allocations for the whole call (the trees, the proofs, the aunt slice
+// headers); every hash is a slice of leafHashes or aunts.
+func treeProofs(roots [][32]byte, off []uint32, leafHashes []byte, auntOff []uint64, aunts []byte) []TreeProofs {
+	out := make([]TreeProofs, len(roots))
+	nl := int(off[len(roots)])
+	all := make([]Proof, nl)
+	hashes := make([][]byte, len(aunts)/32)
+	for k := range hashes {
+		hashes[k] = aunts[32*k : 32*k+32 : 32*k+32]
+	}
+	for t := range out {
+		lo, hi := int(off[t]), int(off[t+1])
+		out[t].Root = roots[t]
+		out[t].Proofs = all[lo:hi:hi]
+		for i := lo; i < hi; i++ {
+			all[i] = Proof{Total: int64(hi - lo), Index: int64(i - lo), LeafHash: leafHashes[32*i : 32*i+32 : 32*i+32],
+				Aunts: hashes[auntOff[i]:auntOff[i+1]:auntOff[i+1]]}
+		}
+	}
+	return out
+}
+
+// MerkleProofs returns merkle.ProofsFromByteSlices (crypto/merkle/proof.go:35-48) of every tree
+// (tmed_merkle_proofs): the root and, per leaf, the proof the reference builds.
+func (e *Engine) MerkleProofs(trees [][][]byte) ([]TreeProofs, error) {
+	nt := len(trees)
+	if nt == 0 {
+		return nil, nil
+	}
+	flat, leafOff, treeOff := flatten(trees)
+	a := e.getArena()
+	defer e.putArena(a)
+	data, lo, to := a.bytes(flat), a.u64(leafOff), a.u32(treeOff)
+	roots, lh, ao, au, err := runProofs(a, nt, len(leafOff)-1, func(r, h *C.uint8_t, o *C.uint64_t, u *C.uint8_t,
+		room C.size_t, need *C.size_t) C.int {
+		return C.tmed_merkle_proofs(e.ctx, data, lo, to, C.size_t(nt), r, h, o, u, room, need)
+	})
+	if err != nil {
+		return nil, err
+	}
+	return treeProofs(roots, treeOff, lh, ao, au), nil
+}
+
+// TxsProofs returns, for every block, Data.Hash() and the merkle.Proof of every transaction as
+// Txs.Proof builds it (types/tx.go:80-93; tmed_txs_proofs): the leaves are tx.Hash(), so
+// Proofs[i].LeafHash is leafHash(tx.Hash()) and TxProof.Validate verifies tx.Hash() as the leaf.
+func (e *Engine) TxsProofs(blocks [][][]byte) ([]TreeProofs, error) {
+	nb := len(blocks)
+	if nb == 0 {
+		return nil, nil
+	}
+	flat, txOff, blockOff := flatten(blocks)
+	a := e.getArena()
+	defer e.putArena(a)
+	data, to, bo := a.bytes(flat), a.u64(txOff), a.u32(blockOff)
+	roots, lh, ao, au, err := runProofs(a, nb, len(txOff)-1, func(r, h *C.uint8_t, o *C.uint64_t, u *C.uint8_t,
+		room C.size_t, need *C.size_t) C.int {
+		return C.tmed_txs_proofs(e.ctx, data, to, bo, C.size_t(nb), r, h, o, u, room, need)
+	})
+	if err != nil {
+		return nil, err
+	}
+	return treeProofs(roots, blockOff, lh, ao, au), nil
+}
+
+// PartSetProofs is the whole of NewPartSetFromData (types/part_set.go:166-194) for every block's
+// bytes (tmed_partset_proofs): the PartSetHeader hash and the proof of every part.  Part p of
+// block b is blocks[b][p*partSize : min(len, (p+1)*partSize)] and its proof is out[b].Proofs[p].
+func (e *Engine) PartSetProofs(blocks [][]byte, partSize uint32) ([]TreeProofs, error) {
+	nb := len(blocks)
+	if nb == 0 {
+		return nil, nil
+	}
+	if partSize == 0 {
+		return nil, errors.New("tmedgpu: part size 0")
+	}
+	var flat []byte
+	dataOff := []uint64{0}
+	nl := 0
+	for _, b := range blocks {
+		flat = append(flat, b...)
+		dataOff = append(dataOff, uint64(len(flat)))
+		nl += (len(b) + int(partSize) - 1) / int(partSize)
+	}
+	flat = append(flat, make([]byte, 8)...) // the device reader may touch the last dword
+	a := e.getArena()
+	defer e.putArena(a)
+	data, do := a.bytes(flat), a.u64(dataOff)
+	po := (*[1 << 26]C.uint32_t)(a.alloc(uintptr(nb+1) * 4))[: nb+1 : nb+1]
+	roots, lh, ao, au, err := runProofs(a, nb, nl, func(r, h *C.uint8_t, o *C.uint64_t, u *C.uint8_t,
+		room C.size_t, need *C.size_t) C.int {
+		return C.tmed_partset_proofs(e.ctx, data, do, C.size_t(nb), C.uint32_t(partSize), r, &po[0], h, o, u, room, need)
+	})
+	if err != nil {
+		return nil, err
+	}
+	partOff := make([]uint32, nb+1)
+	for i := range partOff {
+		partOff[i] = uint32(po[i])
+	}
+	return treeProofs(roots, partOff, lh, ao, au), nil
+}
+
+// VerifyProofs runs Proof.Verify(roots[rootOf[i]], leaves[i]) for every proof
+// (crypto/merkle/proof.go:52-68; tmed_merkle_proofs_verify) and returns one code per proof:
+// ProofOK, or the first check that fails.  rootOf == nil: proof i belongs to roots[i].  On a
+// non-zero code the caller runs proof.Verify itself for the error's text.  LeafHash and the aunts
+// must be 32 bytes each, which Proof.ValidateBasic (proof.go:98-117) guarantees; its limit of 100
+// aunts is not needed here (any count is accepted, and no path is longer than 63).
+func (e *Engine) VerifyProofs(roots [][32]byte, rootOf []uint32, leaves [][]byte, proofs []Proof) ([]uint8, error) {
+	n := len(proofs)
+	if len(leaves) != n || (rootOf != nil && len(rootOf) != n) {
+		return nil, errors.New("tmedgpu: one leaf and one root index per proof")
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	if len(roots) == 0 {
+		return nil, errors.New("tmedgpu: no roots")
+	}
+	var flat []byte
+	leafOff := []uint64{0}
+	auntOff := []uint64{0}
+	totals := make([]int64, n)
+	indexes := make([]int64, n)
+	na := 0
+	for _, p := range proofs {
+		na += len(p.Aunts)
+	}
+	lh := make([]byte, 0, 32*n)
+	au := make([]byte, 0, 32*na+32)
+	for i, p := range proofs {
+		if len(p.LeafHash) != 32 {
+			return nil, errors.New("tmedgpu: a leaf hash of another size than 32 (Proof.ValidateBasic)")
+		}
+		for _, h := range p.Aunts {
+			if len(h) != 32 {
+				return nil, errors.New("tmedgpu: an aunt of another size than 32 (Proof.ValidateBasic)")
+			}
+			au = append(au, h...)
+		}
+		flat = append(flat, leaves[i]...)
+		leafOff = append(leafOff, uint64(len(flat)))
+		auntOff = append(auntOff, uint64(len(au)/32))
+		lh = append(lh, p.LeafHash...)
+		totals[i], indexes[i] = p.Total, p.Index
+	}
+	flat = append(flat, make([]byte, 8)...) // the device reader may touch the last dword
+	a := e.getArena()
+	defer e.putArena(a)
+	codes := (*[1 << 30]C.uint8_t)(a.alloc(uintptr(n)))[:n:n]
+	if rc := C.tmed_merkle_proofs_verify(e.ctx, C.size_t(n), (*C.uint8_t)(unsafe.Pointer(&roots[0])),
+		C.size_t(len(roots)), a.u32(rootOf), a.bytes(flat), a.u64(leafOff), a.bytes(lh), a.i64(totals), a.i64(indexes),
+		a.u64(auntOff), a.bytes(au), &codes[0]); rc != 0 {
+		return nil, errors.New(C.GoString(C.tmed_strerror(rc)))
+	}
+	out := make([]uint8, n)
+	for i := range out {
+		out[i] = uint8(codes[i])
+	}
+	return out, nil
+}
+
 // VoteSignBytes returns Commit.VoteSignBytes for n votes of one commit (tmed_vote_sign_bytes;
 // types/block.go:807-810 -> types/vote.go:93-101): vote i has flag flags[i] and timestamp
 // (tsSec[i], tsNanos[i]).  The seam builds these itself (on the device); this is for callers and
