@@ -10,6 +10,9 @@
                 VerifyCommitLight, all pairs in one seam call (light/verifier.go:32-79), median of
                 --runs calls with the host plan/verify/replay shares; bisection: targets 150
                 heights away, verifySkipping's pivots (light/client.go:706-773), one seam call per round.
+  --config c3v  the c3 direct workload through light.Verify itself (tmed_light_verify) over real
+                headers, beside (a) the c3 leg and (b) the c3 leg plus separate tmed_header_hashes
+                and tmed_valset_hashes calls over the same headers, all in one run.
   --config c4   blocksync replay: B blocks x V validators, VerifyCommitLight per block
                 (blockchain/v0/reactor.go:366-367), key-cached; with N ranks the blocks are
                 sharded and the per-rank int64 tallies all-reduced (RCCL; gloo on CPU).
@@ -481,6 +484,105 @@ def c3(eng, headers: int, gap: int, policy: str = "cache", runs: int = 7, bisect
     return res
 
 
+def c3v(eng, headers: int, gap: int, policy: str = "cache", runs: int = 7):
+    """The C3 direct workload through light.Verify itself (tmed_light_verify), over a chain whose
+    headers are real: header u's ValidatorsHash / NextValidatorsHash are the hashes of sets u and
+    u + 1 and commit u signs the block whose hash is Header.Hash(u).  Header h + gap is verified from
+    trusted header h (trusted set: set h, as the c3 leg), all headers in one call.  Three legs over the
+    same world, each timed `runs` times after a cold and a warm call (median):
+      a  the c3 leg: tmed_verify_commits over Trusting + Light per header (no hashes);
+      b  a plus a separate tmed_header_hashes call and a separate tmed_valset_hashes call over the same
+         untrusted headers and sets: what a caller stitches light.Verify from without this call;
+      v  tmed_light_verify: hashes, both commit checks and the replay in one call.
+    b is the yardstick for v.  Outcomes of v are checked: every request OK, one header changed after
+    signing -> COMMIT_HEADER_HASH, one wrong set -> VALS_HASH; a sample of header hashes against the
+    oracle's restatement."""
+    import tmed.light as L
+    import tmed.types as T
+    from oracle import merkle as OM
+    from tmed.merkle import HeaderBatch, header_hashes, valset_hashes, valset_hashes_arrays
+    from tmed.workload import make_valset, pubkeys_of, seeds_from_tag, sign_commits
+    nv, nh = 175, headers + gap + 1
+    eng.keycache_config(policy != "generic")
+    pool_seeds = seeds_from_tag(b"tmed-c3-key", 0, nh + nv)
+    pool_pubs = pubkeys_of(eng, pool_seeds)
+    sets, orders = [], []
+    for h in range(nh):
+        vals, order = make_valset(pool_pubs[h:h + nv], [10] * nv)
+        sets.append(vals)
+        orders.append(order)
+    hashes = valset_hashes(eng, sets)
+    for vals, hsh in zip(sets, hashes):
+        vals.set_hash = hsh
+    chain = "test_chain_id"
+    hdrs = [{"version_block": 11, "version_app": 0, "chain_id": chain, "height": h + 1, "time": (T2023 + h, 0),
+             "last_block_id": (hashlib.sha256(b"c3v-prev-%d" % h).digest(), 1, hashlib.sha256(b"c3v-pp-%d" % h).digest()),
+             "last_commit_hash": hashlib.sha256(b"c3v-lc-%d" % h).digest(), "data_hash": OM.empty_hash(),
+             "validators_hash": hashes[h], "next_validators_hash": hashes[h + 1],
+             "consensus_hash": hashlib.sha256(b"cons").digest(), "app_hash": hashlib.sha256(b"app-%d" % h).digest(),
+             "last_results_hash": OM.empty_hash(), "evidence_hash": OM.empty_hash(),
+             "proposer_address": sets[h].validators[0].address} for h in range(nh - 1)]
+    hh = header_hashes(eng, hdrs)
+    sample_ok = all(hh[h] == OM.header_hash(hdrs[h]) for h in range(0, nh - 1, max(1, (nh - 1) // 64)))
+    specs = []
+    for h in range(nh - 1):
+        addrs = np.array([np.frombuffer(v.address, np.uint8) for v in sets[h].validators])
+        bid = T.BlockID(hh[h], 1, hashlib.sha256(b"c3v-psh-%d" % h).digest())
+        specs.append((pool_seeds[h:h + nv][orders[h]], addrs, h + 1, 0, bid, T2023 + h, None))
+    t_sign = time.perf_counter()
+    commits = sign_commits(eng, chain, specs)
+    t_sign = time.perf_counter() - t_sign
+    # known answers: one header changed after signing, one pair given the wrong set
+    bad_hdr, bad_set = (headers // 3) + gap, (2 * headers // 3)
+    hdrs_v = list(hdrs)
+    hdrs_v[bad_hdr] = dict(hdrs[bad_hdr], app_hash=hashlib.sha256(b"changed").digest())
+    now, period, drift = (T2023 + nh + 10, 0), 14 * 86400 * L.SECOND, 10 * L.SECOND
+    pairs, reqs, exp = [], [], []
+    for h in range(headers):
+        u = h + gap
+        uvals = sets[u + 1] if h == bad_set else sets[u]
+        pairs.append(L.LightPair(hdrs[h], sets[h], hdrs_v[u], commits[u], uvals, period, now, drift, (1, 3)))
+        exp.append(L.COMMIT_HEADER_HASH if u == bad_hdr else L.VALS_HASH if h == bad_set else L.OK)
+        reqs.append((T.MODE_LIGHT_TRUSTING, sets[h], chain, None, 0, commits[u], 1, 3))
+        reqs.append((T.MODE_LIGHT, sets[u], chain, commits[u].block_id, u + 1, commits[u], 0, 0))
+    pb, pl = T.PreparedBatch(reqs), L.PreparedLight(pairs)
+    hb = HeaderBatch([hdrs_v[h + gap] for h in range(headers)])
+    upk = np.concatenate([sets[h + gap].packed()[0][:nv] for h in range(headers)])
+    upw = np.concatenate([sets[h + gap].packed()[1][:nv] for h in range(headers)])
+    uoff = (np.arange(headers + 1) * nv).astype(np.uint32)
+
+    class _Stitched:  # leg b as one timed unit
+        def run(self, e):
+            pb.run(e)
+            hb.run(e)
+            valset_hashes_arrays(e, upk, upw, uoff)
+
+    res = {"metric": "light-client headers/s through light.Verify (tmed_light_verify)", "unit": "headers/s",
+           "host": _host_threads(),
+           "config": {"workload": "C3v: %d headers x 175 validators, real headers, trust 1/3, gap %d" % (headers, gap),
+                      "key_policy": policy, "sign_s": round(t_sign, 2), "timed_runs": runs}}
+    legs = {}
+    for name, unit in (("a_verify_commits", pb), ("b_verify_commits_plus_hash_calls", _Stitched()), ("v_light_verify", pl)):
+        unit.run(eng)  # cold
+        eng.keycache_wait()
+        unit.run(eng)  # warm
+        med, lo, hi, phases = _timed_runs(eng, unit, runs)
+        legs[name] = {"headers_per_s": round(headers / med, 1), "seconds_median": round(med, 5),
+                      "seconds_min": round(lo, 5), "seconds_max": round(hi, 5)}
+    codes = pl.codes()
+    mism = int(sum(1 for q in range(headers) if int(codes[q]) != exp[q]))
+    a_ok = int((pb.codes() != 0).sum()) == 0
+    res["value"] = legs["v_light_verify"]["headers_per_s"]
+    res["legs"] = legs
+    res["v_over_b"] = round(legs["v_light_verify"]["headers_per_s"] /
+                            legs["b_verify_commits_plus_hash_calls"]["headers_per_s"], 3)
+    res["outcome_mismatches"] = mism
+    res["header_hash_sample_ok"] = bool(sample_ok)
+    res["all_ok"] = mism == 0 and a_ok and bool(sample_ok)
+    eng.keycache_config(True)
+    return res
+
+
 def _c4_corrupt(commits, b0: int, every: int, upto: int):
     """Known-answer corruption of a generated C4 window (every > 0): block b with b % every == 13
     gets one flipped bit in the signature at index j = (b * 7919) % upto, before the 2/3 crossing
@@ -935,6 +1037,8 @@ def main():
             r = c1(eng, args.reps, not args.no_cpu)
         elif cfg == "c3" and rank == 0:
             r = c3(eng, args.headers, args.gap, args.c3_policy, args.runs, args.bisect_gap)
+        elif cfg == "c3v" and rank == 0:
+            r = c3v(eng, args.headers, args.gap, args.c3_policy, args.runs)
         elif cfg == "c4":
             r = c4(eng, args.blocks, args.validators, rank, world, coll, args.window, args.batch, args.corrupt_every,
                        args.pregen, not args.no_pinned, args.c4_policy, not args.no_stream)

@@ -475,9 +475,15 @@ typedef struct {
 } tmed_header;
 
 /*
- * Header.Hash for n headers: out[i] (32 bytes) with ok[i] = 1, or ok[i] = 0 where the
- * reference returns nil (empty ValidatorsHash, :441-443).  Leaves are encoded on the host
- * (gogoproto wrappers as cdcEncode, types/encoding_helper.go), hashed on the device.
+ * Header.Hash for n headers: out[i] (32 bytes) with ok[i] = 1, or ok[i] = 0 (out[i] zeroed) where
+ * the reference returns nil (empty ValidatorsHash, :441-443).  A header whose 14 leaves each fit
+ * two SHA-256 blocks (chain_id_len <= 50, the reference's MaxChainIDLen, types/genesis.go:21; every
+ * hash field and both LastBlockID hashes <= 64 bytes; the LastBlockID leaf <= 118 bytes) is hashed by
+ * header_hash_kernel in one launch: 16 lanes per header, lane l encodes leaf l (gogoproto wrappers
+ * as cdcEncode, types/encoding_helper.go) in registers from a packed record and the 14-leaf tree is
+ * reduced across the lanes.  The limits are the kernel's, not the data's (AppHash may be of any
+ * length): any other header of the call has its leaves encoded on the host and hashed by the
+ * generic leaf and level kernels.  Results are identical either way.
  */
 int tmed_header_hashes(tmed_ctx *ctx, const tmed_header *headers, size_t n, uint8_t *out, uint8_t *ok);
 
@@ -592,6 +598,102 @@ int tmed_merkle_proofs_verify(tmed_ctx *ctx, size_t n, const uint8_t *roots, siz
                               const uint8_t *leaves, const uint64_t *leaf_off, const uint8_t *leaf_hashes,
                               const int64_t *totals, const int64_t *indexes, const uint64_t *aunt_off,
                               const uint8_t *aunts, uint8_t *out_code);
+
+/* ------------------------------------------------- light client: light.Verify */
+
+/*
+ * light.Verify (light/verifier.go:135-151) for n (trusted, untrusted) pairs in one call: the
+ * untrusted headers' Header.Hash (header_hash_kernel), the untrusted sets' ValidatorSet.Hash and
+ * the commit checks on the device, then the reference's checks replayed on the host in the
+ * reference's order.  One request = the arguments of one light.Verify call.
+ */
+typedef struct {
+  /* trustedHeader: the fields light.Verify reads */
+  const char *chain_id;
+  uint32_t chain_id_len;
+  int64_t trusted_height, trusted_time_seconds; /* Time.Unix() */
+  int32_t trusted_time_nanos;                   /* Time.Nanosecond() */
+  const uint8_t *trusted_next_vals_hash;        /* trustedHeader.NextValidatorsHash (adjacent only) */
+  uint32_t trusted_next_vals_hash_len;
+  const tmed_valset *trusted_vals;              /* non-adjacent only (may be NULL for an adjacent pair) */
+  /* untrusted SignedHeader + set */
+  const tmed_header *header;
+  const tmed_commit *commit;
+  const tmed_valset *vals;
+  uint8_t basic_ok; /* Header.ValidateBasic() == nil && Commit.ValidateBasic() == nil, run by the caller in Go */
+  int64_t trusting_period_ns, max_clock_drift_ns, now_seconds; /* time.Duration; now.Unix() */
+  int32_t now_nanos;
+  int64_t trust_num, trust_den; /* trustLevel */
+} tmed_light_request;
+
+/* Outcome codes, numbered in the order the reference checks; the first failing check wins.
+ * Adjacent (VerifyAdjacent, verifier.go:93-132) iff header->height == trusted_height + 1, otherwise
+ * non-adjacent (VerifyNonAdjacent, :32-79). */
+#define TMED_LIGHT_OK 0
+#define TMED_LIGHT_OLD_HEADER_EXPIRED 1  /* :46 / :105 HeaderExpired (:207-210): ErrOldHeaderExpired{expired_*, now} */
+/* 2..9: ErrInvalidHeader{reason}: verifyNewHeaderAndVals (:153-192) over SignedHeader.ValidateBasic
+ * (types/light.go:129-157) */
+#define TMED_LIGHT_HEADER_BASIC 2        /* light.go:137-142: basic_ok == 0 (the caller re-runs the Go method for the text) */
+#define TMED_LIGHT_WRONG_CHAIN 3         /* light.go:144-146 "header belongs to another chain %q, not %q" */
+#define TMED_LIGHT_COMMIT_HEIGHT 4       /* light.go:149-151 "header and commit height mismatch: %d vs %d" */
+#define TMED_LIGHT_COMMIT_HEADER_HASH 5  /* light.go:152-154 "commit signs block %X, header is block %X": hash / hash_len */
+#define TMED_LIGHT_HEIGHT_NOT_GREATER 6  /* verifier.go:164-168 */
+#define TMED_LIGHT_TIME_NOT_AFTER 7      /* verifier.go:170-174 */
+#define TMED_LIGHT_TIME_FROM_FUTURE 8    /* verifier.go:176-181 */
+#define TMED_LIGHT_VALS_HASH 9           /* verifier.go:183-189: hash = untrustedVals.Hash() */
+#define TMED_LIGHT_NEXT_VALS_HASH 10     /* adjacent, verifier.go:117-123: a plain error */
+#define TMED_LIGHT_TRUSTING 11           /* non-adjacent, verifier.go:58-66: VerifyCommitLightTrusting failed, its outcome
+                                            in `commit`: NOT_ENOUGH_POWER is ErrNewValSetCantBeTrusted{e}, anything else
+                                            the bare error */
+#define TMED_LIGHT_COMMIT 12             /* verifier.go:73-76 / :126-129: VerifyCommitLight failed, its outcome in
+                                            `commit`; the caller wraps it in ErrInvalidHeader */
+#define TMED_LIGHT_GO_PATH 13            /* the structs cannot express this request (a time outside the proto Timestamp
+                                            range documented at tmed_commit_hashes): the caller runs the Go function;
+                                            the other requests are unaffected */
+
+#define TMED_LIGHT_ORDERED 1u /* flags: verify the VerifyCommitLight requests in a second batch, and only for pairs
+                                 whose VerifyCommitLightTrusting passed (the reference's note at verifier.go:70-72:
+                                 untrustedVals can be made very large).  0: both speculatively in one batch.
+                                 Outcomes are identical; only verified_light differs. */
+
+typedef struct {
+  int code;
+  int adjacent;               /* 1: VerifyAdjacent's path was taken */
+  int64_t expired_seconds;    /* OLD_HEADER_EXPIRED: trustedHeader.Time.Add(trustingPeriod) */
+  int32_t expired_nanos;
+  uint32_t hash_len;          /* COMMIT_HEADER_HASH: 32, or 0 where Header.Hash() is nil; VALS_HASH: 32 */
+  uint8_t hash[32];           /* COMMIT_HEADER_HASH: Header.Hash(); VALS_HASH: untrustedVals.Hash() */
+  tmed_commit_result commit;  /* TRUSTING / COMMIT: the failing call's result (else zero) */
+  uint32_t verified_trusting; /* signatures sent to the verifier for VerifyCommitLightTrusting */
+  uint32_t verified_light;    /* ... and for VerifyCommitLight */
+} tmed_light_result;
+
+/*
+ * Checks of one request, in the reference's order (the first failing one is the outcome):
+ * OLD_HEADER_EXPIRED, HEADER_BASIC, WRONG_CHAIN, COMMIT_HEIGHT, COMMIT_HEADER_HASH (a nil Header.Hash
+ * compares as empty bytes, as bytes.Equal does), HEIGHT_NOT_GREATER, TIME_NOT_AFTER, TIME_FROM_FUTURE,
+ * VALS_HASH, then NEXT_VALS_HASH (adjacent) or TRUSTING (non-adjacent), then COMMIT.  Times are compared
+ * as Go's Time.Add / After / Before on (Unix seconds, nanoseconds).
+ *
+ * Device work of one call: header_hash_kernel over the untrusted headers of the requests that pass
+ * the checks before COMMIT_HEADER_HASH; the valset leaf and level kernels over the untrusted sets of
+ * the requests that also pass the host-decidable checks after it, each distinct tmed_valset pointer
+ * once; then one pass of tmed_verify_commits' plan -> batch -> replay (key-set cache and pipelining
+ * included) over two commit requests per non-adjacent pair and one per adjacent pair, for the pairs
+ * that passed every earlier check: a request that fails an earlier check sends no signatures.
+ * Submitted blocksync windows are collected first, as by every seam call.
+ * TMED_EINVAL for malformed calls only (a NULL header, commit or vals, a NULL trusted_vals of a
+ * non-adjacent pair, unknown flags).
+ *
+ * tmed_light_verify_with: the same replay with the hashes and the batch verifier supplied by the
+ * caller (the CPU test-suite: the oracle's hashes and verifier): header_hashes n x 32 with header_ok
+ * (0 = nil) and vals_hashes n x 32, one entry per request.
+ */
+int tmed_light_verify(tmed_ctx *ctx, const tmed_light_request *reqs, size_t n, uint32_t flags,
+                      tmed_light_result *out);
+int tmed_light_verify_with(const tmed_light_request *reqs, size_t n, uint32_t flags, const uint8_t *header_hashes,
+                           const uint8_t *header_ok, const uint8_t *vals_hashes, tmed_light_result *out,
+                           tmed_batch_verify_fn verify, void *user);
 
 /* ------------------------------------------------- blocksync replay (f4) */
 

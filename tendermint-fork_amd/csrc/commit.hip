@@ -1019,6 +1019,63 @@ extern "C" int tmed_verify_commits(tmed_ctx *ctx, const tmed_commit_request *req
   return c_guard(ctx, [&] { return verify_commits_impl(ctx, reqs, n, out); });
 }
 
+// ---- light.Verify (light/verifier.go:135-151; the replay is light_host.h) -------------------------
+// Header.Hash of the requests need_hdr (header_hash_kernel, or the host-leaf route for a header
+// outside the kernel's limits) and ValidatorSet.Hash of the untrusted sets of the requests
+// need_vals, each distinct tmed_valset pointer once, under one hold of the context's lock;
+// submitted blocksync windows are collected first.
+static int light_hashes_device(tmed_ctx *ctx, const tmed_light_request *reqs, const std::vector<size_t> &need_hdr,
+                               const std::vector<size_t> &need_vals, uint8_t *hdr_hash, uint8_t *hdr_ok,
+                               uint8_t *vals_hash) {
+  const size_t m = need_hdr.size();
+  std::vector<tmed_header> hs;
+  hs.reserve(m);
+  for (const size_t i : need_hdr) {
+    if (!tmed::header_pointers_ok(*reqs[i].header)) return TMED_EINVAL;
+    hs.push_back(*reqs[i].header);
+  }
+  std::unordered_map<const tmed_valset *, size_t> set_of;
+  std::vector<const tmed_valset *> sets;
+  for (const size_t i : need_vals) {
+    const tmed_valset *vs = reqs[i].vals;
+    if (!set_of.emplace(vs, sets.size()).second) continue;
+    if (vs->n && (!vs->pubkeys || !vs->powers)) return TMED_EINVAL;
+    sets.push_back(vs);
+  }
+  std::vector<uint8_t> ho(32 * std::max<size_t>(m, 1)), ok(std::max<size_t>(m, 1));
+  std::vector<uint8_t> so(32 * std::max<size_t>(sets.size(), 1));
+  int rc;
+  {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    rc = bs_drain(ctx);
+    if (rc == TMED_OK && m) rc = tmed::header_hashes_locked(ctx, hs.data(), m, ho.data(), ok.data());
+    if (rc == TMED_OK && !sets.empty())
+      rc = tmed::valsets_hashes_locked(ctx, sets.data(), sets.size(), so.data());
+  }
+  bs_reap(ctx);
+  if (rc != TMED_OK) return rc;
+  for (size_t j = 0; j < m; j++) {
+    memcpy(hdr_hash + 32 * need_hdr[j], ho.data() + 32 * j, 32);
+    hdr_ok[need_hdr[j]] = ok[j];
+  }
+  for (const size_t i : need_vals) memcpy(vals_hash + 32 * i, so.data() + 32 * set_of[reqs[i].vals], 32);
+  return TMED_OK;
+}
+
+extern "C" int tmed_light_verify(tmed_ctx *ctx, const tmed_light_request *reqs, size_t n, uint32_t flags,
+                                 tmed_light_result *out) {
+  if (!ctx) return TMED_EINVAL;
+  return c_guard(ctx, [&] {
+    return tmed_light::light_run(
+        reqs, n, flags, out,
+        [&](const std::vector<size_t> &need_hdr, const std::vector<size_t> &need_vals, uint8_t *hh, uint8_t *hok,
+            uint8_t *vh) { return light_hashes_device(ctx, reqs, need_hdr, need_vals, hh, hok, vh); },
+        [&](const tmed_commit_request *rq, size_t m, tmed_commit_result *res) {
+          return verify_commits_impl(ctx, rq, m, res);
+        });
+  });
+}
+
 extern "C" int tmed_blocksync_submit(tmed_ctx *ctx, const tmed_blocksync_window *w, uint32_t batch_blocks,
                                      tmed_commit_result *out) {
   return c_guard(ctx, [&] {

@@ -119,6 +119,14 @@ void bs_destroy(tmed_ctx *c);  // commit.hip: the blocksync batch stream (before
 // completed (their key-set cache pins take the lock).
 int bs_collect_submitted(tmed_ctx *c);
 void bs_release_collected(tmed_ctx *c);
+// merkle.hip, for the light-client seam (commit.hip): Header.Hash of n headers and ValidatorSet.Hash
+// of n_sets sets as tmed_header_hashes / tmed_valset_hashes compute them, arguments already checked;
+// ctx->mu held.
+bool header_pointers_ok(const tmed_header &h);  // no NULL array with a non-zero length
+int header_hashes_locked(tmed_ctx *c, const tmed_header *headers, size_t n, uint8_t *out, uint8_t *ok);
+int valset_hashes_locked(tmed_ctx *c, const uint8_t *pubkeys, const int64_t *powers, const uint32_t *set_off,
+                         size_t n_sets, uint8_t *out);
+int valsets_hashes_locked(tmed_ctx *c, const tmed_valset *const *sets, size_t n_sets, uint8_t *out);
 struct Lane;
 void lane_release(Lane &L);    // keyset.hip: the second kernel lane's stream and scratch
 bool lanes_on();               // keyset.hip: TMED_LANES != 1
@@ -282,6 +290,10 @@ struct tmed_ctx {
   // copy, plus the roots.  Its own buffers: no batch of a submitted blocksync window ever holds them.
   tmed::HostBuf h_csig;
   tmed::DevBuf d_csig;
+  // header_hash_kernel (merkle.hip): the packed header records (pinned) and their device copy, plus
+  // the hashes.  Its own buffers, as h_csig / d_csig.
+  tmed::HostBuf h_hdr;
+  tmed::DevBuf d_hdr;
   tmed::DevBuf d_korder;  // key-grouped order of a key-cached batch: counts / cursors + permutation
   tmed::DevBuf d_zip;     // ZIP-215 batch mode scratch (zip215.hip zip_bufs: points, digits, sort, buckets)
   bool zip_dense = false; // ZIP-215: the last large chunk had failures (zip215.hip: decide the next one singly first)

@@ -36,6 +36,7 @@
 #include "../../include/tmed25519.h"
 #include "commitsig_leaf.h"
 #include "ctx.h"
+#include "header_leaf.h"
 #include "merkle_path.h"
 #include "sha256.h"
 
@@ -289,6 +290,48 @@ __global__ __launch_bounds__(256) void merkle_verify_kernel(const uint8_t *__res
   code[i] = same ? TMED_PROOF_OK : TMED_PROOF_ROOT_HASH;
 }
 
+// ---- Header.Hash in one launch (types/block.go:440-475; leaves, record and fold: header_leaf.h) ----
+// A 16-lane group per header, four headers per wave: lane l < 14 encodes leaf l and takes its
+// leafHash, then the fixed tree 14 -> 7 -> 4 -> 2 -> 1 is folded inside the group: at step s = 1, 2,
+// 4, 8 the node at lane l (a multiple of 2 s) takes the node at lane l + s as its right child when
+// that lane holds one (l + s < 14), else it is the odd last node and is promoted as it is: the same
+// pairing as merkle_level_kernel.  Every lane of the wave runs every shuffle: lanes 14 and 15 of a
+// group redo leaf 13 and the groups past n redo header n - 1; neither is ever taken or stored.
+__global__ __launch_bounds__(256) void header_hash_kernel(const uint8_t *__restrict__ recs, uint32_t n,
+                                                          uint8_t *__restrict__ out) {
+  const uint32_t l = threadIdx.x & 15u, g = (blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+  const uint32_t hi = g < n ? g : n - 1, sl = l < kHdrLeaves ? l : kHdrLeaves - 1;
+  const uint8_t *rec = recs + (size_t)hi * kHdrRecBytes;
+  const uint4 m = reinterpret_cast<const uint4 *>(rec + kHdrMetaOff)[sl];
+  const uint4 *img = reinterpret_cast<const uint4 *>(rec + sl * kHdrSlotBytes);
+  uint32_t w[32];
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const uint4 q = img[k];
+    w[4 * k] = bswap32(q.x); w[4 * k + 1] = bswap32(q.y); w[4 * k + 2] = bswap32(q.z); w[4 * k + 3] = bswap32(q.w);
+  }
+  const uint32_t len = header_leaf_words(w, sl, m.x, m.y, m.z, m.w);
+  uint32_t d[8];
+  sha256_init(d);
+  sha256_compress(d, w);
+  if (len > 55) sha256_compress(d, w + 16);
+#pragma unroll
+  for (uint32_t s = 1; s < 16; s <<= 1) {
+    uint32_t r[8], st[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) r[k] = __shfl_down(d[k], s, 16);
+    sha256_inner(st, d, r);
+    const bool take = header_fold_takes(l, s);
+#pragma unroll
+    for (int k = 0; k < 8; k++) d[k] = take ? st[k] : d[k];
+  }
+  if (l == 0 && g < n) {
+    uint4 *o = reinterpret_cast<uint4 *>(out + 32 * (size_t)g);
+    o[0] = make_uint4(bswap32(d[0]), bswap32(d[1]), bswap32(d[2]), bswap32(d[3]));
+    o[1] = make_uint4(bswap32(d[4]), bswap32(d[5]), bswap32(d[6]), bswap32(d[7]));
+  }
+}
+
 static uint32_t blocks_for(size_t n) { return (uint32_t)((n + 255) / 256); }
 
 // Reduce per-tree leaf digests (c->d_merkle_a: counts[t] nodes per tree, tree-contiguous)
@@ -391,11 +434,10 @@ void header_leaves(const tmed_header &h, std::vector<uint8_t> &leaves, std::vect
 // Leaves on the host -> roots on the host: the common driver of the byte-slice APIs.  txs: the
 // byte slices are transactions (leaf = leafHash(SHA-256(tx)), txs_leaf_kernel, timed for
 // tmed_last_kernel_ms); else they are the leaves themselves.
-int roots_from_host_leaves(tmed_ctx *c, const uint8_t *leaves, const uint64_t *leaf_off, size_t L,
-                           const std::vector<uint32_t> &counts, uint8_t *roots, bool txs = false) {
+int roots_from_host_leaves_locked(tmed_ctx *c, const uint8_t *leaves, const uint64_t *leaf_off, size_t L,
+                                  const std::vector<uint32_t> &counts, uint8_t *roots, bool txs = false) {
   const size_t T = counts.size();
   const size_t bytes = leaf_off[L] - leaf_off[0];
-  std::lock_guard<std::mutex> lk(c->mu);
   (void)hipSetDevice(c->device);
   hipStream_t s = c->stream;
   hipError_t e = c->d_msg.ensure(bytes + 16);
@@ -426,6 +468,12 @@ int roots_from_host_leaves(tmed_ctx *c, const uint8_t *leaves, const uint64_t *l
   e = hipMemcpyAsync(roots, c->d_out.p, T * 32, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
   return map_err(e);
+}
+
+int roots_from_host_leaves(tmed_ctx *c, const uint8_t *leaves, const uint64_t *leaf_off, size_t L,
+                           const std::vector<uint32_t> &counts, uint8_t *roots, bool txs = false) {
+  std::lock_guard<std::mutex> lk(c->mu);
+  return roots_from_host_leaves_locked(c, leaves, leaf_off, L, counts, roots, txs);
 }
 
 // ---- Commit.Hash (types/block.go:894-912) ---------------------------------------------------
@@ -515,6 +563,34 @@ unsigned pack_threads(size_t sigs) {
   const char *v = getenv("TMED_HOST_THREADS");  // as the seam's host pool: 16 by default
   const unsigned want = v ? (unsigned)std::max(1, atoi(v)) : 16u;
   return std::min(want, std::max(1u, std::thread::hardware_concurrency()));
+}
+
+// Header.Hash of the headers idx[0 .. m) (all header_fused_ok) into out + 32 * idx[j].  ctx->mu held.
+int header_hashes_fused(tmed_ctx *c, const tmed_header *headers, const std::vector<size_t> &idx, uint8_t *out) {
+  const size_t m = idx.size();
+  if (m > 0x0fffffffu) return TMED_EINVAL;
+  const size_t o_roots = m * (size_t)kHdrRecBytes;  // a multiple of 256
+  (void)hipSetDevice(c->device);
+  hipStream_t s = c->stream;
+  hipError_t e = c->h_hdr.ensure(o_roots + 32 * m);
+  if (e == hipSuccess) e = c->d_hdr.ensure(o_roots + 32 * m);
+  if (e != hipSuccess) return map_err(e);
+  uint8_t *h = (uint8_t *)c->h_hdr.p, *d = (uint8_t *)c->d_hdr.p;
+  host_for(m, pack_threads(m * 32), [&](size_t j) { header_pack(headers[idx[j]], h + j * kHdrRecBytes); });
+  e = hipMemcpyAsync(d, h, o_roots, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipEventRecord(c->ev0, s);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(header_hash_kernel, dim3(blocks_for(16 * m)), dim3(256), 0, s, (const uint8_t *)d, (uint32_t)m,
+                       d + o_roots);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipEventRecord(c->ev1, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(h + o_roots, d + o_roots, 32 * m, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return map_err(e);
+  (void)hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1);
+  for (size_t j = 0; j < m; j++) memcpy(out + 32 * idx[j], h + o_roots + 32 * j, 32);
+  return TMED_OK;
 }
 
 int commit_hashes_locked(tmed_ctx *c, const tmed_commit *commits, size_t n, const std::vector<uint32_t> &counts,
@@ -742,6 +818,96 @@ int verify_proofs_locked(tmed_ctx *c, const ProofIn &in, const std::vector<uint6
 
 }  // namespace
 
+namespace tmed {
+
+bool header_pointers_ok(const tmed_header &h) {
+  for (int k = 0; k < 9; k++)
+    if (h.hash_lens[k] && !h.hashes[k]) return false;
+  return !((h.chain_id_len && !h.chain_id) || (h.last_block_id.hash_len && !h.last_block_id.hash) ||
+           (h.last_block_id.psh_hash_len && !h.last_block_id.psh_hash));
+}
+
+int valset_hashes_locked(tmed_ctx *c, const uint8_t *pubkeys, const int64_t *powers, const uint32_t *set_off,
+                         size_t n_sets, uint8_t *out) {
+  const size_t N = set_off[n_sets];
+  std::vector<uint32_t> counts(n_sets);
+  for (size_t t = 0; t < n_sets; t++) counts[t] = set_off[t + 1] - set_off[t];
+  (void)hipSetDevice(c->device);
+  hipStream_t s = c->stream;
+  hipError_t e = c->d_a.ensure(std::max<size_t>(N, 1) * 32);
+  if (e == hipSuccess) e = c->d_b.ensure(std::max<size_t>(N, 1) * 8);
+  if (e == hipSuccess) e = c->d_merkle_a.ensure(std::max<size_t>(N, 1) * sizeof(Digest));
+  if (e == hipSuccess) e = c->d_out.ensure(n_sets * 32);
+  if (e == hipSuccess && N) e = hipMemcpyAsync(c->d_a.p, pubkeys, N * 32, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && N) e = hipMemcpyAsync(c->d_b.p, powers, N * 8, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && N) {
+    hipLaunchKernelGGL(valset_leaf_kernel, dim3(blocks_for(N)), dim3(256), 0, s, (const uint8_t *)c->d_a.p,
+                       (const int64_t *)c->d_b.p, (uint32_t)N, (Digest *)c->d_merkle_a.p);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return map_err(e);
+  int rc = reduce_trees(c, counts, N, (uint8_t *)c->d_out.p, s);
+  if (rc != TMED_OK) return rc;
+  e = hipMemcpyAsync(out, c->d_out.p, n_sets * 32, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  return map_err(e);
+}
+
+// ValidatorSet.Hash of n_sets validator sets given as structs: their keys and powers are packed
+// straight into the context's pinned staging (h_a / h_b: one pass over the callers' arrays, and the
+// copies to the device run from page-locked memory), then hashed as above.
+int valsets_hashes_locked(tmed_ctx *c, const tmed_valset *const *sets, size_t n_sets, uint8_t *out) {
+  std::vector<uint32_t> set_off(n_sets + 1, 0);
+  for (size_t s = 0; s < n_sets; s++) {
+    if (sets[s]->n > 0xffffffffu - set_off[s]) return TMED_EINVAL;
+    set_off[s + 1] = set_off[s] + (uint32_t)sets[s]->n;
+  }
+  const size_t N = set_off[n_sets];
+  (void)hipSetDevice(c->device);
+  hipError_t e = c->h_a.ensure(std::max<size_t>(N, 1) * 32);
+  if (e == hipSuccess) e = c->h_b.ensure(std::max<size_t>(N, 1) * 8);
+  if (e != hipSuccess) return map_err(e);
+  uint8_t *pubs = (uint8_t *)c->h_a.p;
+  int64_t *pows = (int64_t *)c->h_b.p;
+  host_for(n_sets, pack_threads(N), [&](size_t s) {
+    if (!sets[s]->n) return;
+    memcpy(pubs + 32 * (size_t)set_off[s], sets[s]->pubkeys, 32 * sets[s]->n);
+    memcpy(pows + set_off[s], sets[s]->powers, 8 * sets[s]->n);
+  });
+  return valset_hashes_locked(c, pubs, pows, set_off.data(), n_sets, out);
+}
+
+// Eligible headers (header_fused_ok) through header_hash_kernel, the others through host-encoded
+// leaves and the generic leaf and level kernels; ok = 0 and a zeroed hash where ValidatorsHash is
+// empty (Header.Hash returns nil, types/block.go:441-443).
+int header_hashes_locked(tmed_ctx *c, const tmed_header *headers, size_t n, uint8_t *out, uint8_t *ok) {
+  std::vector<size_t> fused, rest;
+  for (size_t i = 0; i < n; i++) (header_fused_ok(headers[i]) ? fused : rest).push_back(i);
+  int rc = TMED_OK;
+  if (!fused.empty()) rc = header_hashes_fused(c, headers, fused, out);
+  if (rc == TMED_OK && !rest.empty()) {
+    std::vector<uint8_t> leaves, roots(32 * rest.size());
+    std::vector<uint64_t> off;
+    leaves.reserve(rest.size() * 200);
+    off.reserve(rest.size() * 14 + 1);
+    off.push_back(0);
+    for (const size_t i : rest) header_leaves(headers[i], leaves, off);
+    const std::vector<uint32_t> counts(rest.size(), 14);
+    rc = roots_from_host_leaves_locked(c, leaves.data(), off.data(), off.size() - 1, counts, roots.data());
+    if (rc == TMED_OK)
+      for (size_t j = 0; j < rest.size(); j++) memcpy(out + 32 * rest[j], roots.data() + 32 * j, 32);
+  }
+  if (rc != TMED_OK) return rc;
+  for (size_t i = 0; i < n; i++) {
+    ok[i] = headers[i].hash_lens[2] != 0;
+    if (!ok[i]) memset(out + 32 * i, 0, 32);
+  }
+  return TMED_OK;
+}
+
+}  // namespace tmed
+
 extern "C" {
 
 int tmed_commit_hashes(tmed_ctx *c, const tmed_commit *commits, size_t n, uint8_t *out, uint8_t *ok) {
@@ -828,54 +994,25 @@ int tmed_valset_hashes(tmed_ctx *c, const uint8_t *pubkeys, const int64_t *power
   if (n_sets == 0) return TMED_OK;
   const size_t N = set_off[n_sets];
   if (set_off[0] != 0 || N > 0xffffffffu || (N && (!pubkeys || !powers))) return TMED_EINVAL;
-  std::vector<uint32_t> counts(n_sets);
-  for (size_t t = 0; t < n_sets; t++) {
+  for (size_t t = 0; t < n_sets; t++)
     if (set_off[t + 1] < set_off[t]) return TMED_EINVAL;
-    counts[t] = set_off[t + 1] - set_off[t];
-  }
   std::lock_guard<std::mutex> lk(c->mu);
-  (void)hipSetDevice(c->device);
-  hipStream_t s = c->stream;
-  hipError_t e = c->d_a.ensure(std::max<size_t>(N, 1) * 32);
-  if (e == hipSuccess) e = c->d_b.ensure(std::max<size_t>(N, 1) * 8);
-  if (e == hipSuccess) e = c->d_merkle_a.ensure(std::max<size_t>(N, 1) * sizeof(Digest));
-  if (e == hipSuccess) e = c->d_out.ensure(n_sets * 32);
-  if (e == hipSuccess && N) e = hipMemcpyAsync(c->d_a.p, pubkeys, N * 32, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && N) e = hipMemcpyAsync(c->d_b.p, powers, N * 8, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && N) {
-    hipLaunchKernelGGL(valset_leaf_kernel, dim3(blocks_for(N)), dim3(256), 0, s, (const uint8_t *)c->d_a.p,
-                       (const int64_t *)c->d_b.p, (uint32_t)N, (Digest *)c->d_merkle_a.p);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return map_err(e);
-  int rc = reduce_trees(c, counts, N, (uint8_t *)c->d_out.p, s);
-  if (rc != TMED_OK) return rc;
-  e = hipMemcpyAsync(out, c->d_out.p, n_sets * 32, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  return map_err(e);
+  return valset_hashes_locked(c, pubkeys, powers, set_off, n_sets, out);
 }
 
 int tmed_header_hashes(tmed_ctx *c, const tmed_header *headers, size_t n, uint8_t *out, uint8_t *ok) {
   if (!c || (n && (!headers || !out || !ok))) return TMED_EINVAL;
   if (n == 0) return TMED_OK;
-  std::vector<uint8_t> leaves;
-  std::vector<uint64_t> off;
-  leaves.reserve(n * 200);
-  off.reserve(n * 14 + 1);
-  off.push_back(0);
-  std::vector<uint32_t> counts(n, 14);
-  for (size_t i = 0; i < n; i++) {
-    const tmed_header &h = headers[i];
-    for (int k = 0; k < 9; k++)
-      if (h.hash_lens[k] && !h.hashes[k]) return TMED_EINVAL;
-    if ((h.chain_id_len && !h.chain_id) || (h.last_block_id.hash_len && !h.last_block_id.hash) ||
-        (h.last_block_id.psh_hash_len && !h.last_block_id.psh_hash))
-      return TMED_EINVAL;
-    header_leaves(h, leaves, off);
-    ok[i] = h.hash_lens[2] != 0;  // Header.Hash returns nil without a ValidatorsHash (:441-443)
+  for (size_t i = 0; i < n; i++)
+    if (!header_pointers_ok(headers[i])) return TMED_EINVAL;
+  try {
+    std::lock_guard<std::mutex> lk(c->mu);
+    return header_hashes_locked(c, headers, n, out, ok);
+  } catch (const std::bad_alloc &) {
+    return TMED_ENOMEM;
+  } catch (...) {
+    return TMED_EINTERNAL;
   }
-  return roots_from_host_leaves(c, leaves.data(), off.data(), off.size() - 1, counts, out);
 }
 
 int tmed_partset_roots(tmed_ctx *c, const uint8_t *data, const uint64_t *data_off, size_t n_blocks,

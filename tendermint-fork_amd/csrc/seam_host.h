@@ -34,6 +34,7 @@
 #include "../../include/tmed25519.h"
 #include "host_pool.h"
 #include "keycache.h"
+#include "light_host.h"
 #include "signbytes.h"
 
 namespace {
@@ -974,6 +975,34 @@ extern "C" int tmed_verify_commits_with(const tmed_commit_request *reqs, size_t 
                     });
   } catch (const std::bad_alloc &) {
     return TMED_ENOMEM;
+  }
+}
+
+// light.Verify over hashes and a batch verifier supplied by the caller (light_host.h is the replay).
+extern "C" int tmed_light_verify_with(const tmed_light_request *reqs, size_t n, uint32_t flags,
+                                      const uint8_t *header_hashes, const uint8_t *header_ok,
+                                      const uint8_t *vals_hashes, tmed_light_result *out, tmed_batch_verify_fn verify,
+                                      void *user) {
+  if (!verify || (n && (!header_hashes || !header_ok || !vals_hashes))) return TMED_EINVAL;
+  try {
+    return tmed_light::light_run(
+        reqs, n, flags, out,
+        [&](const std::vector<size_t> &need_hdr, const std::vector<size_t> &need_vals, uint8_t *hh, uint8_t *hok,
+            uint8_t *vh) {
+          for (const size_t i : need_hdr) {
+            memcpy(hh + 32 * i, header_hashes + 32 * i, 32);
+            hok[i] = header_ok[i];
+          }
+          for (const size_t i : need_vals) memcpy(vh + 32 * i, vals_hashes + 32 * i, 32);
+          return TMED_OK;
+        },
+        [&](const tmed_commit_request *rq, size_t m, tmed_commit_result *res) {
+          return tmed_verify_commits_with(rq, m, res, verify, user);
+        });
+  } catch (const std::bad_alloc &) {
+    return TMED_ENOMEM;
+  } catch (...) {
+    return TMED_EINTERNAL;
   }
 }
 

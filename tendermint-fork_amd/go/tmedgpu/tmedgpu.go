@@ -1239,3 +1239,164 @@ func (p *Pool) VerifyCommits(reqs []Request) ([]Result, error) {
 		return C.tmed_verify_commits_multi(p.ctxs(a), C.size_t(len(p.engines)), creqs, n, res)
 	})
 }
+
+// ---- light.Verify (light/verifier.go:135-151) ----------------------------------------------------
+
+// Outcome codes of LightVerify, numbered in the order the reference checks (see tmed25519.h, which
+// cites each check's lines); the first failing check wins.
+const (
+	LightOK               = C.TMED_LIGHT_OK
+	LightOldHeaderExpired = C.TMED_LIGHT_OLD_HEADER_EXPIRED
+	LightHeaderBasic      = C.TMED_LIGHT_HEADER_BASIC
+	LightWrongChain       = C.TMED_LIGHT_WRONG_CHAIN
+	LightCommitHeight     = C.TMED_LIGHT_COMMIT_HEIGHT
+	LightCommitHeaderHash = C.TMED_LIGHT_COMMIT_HEADER_HASH
+	LightHeightNotGreater = C.TMED_LIGHT_HEIGHT_NOT_GREATER
+	LightTimeNotAfter     = C.TMED_LIGHT_TIME_NOT_AFTER
+	LightTimeFromFuture   = C.TMED_LIGHT_TIME_FROM_FUTURE
+	LightValsHash         = C.TMED_LIGHT_VALS_HASH
+	LightNextValsHash     = C.TMED_LIGHT_NEXT_VALS_HASH
+	LightTrusting         = C.TMED_LIGHT_TRUSTING
+	LightCommit           = C.TMED_LIGHT_COMMIT
+	LightGoPath           = C.TMED_LIGHT_GO_PATH
+	// LightOrdered (flags): VerifyCommitLight runs in a second batch, only after a passed
+	// VerifyCommitLightTrusting (the reference's note at verifier.go:70-72).
+	LightOrdered uint32 = C.TMED_LIGHT_ORDERED
+)
+
+// HeaderData is a flat copy of the fields of types.Header that Header.Hash reads
+// (types/block.go:440-475), in struct order.
+type HeaderData struct {
+	VersionBlock, VersionApp uint64
+	ChainID                  string
+	Height                   int64
+	TimeSeconds              int64 // Time.Unix()
+	TimeNanos                int32 // Time.Nanosecond()
+	LastBlockID              BlockID
+	// LastCommitHash, DataHash, ValidatorsHash, NextValidatorsHash, ConsensusHash, AppHash,
+	// LastResultsHash, EvidenceHash, ProposerAddress
+	Hashes [9][]byte
+}
+
+// LightRequest holds the arguments of one light.Verify call.
+type LightRequest struct {
+	// trustedHeader: the fields light.Verify reads
+	ChainID             string
+	TrustedHeight       int64
+	TrustedTimeSeconds  int64
+	TrustedTimeNanos    int32
+	TrustedNextValsHash []byte
+	TrustedVals         *ValSet // non-adjacent only
+	// untrusted SignedHeader + set
+	Header  *HeaderData
+	Commit  *CommitData
+	Vals    *ValSet
+	BasicOK bool // Header.ValidateBasic() == nil && Commit.ValidateBasic() == nil
+	// trustingPeriod, maxClockDrift (time.Duration), now, trustLevel
+	TrustingPeriodNs, MaxClockDriftNs int64
+	NowSeconds                        int64
+	NowNanos                          int32
+	TrustNum, TrustDen                int64
+}
+
+// LightResult is one request's outcome; the caller builds the reference's error value from it
+// (INTEGRATION.md §2c).
+type LightResult struct {
+	Code           int
+	Adjacent       bool
+	ExpiredSeconds int64 // LightOldHeaderExpired: trustedHeader.Time.Add(trustingPeriod)
+	ExpiredNanos   int32
+	Hash           []byte // LightCommitHeaderHash: Header.Hash() (nil as in Go); LightValsHash: untrustedVals.Hash()
+	Commit         Result // LightTrusting / LightCommit: the failing VerifyCommitLight* outcome
+	VerifiedTrusting, VerifiedLight uint32
+}
+
+func (a *arena) headerC(h *HeaderData) C.tmed_header {
+	t := C.tmed_header{version_block: C.uint64_t(h.VersionBlock), version_app: C.uint64_t(h.VersionApp),
+		chain_id: a.cstring(h.ChainID), chain_id_len: C.uint32_t(len(h.ChainID)), height: C.int64_t(h.Height),
+		time_seconds: C.int64_t(h.TimeSeconds), time_nanos: C.int32_t(h.TimeNanos),
+		last_block_id: a.blockID(&h.LastBlockID)}
+	for k := range h.Hashes {
+		t.hashes[k] = a.bytes(h.Hashes[k])
+		t.hash_lens[k] = C.uint32_t(len(h.Hashes[k]))
+	}
+	return t
+}
+
+// LightVerify is light.Verify for many (trusted, untrusted) pairs in one call: the header hashes,
+// the set hashes and the signatures of both commit checks are computed on the device, then the
+// reference's checks are replayed in its order.  An error means "take the original Go path".
+func (e *Engine) LightVerify(reqs []LightRequest, flags uint32) ([]LightResult, error) {
+	n := len(reqs)
+	if n == 0 {
+		return nil, nil
+	}
+	a := e.getArena()
+	defer e.putArena(a)
+	creqs := (*[1 << 24]C.tmed_light_request)(a.alloc(uintptr(n) * unsafe.Sizeof(C.tmed_light_request{})))[:n:n]
+	hs := (*[1 << 24]C.tmed_header)(a.alloc(uintptr(n) * unsafe.Sizeof(C.tmed_header{})))[:n:n]
+	cs := (*[1 << 24]C.tmed_commit)(a.alloc(uintptr(n) * unsafe.Sizeof(C.tmed_commit{})))[:n:n]
+	vs := (*[1 << 24]C.tmed_valset)(a.alloc(uintptr(2*n) * unsafe.Sizeof(C.tmed_valset{})))[: 2*n : 2*n]
+	// one C copy per distinct *ValSet (the library hashes and resolves each set once per call) and
+	// per distinct *CommitData
+	seen := make(map[*ValSet]*C.tmed_valset, 2*n)
+	seenC := make(map[*CommitData]*C.tmed_commit, n)
+	nv := 0
+	valset := func(v *ValSet) *C.tmed_valset {
+		if v == nil {
+			return nil
+		}
+		cv, ok := seen[v]
+		if !ok {
+			vs[nv] = a.valset(v)
+			cv = &vs[nv]
+			seen[v] = cv
+			nv++
+		}
+		return cv
+	}
+	for i := range reqs {
+		r := &reqs[i]
+		if r.Header == nil || r.Commit == nil || r.Vals == nil {
+			return nil, errors.New("tmedgpu: LightVerify: nil header, commit or validator set")
+		}
+		hs[i] = a.headerC(r.Header)
+		cc, ok := seenC[r.Commit]
+		if !ok {
+			cs[i] = a.commitC(r.Commit, nil)
+			cc = &cs[i]
+			seenC[r.Commit] = cc
+		}
+		var basic C.uint8_t
+		if r.BasicOK {
+			basic = 1
+		}
+		creqs[i] = C.tmed_light_request{chain_id: a.cstring(r.ChainID), chain_id_len: C.uint32_t(len(r.ChainID)),
+			trusted_height: C.int64_t(r.TrustedHeight), trusted_time_seconds: C.int64_t(r.TrustedTimeSeconds),
+			trusted_time_nanos: C.int32_t(r.TrustedTimeNanos), trusted_next_vals_hash: a.bytes(r.TrustedNextValsHash),
+			trusted_next_vals_hash_len: C.uint32_t(len(r.TrustedNextValsHash)), trusted_vals: valset(r.TrustedVals),
+			header: &hs[i], commit: cc, vals: valset(r.Vals), basic_ok: basic,
+			trusting_period_ns: C.int64_t(r.TrustingPeriodNs), max_clock_drift_ns: C.int64_t(r.MaxClockDriftNs),
+			now_seconds: C.int64_t(r.NowSeconds), now_nanos: C.int32_t(r.NowNanos),
+			trust_num: C.int64_t(r.TrustNum), trust_den: C.int64_t(r.TrustDen)}
+	}
+	res := make([]C.tmed_light_result, n)
+	if rc := C.tmed_light_verify(e.ctx, &creqs[0], C.size_t(n), C.uint32_t(flags), &res[0]); rc != 0 {
+		return nil, errors.New(C.GoString(C.tmed_strerror(rc)))
+	}
+	out := make([]LightResult, n)
+	for i := range res {
+		o := LightResult{Code: int(res[i].code), Adjacent: res[i].adjacent != 0,
+			ExpiredSeconds: int64(res[i].expired_seconds), ExpiredNanos: int32(res[i].expired_nanos),
+			VerifiedTrusting: uint32(res[i].verified_trusting), VerifiedLight: uint32(res[i].verified_light)}
+		o.Commit = toResults([]C.tmed_commit_result{res[i].commit})[0]
+		if hl := int(res[i].hash_len); hl > 0 {
+			o.Hash = make([]byte, hl)
+			for k := 0; k < hl; k++ {
+				o.Hash[k] = byte(res[i].hash[k])
+			}
+		}
+		out[i] = o
+	}
+	return out, nil
+}
