@@ -281,11 +281,17 @@ struct tmed_ctx {
   tmed::VoteSlot vslot[3];  // the blocksync pipeline (commit.hip BsStream: two slots, three when the signatures go direct)
   BsStream *bs = nullptr;   // batches of submitted blocksync windows in flight (tmed_blocksync_submit)
   tmed::Lane lane1;         // the pipelined seam's second kernel lane (VoteStage::lane)
-  tmed::DevBuf d_merkle_a, d_merkle_b, d_merkle_idx;  // Merkle level digests (ping-pong) + level indexes
-  // Merkle proofs (merkle.hip): every node of every level of every tree of one call (at most 2 L + 32 T
-  // digests), the per-level base tables uploaded before the launches, the leaves' aunt offsets and
-  // the call's outputs (verify: its root indexes, totals / indexes and codes)
-  tmed::DevBuf d_merkle_lv, d_merkle_tab, d_proof_off, d_proof_out, d_proof_in;
+  // Merkle roots and proofs (merkle.hip), one builder for both: every node of every level of every
+  // tree of one call (d_merkle_lv: the leaf kernels write level 0 at its start; at most 2 L + 32 T
+  // digests for L leaves in T trees; tmed_merkle_proofs_verify keeps its aunts there) and the call's
+  // level plan (d_merkle_tab: level starts, then the per-level base tables of merkle_levels.h),
+  // uploaded once before the level launches
+  tmed::DevBuf d_merkle_lv, d_merkle_tab;
+  // a byte-slice call's leaf offsets from 0 (host): the source of a queued copy until the call's wait
+  std::vector<uint64_t> merkle_off;
+  // Merkle proofs: the leaves' aunt offsets and the call's outputs (verify: its root indexes,
+  // totals / indexes and codes)
+  tmed::DevBuf d_proof_off, d_proof_out, d_proof_in;
   // tmed_commit_hashes (merkle.hip): the commits' arrays packed per kind (pinned) and their device
   // copy, plus the roots.  Its own buffers: no batch of a submitted blocksync window ever holds them.
   tmed::HostBuf h_csig;

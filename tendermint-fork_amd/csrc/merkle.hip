@@ -20,11 +20,16 @@
 // (HashFromByteSlicesIterative, tree.go:57-101, is asserted equal by tree_test.go:104-116),
 // which is what the level kernel does.  Work per inner node: 2 SHA-256 blocks.
 //
+// Host shape, the same for every root and proof call: the level plan (merkle_levels.h) from the
+// trees' leaf counts, a leaf stage that writes level 0 into the node buffer, build_levels (the plan
+// uploaded once, then every level launch back to back into the one buffer that keeps every level),
+// emit_roots on the last level, and one wait before the call returns.
+//
 // Proofs (crypto/merkle/proof.go:35-68, 151-181, 216-237; types/part_set.go:166-194 keeps every
-// part's proof, types/tx.go:80-93 builds one per transaction): the proof route runs the same leaf
-// and level kernels into one buffer that keeps every level, then merkle_aunts_kernel copies each
-// leaf's siblings out (no hashing); merkle_verify_kernel is Proof.Verify, one lane per proof.  The
-// path arithmetic both share with the host sizing is merkle_path.h.
+// part's proof, types/tx.go:80-93 builds one per transaction): after the levels are built,
+// merkle_aunts_kernel copies each leaf's siblings out of them (no hashing); merkle_verify_kernel is
+// Proof.Verify, one lane per proof.  The path arithmetic both share with the host sizing is
+// merkle_path.h.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -37,6 +42,7 @@
 #include "commitsig_leaf.h"
 #include "ctx.h"
 #include "header_leaf.h"
+#include "merkle_levels.h"
 #include "merkle_path.h"
 #include "sha256.h"
 
@@ -191,10 +197,10 @@ __global__ __launch_bounds__(256) void merkle_emit_kernel(const Digest *__restri
 }
 
 // ---- Merkle proofs (crypto/merkle/proof.go) ------------------------------------------------------
-// The proof route keeps every level: level l of all trees lies tree-contiguous at nodes + lvl_off[l]
-// (tree t's nodes at tab[l * (ntrees + 1) + t] ..), built by merkle_level_kernel from level l - 1.
-// A tree that is down to one node carries it through the remaining levels, so the last level holds
-// every root.
+// Every level is kept (merkle_levels.h): level l of all trees lies tree-contiguous at nodes +
+// lvl_off[l] (tree t's nodes at tab[l * (ntrees + 1) + t] ..), built by merkle_level_kernel from
+// level l - 1.  A tree that is down to one node carries it through the remaining levels, so the last
+// level holds every root.
 
 // Proof.Aunts and Proof.LeafHash of every leaf, no hashing: eight lanes per leaf, lane w of a leaf
 // copies digest word w.  The leaf at position p of its tree walks the kept levels: at a level of c
@@ -332,50 +338,66 @@ __global__ __launch_bounds__(256) void header_hash_kernel(const uint8_t *__restr
   }
 }
 
-static uint32_t blocks_for(size_t n) { return (uint32_t)((n + 255) / 256); }
+static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// Reduce per-tree leaf digests (c->d_merkle_a: counts[t] nodes per tree, tree-contiguous)
-// to roots (d_roots, 32 B each).  Host-side level bookkeeping (O(trees) per level); all
-// hashing on the device.  Caller holds ctx->mu.
-static int reduce_trees(tmed_ctx *c, std::vector<uint32_t> counts, size_t total_leaves, uint8_t *d_roots,
-                        hipStream_t s) {
-  const size_t T = counts.size();
-  if (total_leaves > 0xffffffffu) return TMED_EINVAL;
-  Digest *cur = (Digest *)c->d_merkle_a.p;
-  hipError_t e = c->d_merkle_b.ensure(std::max<size_t>(total_leaves, 1) * sizeof(Digest));
-  if (e != hipSuccess) return map_err(e);
-  Digest *nxt = (Digest *)c->d_merkle_b.p;
-  std::vector<uint32_t> in_base(T + 1), out_base(T + 1);
-  e = c->d_merkle_idx.ensure((2 * T + 2) * sizeof(uint32_t));
-  if (e != hipSuccess) return map_err(e);
-  uint32_t *d_in = (uint32_t *)c->d_merkle_idx.p, *d_out = d_in + T + 1;
-  for (;;) {
-    in_base[0] = out_base[0] = 0;
-    bool more = false;
-    for (size_t t = 0; t < T; t++) {
-      in_base[t + 1] = in_base[t] + counts[t];
-      if (counts[t] > 1) more = true;
-      counts[t] = (counts[t] + 1) / 2;  // 0 -> 0, 1 -> 1
-      out_base[t + 1] = out_base[t] + counts[t];
-    }
-    if (!more) break;
-    e = hipMemcpyAsync(d_in, in_base.data(), (T + 1) * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_out, out_base.data(), (T + 1) * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-      const uint32_t nout = out_base[T];
-      hipLaunchKernelGGL(merkle_level_kernel, dim3(blocks_for(nout)), dim3(256), 0, s, cur, d_in, d_out,
-                         (uint32_t)T, nout, nxt);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(s);  // the host index vectors are rewritten next level
-    if (e != hipSuccess) return map_err(e);
-    std::swap(cur, nxt);
-  }
-  e = hipMemcpyAsync(d_in, in_base.data(), (T + 1) * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(merkle_emit_kernel, dim3(blocks_for(T)), dim3(256), 0, s, cur, d_in, (uint32_t)T, d_roots);
-    e = hipGetLastError();
-  }
+// One step of a call's chain of stream operations: after a failure (e) or for no lanes nothing is
+// launched; else kernel k over `lanes` lanes in blocks of 256.
+template <class K, class... A>
+static hipError_t launch(hipError_t e, K k, size_t lanes, hipStream_t s, A... args) {
+  if (e != hipSuccess || lanes == 0) return e;
+  hipLaunchKernelGGL(k, dim3((uint32_t)((lanes + 255) / 256)), dim3(256), 0, s, args...);
+  return hipGetLastError();
+}
+
+// ---- the one tree builder ---------------------------------------------------------------------
+// d_merkle_lv holds every level of the call's plan (merkle_levels.h), d_merkle_tab the plan itself:
+// the level starts, then (from the next multiple of 256 bytes) the per-level base tables.  Every
+// function below takes ctx->mu held and queues on the context stream without waiting.
+static Digest *dev_nodes(tmed_ctx *c) { return (Digest *)c->d_merkle_lv.p; }
+static const uint64_t *dev_lvl_off(tmed_ctx *c) { return (const uint64_t *)c->d_merkle_tab.p; }
+static const uint32_t *dev_tab(tmed_ctx *c, const MerkleLevels &p) {
+  return (const uint32_t *)((const uint8_t *)c->d_merkle_tab.p + align256(p.nlevels * 8));
+}
+
+// Room for every node of the plan, before the leaf stage writes level 0 at the buffer's start
+// (and before the call queues anything).  TMED_EINVAL past 2^32 - 1 leaves: the tables are 32-bit.
+static int ensure_nodes(tmed_ctx *c, const MerkleLevels &p) {
+  if (p.leaves > 0xffffffffu) return TMED_EINVAL;
+  return map_err(c->d_merkle_lv.ensure(std::max<uint64_t>(p.nodes, 1) * sizeof(Digest)));
+}
+
+// Level 0 (written by a leaf stage queued before) -> every level: the plan uploaded once, then one
+// merkle_level_kernel launch per level, back to back.
+static hipError_t build_levels(tmed_ctx *c, const MerkleLevels &p, hipStream_t s) {
+  const size_t o_tab = align256(p.nlevels * 8);
+  hipError_t e = c->d_merkle_tab.ensure(o_tab + p.tab.size() * 4);
+  if (e != hipSuccess) return e;
+  uint8_t *d = (uint8_t *)c->d_merkle_tab.p;
+  e = hipMemcpyAsync(d, p.lvl_off.data(), p.nlevels * 8, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(d + o_tab, p.tab.data(), p.tab.size() * 4, hipMemcpyHostToDevice, s);
+  Digest *lv = dev_nodes(c);
+  const uint32_t *tab = dev_tab(c, p);
+  for (size_t l = 0; l + 1 < p.nlevels; l++)
+    e = launch(e, merkle_level_kernel, p.level_nodes(l + 1), s, lv + p.lvl_off[l], tab + l * (p.T + 1),
+               tab + (l + 1) * (p.T + 1), (uint32_t)p.T, p.level_nodes(l + 1), lv + p.lvl_off[l + 1]);
+  return e;
+}
+
+// The last level -> d_roots (32 B a tree, emptyHash for an empty tree).
+static hipError_t emit_roots(tmed_ctx *c, const MerkleLevels &p, uint8_t *d_roots, hipStream_t s) {
+  const size_t last = p.nlevels - 1;
+  return launch(hipSuccess, merkle_emit_kernel, p.T, s, dev_nodes(c) + p.lvl_off[last],
+                dev_tab(c, p) + last * (p.T + 1), (uint32_t)p.T, d_roots);
+}
+
+// The one exit of every device call of this file, taken on a failure (e) as on success: the call
+// has queued copies whose sources are host vectors of its own (the plan, offsets) or the caller's
+// pageable arrays, so it waits for the stream before any of them goes away.  timed: ev0 / ev1 were
+// recorded around the call's kernel of record (tmed_last_kernel_ms).
+static int finish_call(tmed_ctx *c, hipError_t e, bool timed) {
+  const hipError_t es = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess) e = es;
+  if (e == hipSuccess && timed) (void)hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1);
   return map_err(e);
 }
 
@@ -384,6 +406,73 @@ static int reduce_trees(tmed_ctx *c, std::vector<uint32_t> counts, size_t total_
 using namespace tmed;
 
 namespace {
+
+// ---- the call frame of every extern "C" function of this file -----------------------------------
+// guarded(body): body checks the arguments and builds the call's host vectors; no exception
+// crosses the C boundary.  Inside it, locked(c, collect, run) is the device part under ctx->mu;
+// collect: the call follows the seam's rule (ctx.h bs_collect_submitted) and first collects the
+// submitted blocksync windows, then releases the completed ones once the lock is dropped.
+template <class F>
+int guarded(F &&body) {
+  try {
+    return body();
+  } catch (const std::bad_alloc &) {
+    return TMED_ENOMEM;
+  } catch (...) {
+    return TMED_EINTERNAL;
+  }
+}
+
+template <class F>
+int locked(tmed_ctx *c, bool collect, F &&run) {
+  int rc;
+  {
+    std::lock_guard<std::mutex> lk(c->mu);
+    rc = collect ? bs_collect_submitted(c) : TMED_OK;
+    if (rc == TMED_OK) rc = run();
+  }
+  if (collect) bs_release_collected(c);
+  return rc;
+}
+
+// ---- argument checks ------------------------------------------------------------------------
+// The forest of a byte-slice call (n_trees >= 1): tree t holds leaves [tree_off[t], tree_off[t+1]),
+// leaf i the bytes [leaf_off[i], leaf_off[i+1]) of `leaves`.  counts: leaves per tree.
+int forest_counts(const uint32_t *tree_off, size_t n_trees, const uint64_t *leaf_off, const uint8_t *leaves,
+                  std::vector<uint32_t> &counts) {
+  const size_t L = tree_off[n_trees];
+  if (tree_off[0] != 0) return TMED_EINVAL;
+  counts.resize(n_trees);
+  for (size_t t = 0; t < n_trees; t++) {
+    if (tree_off[t + 1] < tree_off[t]) return TMED_EINVAL;
+    counts[t] = tree_off[t + 1] - tree_off[t];
+  }
+  for (size_t i = 0; i < L; i++)
+    if (leaf_off[i + 1] < leaf_off[i] || leaf_off[i + 1] - leaf_off[i] > 0xffffffffu - 64) return TMED_EINVAL;
+  if (L && leaf_off[L] > leaf_off[0] && !leaves) return TMED_EINVAL;
+  return TMED_OK;
+}
+
+// The part sets of a part-set call (n_blocks >= 1): block b's bytes [data_off[b], data_off[b+1]) cut
+// into parts of part_size (types/part_set.go:166-194).  off: the parts' offsets (from data_off[0]),
+// counts: parts per block, part_off (n_blocks + 1 entries, or NULL): each block's first part.  The
+// running part count is checked per block, so no offsets are pushed past 2^32 - 1 parts.
+int split_parts(const uint8_t *data, const uint64_t *data_off, size_t n_blocks, uint32_t part_size,
+                std::vector<uint64_t> &off, std::vector<uint32_t> &counts, uint32_t *part_off) {
+  counts.resize(n_blocks);
+  off.assign(1, data_off[0]);
+  for (size_t b = 0; b < n_blocks; b++) {
+    if (data_off[b + 1] < data_off[b]) return TMED_EINVAL;
+    const uint64_t len = data_off[b + 1] - data_off[b];
+    const uint64_t parts = (len + part_size - 1) / part_size;  // types/part_set.go:168
+    if (parts > 0xffffffffu || off.size() - 1 + parts > 0xffffffffu) return TMED_EINVAL;
+    counts[b] = (uint32_t)parts;
+    if (part_off) part_off[b] = (uint32_t)(off.size() - 1);
+    for (uint64_t p = 0; p < parts; p++) off.push_back(std::min(data_off[b] + (p + 1) * part_size, data_off[b + 1]));
+  }
+  if (part_off) part_off[n_blocks] = (uint32_t)(off.size() - 1);
+  return off.size() > 1 && !data ? TMED_EINVAL : TMED_OK;
+}
 
 // gogoproto varint / field helpers for the header leaves (types/block.go:440-475)
 void put_varint(std::vector<uint8_t> &o, uint64_t v) {
@@ -431,49 +520,43 @@ void header_leaves(const tmed_header &h, std::vector<uint8_t> &leaves, std::vect
   }
 }
 
-// Leaves on the host -> roots on the host: the common driver of the byte-slice APIs.  txs: the
-// byte slices are transactions (leaf = leafHash(SHA-256(tx)), txs_leaf_kernel, timed for
-// tmed_last_kernel_ms); else they are the leaves themselves.
-int roots_from_host_leaves_locked(tmed_ctx *c, const uint8_t *leaves, const uint64_t *leaf_off, size_t L,
-                                  const std::vector<uint32_t> &counts, uint8_t *roots, bool txs = false) {
-  const size_t T = counts.size();
+// The leaf stage of the byte-slice calls: L leaves on the host -> level 0 (ensure_nodes has run).
+// txs: the byte slices are transactions (leaf = leafHash(SHA-256(tx)), txs_leaf_kernel); else they
+// are the leaves themselves.  timed: ev0 / ev1 around the leaf kernel.
+hipError_t hash_host_leaves(tmed_ctx *c, const uint8_t *leaves, const uint64_t *leaf_off, size_t L, bool txs,
+                            bool timed, hipStream_t s) {
   const size_t bytes = leaf_off[L] - leaf_off[0];
-  (void)hipSetDevice(c->device);
-  hipStream_t s = c->stream;
   hipError_t e = c->d_msg.ensure(bytes + 16);
   if (e == hipSuccess) e = c->d_off.ensure((L + 1) * 8);
-  if (e == hipSuccess) e = c->d_merkle_a.ensure(std::max<size_t>(L, 1) * sizeof(Digest));
-  if (e == hipSuccess) e = c->d_out.ensure(std::max<size_t>(T, 1) * 32);
-  if (e != hipSuccess) return map_err(e);
-  std::vector<uint64_t> off(L + 1);
+  if (e != hipSuccess) return e;
+  std::vector<uint64_t> &off = c->merkle_off;
+  off.resize(L + 1);
   for (size_t i = 0; i <= L; i++) off[i] = leaf_off[i] - leaf_off[0];
   if (bytes) e = hipMemcpyAsync(c->d_msg.p, leaves + leaf_off[0], bytes, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipMemcpyAsync(c->d_off.p, off.data(), (L + 1) * 8, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && txs) e = hipEventRecord(c->ev0, s);
-  if (e == hipSuccess && L) {
-    if (txs)
-      hipLaunchKernelGGL(txs_leaf_kernel, dim3(blocks_for(L)), dim3(256), 0, s, (const uint8_t *)c->d_msg.p,
-                         (const uint64_t *)c->d_off.p, (uint32_t)L, (Digest *)c->d_merkle_a.p);
-    else
-      hipLaunchKernelGGL(merkle_leaf_kernel, dim3(blocks_for(L)), dim3(256), 0, s, (const uint8_t *)c->d_msg.p,
-                         (const uint64_t *)c->d_off.p, (uint32_t)L, (Digest *)c->d_merkle_a.p);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess && txs) e = hipEventRecord(c->ev1, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return map_err(e);
-  if (txs) (void)hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1);
-  int rc = reduce_trees(c, counts, L, (uint8_t *)c->d_out.p, s);
-  if (rc != TMED_OK) return rc;
-  e = hipMemcpyAsync(roots, c->d_out.p, T * 32, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  return map_err(e);
+  if (e == hipSuccess && timed) e = hipEventRecord(c->ev0, s);
+  e = launch(e, txs ? txs_leaf_kernel : merkle_leaf_kernel, L, s, (const uint8_t *)c->d_msg.p,
+             (const uint64_t *)c->d_off.p, (uint32_t)L, dev_nodes(c));
+  if (e == hipSuccess && timed) e = hipEventRecord(c->ev1, s);
+  return e;
 }
 
-int roots_from_host_leaves(tmed_ctx *c, const uint8_t *leaves, const uint64_t *leaf_off, size_t L,
-                           const std::vector<uint32_t> &counts, uint8_t *roots, bool txs = false) {
-  std::lock_guard<std::mutex> lk(c->mu);
-  return roots_from_host_leaves_locked(c, leaves, leaf_off, L, counts, roots, txs);
+// Leaves on the host -> roots on the host: the common driver of the byte-slice root calls (the
+// transactions' leaf kernel is timed for tmed_last_kernel_ms).  ctx->mu held.
+int roots_from_host_leaves_locked(tmed_ctx *c, const uint8_t *leaves, const uint64_t *leaf_off, size_t L,
+                                  const std::vector<uint32_t> &counts, uint8_t *roots, bool txs = false) {
+  const MerkleLevels plan(counts);
+  const size_t T = counts.size();
+  (void)hipSetDevice(c->device);
+  hipStream_t s = c->stream;
+  const int rc = ensure_nodes(c, plan);
+  if (rc != TMED_OK) return rc;
+  hipError_t e = c->d_out.ensure(T * 32);
+  if (e == hipSuccess) e = hash_host_leaves(c, leaves, leaf_off, L, txs, /*timed=*/txs, s);
+  if (e == hipSuccess) e = build_levels(c, plan, s);
+  if (e == hipSuccess) e = emit_roots(c, plan, (uint8_t *)c->d_out.p, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(roots, c->d_out.p, T * 32, hipMemcpyDeviceToHost, s);
+  return finish_call(c, e, /*timed=*/txs);
 }
 
 // ---- Commit.Hash (types/block.go:894-912) ---------------------------------------------------
@@ -481,8 +564,6 @@ int roots_from_host_leaves(tmed_ctx *c, const uint8_t *leaves, const uint64_t *l
 // Marshal fails and Commit.Hash panics.
 constexpr int64_t kMinTimeSeconds = -62135596800ll;  // 0001-01-01T00:00:00Z, Go's zero time
 constexpr int64_t kMaxTimeSeconds = 253402300800ll;  // 10000-01-01T00:00:00Z (exclusive)
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // The commits' arrays of one call, packed per kind: region offsets for N signatures.
 struct CsigLayout {
@@ -579,28 +660,25 @@ int header_hashes_fused(tmed_ctx *c, const tmed_header *headers, const std::vect
   host_for(m, pack_threads(m * 32), [&](size_t j) { header_pack(headers[idx[j]], h + j * kHdrRecBytes); });
   e = hipMemcpyAsync(d, h, o_roots, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipEventRecord(c->ev0, s);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(header_hash_kernel, dim3(blocks_for(16 * m)), dim3(256), 0, s, (const uint8_t *)d, (uint32_t)m,
-                       d + o_roots);
-    e = hipGetLastError();
-  }
+  e = launch(e, header_hash_kernel, 16 * m, s, (const uint8_t *)d, (uint32_t)m, d + o_roots);
   if (e == hipSuccess) e = hipEventRecord(c->ev1, s);
   if (e == hipSuccess) e = hipMemcpyAsync(h + o_roots, d + o_roots, 32 * m, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return map_err(e);
-  (void)hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1);
+  const int rc = finish_call(c, e, /*timed=*/true);
+  if (rc != TMED_OK) return rc;
   for (size_t j = 0; j < m; j++) memcpy(out + 32 * idx[j], h + o_roots + 32 * j, 32);
   return TMED_OK;
 }
 
 int commit_hashes_locked(tmed_ctx *c, const tmed_commit *commits, size_t n, const std::vector<uint32_t> &counts,
                          const std::vector<size_t> &base, size_t N, uint8_t *out) {
+  const MerkleLevels plan(counts);
   (void)hipSetDevice(c->device);
   hipStream_t s = c->stream;
   const CsigLayout lay(N, n);
+  int rc = ensure_nodes(c, plan);
+  if (rc != TMED_OK) return rc;
   hipError_t e = c->h_csig.ensure(lay.total);
   if (e == hipSuccess) e = c->d_csig.ensure(lay.total);
-  if (e == hipSuccess) e = c->d_merkle_a.ensure(std::max<size_t>(N, 1) * sizeof(Digest));
   if (e != hipSuccess) return map_err(e);
   uint8_t *h = (uint8_t *)c->h_csig.p, *d = (uint8_t *)c->d_csig.p;
   host_for(n, pack_threads(N), [&](size_t i) {
@@ -614,20 +692,14 @@ int commit_hashes_locked(tmed_ctx *c, const tmed_commit *commits, size_t n, cons
     if (e == hipSuccess) e = hipMemcpyAsync(d + lay.addr, h + lay.addr, 20 * N, hipMemcpyHostToDevice, s);
   }
   if (e == hipSuccess) e = hipEventRecord(c->ev0, s);
-  if (e == hipSuccess && N) {
-    hipLaunchKernelGGL(commit_leaf_kernel, dim3(blocks_for(N)), dim3(256), 0, s, (const uint32_t *)(d + lay.meta),
-                       (const int64_t *)(d + lay.sec), (const int32_t *)(d + lay.nanos), d + lay.addr, d + lay.sig,
-                       (uint32_t)N, (Digest *)c->d_merkle_a.p);
-    e = hipGetLastError();
-  }
+  e = launch(e, commit_leaf_kernel, N, s, (const uint32_t *)(d + lay.meta), (const int64_t *)(d + lay.sec),
+             (const int32_t *)(d + lay.nanos), d + lay.addr, d + lay.sig, (uint32_t)N, dev_nodes(c));
   if (e == hipSuccess) e = hipEventRecord(c->ev1, s);
-  if (e != hipSuccess) return map_err(e);
-  int rc = reduce_trees(c, counts, N, d + lay.roots, s);
+  if (e == hipSuccess) e = build_levels(c, plan, s);
+  if (e == hipSuccess) e = emit_roots(c, plan, d + lay.roots, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(h + lay.roots, d + lay.roots, n * 32, hipMemcpyDeviceToHost, s);
+  rc = finish_call(c, e, /*timed=*/true);
   if (rc != TMED_OK) return rc;
-  e = hipMemcpyAsync(h + lay.roots, d + lay.roots, n * 32, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return map_err(e);
-  (void)hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1);
   memcpy(out, h + lay.roots, n * 32);
   return TMED_OK;
 }
@@ -646,86 +718,31 @@ struct ProofOut {
 // leaves' aunt offsets (sized by the caller).  ctx->mu held.
 int proofs_locked(tmed_ctx *c, const uint8_t *leaves, const uint64_t *leaf_off, size_t L,
                   const std::vector<uint32_t> &counts, bool txs, const std::vector<uint64_t> &ao, const ProofOut &o) {
+  const MerkleLevels plan(counts);
   const size_t T = counts.size();
-  const size_t bytes = leaf_off[L] - leaf_off[0];
   const size_t need = 32 * (size_t)ao[L];
-  // the per-level base tables, all of them before the first launch
-  std::vector<uint32_t> cnt(counts), tab;
-  std::vector<uint64_t> lvl;
-  uint64_t nodes = 0;
-  for (;;) {
-    const size_t at = tab.size();
-    tab.resize(at + T + 1);
-    lvl.push_back(nodes);
-    tab[at] = 0;
-    bool more = false;
-    for (size_t t = 0; t < T; t++) {
-      tab[at + t + 1] = tab[at + t] + cnt[t];
-      if (cnt[t] > 1) more = true;
-      cnt[t] = (cnt[t] + 1) / 2;  // 0 -> 0, 1 -> 1
-    }
-    nodes += tab[at + T];
-    if (!more) break;
-  }
-  const size_t nlev = lvl.size();
-  const size_t o_tab = align256(nlev * 8), o_leaf = align256(need), o_root = align256(o_leaf + 32 * L);
+  const size_t o_leaf = align256(need), o_root = align256(o_leaf + 32 * L);  // d_proof_out: aunts | leaf hashes | roots
   (void)hipSetDevice(c->device);
   hipStream_t s = c->stream;
-  hipError_t e = c->d_msg.ensure(bytes + 16);
-  if (e == hipSuccess) e = c->d_off.ensure((L + 1) * 8);
-  if (e == hipSuccess) e = c->d_merkle_lv.ensure(std::max<uint64_t>(nodes, 1) * sizeof(Digest));
-  if (e == hipSuccess) e = c->d_merkle_tab.ensure(o_tab + tab.size() * 4);
-  if (e == hipSuccess) e = c->d_proof_off.ensure((L + 1) * 8);
+  const int rc = ensure_nodes(c, plan);
+  if (rc != TMED_OK) return rc;
+  hipError_t e = c->d_proof_off.ensure((L + 1) * 8);
   if (e == hipSuccess) e = c->d_proof_out.ensure(o_root + 32 * T);
-  if (e != hipSuccess) return map_err(e);
-  Digest *lv = (Digest *)c->d_merkle_lv.p;
-  uint8_t *d_tab = (uint8_t *)c->d_merkle_tab.p, *d_res = (uint8_t *)c->d_proof_out.p;
-  const uint64_t *d_lvl = (const uint64_t *)d_tab;
-  const uint32_t *d_t = (const uint32_t *)(d_tab + o_tab);
-  std::vector<uint64_t> off(L + 1);
-  for (size_t i = 0; i <= L; i++) off[i] = leaf_off[i] - leaf_off[0];
-  if (bytes) e = hipMemcpyAsync(c->d_msg.p, leaves + leaf_off[0], bytes, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(c->d_off.p, off.data(), (L + 1) * 8, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_tab, lvl.data(), nlev * 8, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_tab + o_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, s);
+  uint8_t *d_res = (uint8_t *)c->d_proof_out.p;
+  if (e == hipSuccess) e = hash_host_leaves(c, leaves, leaf_off, L, txs, /*timed=*/false, s);
+  if (e == hipSuccess) e = build_levels(c, plan, s);
+  if (e == hipSuccess) e = emit_roots(c, plan, d_res + o_root, s);
   if (e == hipSuccess) e = hipMemcpyAsync(c->d_proof_off.p, ao.data(), (L + 1) * 8, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && L) {
-    if (txs)
-      hipLaunchKernelGGL(txs_leaf_kernel, dim3(blocks_for(L)), dim3(256), 0, s, (const uint8_t *)c->d_msg.p,
-                         (const uint64_t *)c->d_off.p, (uint32_t)L, lv);
-    else
-      hipLaunchKernelGGL(merkle_leaf_kernel, dim3(blocks_for(L)), dim3(256), 0, s, (const uint8_t *)c->d_msg.p,
-                         (const uint64_t *)c->d_off.p, (uint32_t)L, lv);
-    e = hipGetLastError();
-  }
-  for (size_t l = 0; e == hipSuccess && l + 1 < nlev; l++) {
-    const uint32_t nout = tab[(l + 1) * (T + 1) + T];
-    hipLaunchKernelGGL(merkle_level_kernel, dim3(blocks_for(nout)), dim3(256), 0, s, lv + lvl[l], d_t + l * (T + 1),
-                       d_t + (l + 1) * (T + 1), (uint32_t)T, nout, lv + lvl[l + 1]);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(merkle_emit_kernel, dim3(blocks_for(T)), dim3(256), 0, s, lv + lvl[nlev - 1],
-                       d_t + (nlev - 1) * (T + 1), (uint32_t)T, d_res + o_root);
-    e = hipGetLastError();
-  }
   if (e == hipSuccess) e = hipEventRecord(c->ev0, s);
-  if (e == hipSuccess && L) {
-    hipLaunchKernelGGL(merkle_aunts_kernel, dim3(blocks_for(8 * L)), dim3(256), 0, s, lv, d_lvl, d_t, (uint32_t)T,
-                       (uint32_t)nlev, (uint32_t)L, (const uint64_t *)c->d_proof_off.p, (uint32_t *)d_res,
-                       (uint32_t *)(d_res + o_leaf));
-    e = hipGetLastError();
-  }
+  if (e == hipSuccess)  // (the device tables are there once build_levels has run)
+    e = launch(e, merkle_aunts_kernel, 8 * L, s, dev_nodes(c), dev_lvl_off(c), dev_tab(c, plan), (uint32_t)T,
+               (uint32_t)plan.nlevels, (uint32_t)L, (const uint64_t *)c->d_proof_off.p, (uint32_t *)d_res,
+               (uint32_t *)(d_res + o_leaf));
   if (e == hipSuccess) e = hipEventRecord(c->ev1, s);
   if (e == hipSuccess && need) e = hipMemcpyAsync(o.aunts, d_res, need, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess && L) e = hipMemcpyAsync(o.leaf_hashes, d_res + o_leaf, 32 * L, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipMemcpyAsync(o.roots, d_res + o_root, 32 * T, hipMemcpyDeviceToHost, s);
-  // (a failed call still waits: the host vectors above are the sources of queued copies)
-  const hipError_t es = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) return map_err(e);
-  (void)hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1);
-  return TMED_OK;
+  return finish_call(c, e, /*timed=*/true);
 }
 
 // The common tail of the three generators: size the aunts on the host (merkle_path.h), answer a
@@ -741,13 +758,8 @@ int proofs_from_host_leaves(tmed_ctx *c, const uint8_t *leaves, const uint64_t *
   if (o.aunts && o.aunts_cap < need) return TMED_ENOMEM;
   if (o.aunts) {
     if (!o.roots || (L && !o.leaf_hashes)) return TMED_EINVAL;
-    int rc;
-    {
-      std::lock_guard<std::mutex> lk(c->mu);
-      rc = bs_collect_submitted(c);  // submitted blocksync windows are collected first (the seam's rule)
-      if (rc == TMED_OK) rc = proofs_locked(c, leaves, leaf_off, L, counts, txs, ao, o);
-    }
-    bs_release_collected(c);
+    const int rc =
+        locked(c, /*collect=*/true, [&] { return proofs_locked(c, leaves, leaf_off, L, counts, txs, ao, o); });
     if (rc != TMED_OK) return rc;
   }
   memcpy(o.aunt_off, ao.data(), (L + 1) * 8);
@@ -797,23 +809,45 @@ int verify_proofs_locked(tmed_ctx *c, const ProofIn &in, const std::vector<uint6
   if (e == hipSuccess) e = hipMemcpyAsync(d_in + o_idx, in.indexes, 8 * n, hipMemcpyHostToDevice, s);
   if (e == hipSuccess && in.root_of) e = hipMemcpyAsync(d_in + o_rof, in.root_of, 4 * n, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipEventRecord(c->ev0, s);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(merkle_verify_kernel, dim3(blocks_for(n)), dim3(256), 0, s, (const uint8_t *)c->d_msg.p,
-                       (const uint64_t *)c->d_off.p, (const uint8_t *)d_in, (const int64_t *)(d_in + o_tot),
-                       (const int64_t *)(d_in + o_idx), (const uint64_t *)c->d_proof_off.p,
-                       (const uint8_t *)c->d_merkle_lv.p, (const uint8_t *)(d_in + o_root),
-                       in.root_of ? (const uint32_t *)(d_in + o_rof) : nullptr, (uint32_t)n,
-                       (uint8_t *)c->d_proof_out.p);
-    e = hipGetLastError();
-  }
+  e = launch(e, merkle_verify_kernel, n, s, (const uint8_t *)c->d_msg.p, (const uint64_t *)c->d_off.p,
+             (const uint8_t *)d_in, (const int64_t *)(d_in + o_tot), (const int64_t *)(d_in + o_idx),
+             (const uint64_t *)c->d_proof_off.p, (const uint8_t *)c->d_merkle_lv.p, (const uint8_t *)(d_in + o_root),
+             in.root_of ? (const uint32_t *)(d_in + o_rof) : nullptr, (uint32_t)n, (uint8_t *)c->d_proof_out.p);
   if (e == hipSuccess) e = hipEventRecord(c->ev1, s);
   if (e == hipSuccess) e = hipMemcpyAsync(out_code, c->d_proof_out.p, n, hipMemcpyDeviceToHost, s);
-  // (a failed call still waits: off is the source of queued copies)
-  const hipError_t es = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) return map_err(e);
-  (void)hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1);
-  return TMED_OK;
+  return finish_call(c, e, /*timed=*/true);
+}
+
+// tmed_merkle_roots, and tmed_txs_hashes (txs) over blocks of transactions
+int forest_roots(tmed_ctx *c, const uint8_t *leaves, const uint64_t *leaf_off, const uint32_t *tree_off,
+                 size_t n_trees, uint8_t *roots, bool txs) {
+  if (!c || (n_trees && (!tree_off || !roots || !leaf_off))) return TMED_EINVAL;
+  if (n_trees == 0) return TMED_OK;
+  return guarded([&] {
+    std::vector<uint32_t> counts;
+    const int rc = forest_counts(tree_off, n_trees, leaf_off, leaves, counts);
+    if (rc != TMED_OK) return rc;
+    return locked(c, /*collect=*/false, [&] {
+      return roots_from_host_leaves_locked(c, leaves, leaf_off, tree_off[n_trees], counts, roots, txs);
+    });
+  });
+}
+
+// tmed_merkle_proofs, and tmed_txs_proofs (txs) over blocks of transactions
+int forest_proofs(tmed_ctx *c, const uint8_t *leaves, const uint64_t *leaf_off, const uint32_t *tree_off,
+                  size_t n_trees, bool txs, const ProofOut &o) {
+  if (!c || !o.aunt_off || !o.aunts_len || (n_trees && (!tree_off || !leaf_off))) return TMED_EINVAL;
+  if (n_trees == 0) {
+    o.aunt_off[0] = 0;
+    *o.aunts_len = 0;
+    return TMED_OK;
+  }
+  return guarded([&] {
+    std::vector<uint32_t> counts;
+    const int rc = forest_counts(tree_off, n_trees, leaf_off, leaves, counts);
+    if (rc != TMED_OK) return rc;
+    return proofs_from_host_leaves(c, leaves, leaf_off, tree_off[n_trees], counts, txs, o);
+  });
 }
 
 }  // namespace
@@ -832,26 +866,22 @@ int valset_hashes_locked(tmed_ctx *c, const uint8_t *pubkeys, const int64_t *pow
   const size_t N = set_off[n_sets];
   std::vector<uint32_t> counts(n_sets);
   for (size_t t = 0; t < n_sets; t++) counts[t] = set_off[t + 1] - set_off[t];
+  const MerkleLevels plan(counts);
   (void)hipSetDevice(c->device);
   hipStream_t s = c->stream;
+  const int rc = ensure_nodes(c, plan);
+  if (rc != TMED_OK) return rc;
   hipError_t e = c->d_a.ensure(std::max<size_t>(N, 1) * 32);
   if (e == hipSuccess) e = c->d_b.ensure(std::max<size_t>(N, 1) * 8);
-  if (e == hipSuccess) e = c->d_merkle_a.ensure(std::max<size_t>(N, 1) * sizeof(Digest));
   if (e == hipSuccess) e = c->d_out.ensure(n_sets * 32);
   if (e == hipSuccess && N) e = hipMemcpyAsync(c->d_a.p, pubkeys, N * 32, hipMemcpyHostToDevice, s);
   if (e == hipSuccess && N) e = hipMemcpyAsync(c->d_b.p, powers, N * 8, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && N) {
-    hipLaunchKernelGGL(valset_leaf_kernel, dim3(blocks_for(N)), dim3(256), 0, s, (const uint8_t *)c->d_a.p,
-                       (const int64_t *)c->d_b.p, (uint32_t)N, (Digest *)c->d_merkle_a.p);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return map_err(e);
-  int rc = reduce_trees(c, counts, N, (uint8_t *)c->d_out.p, s);
-  if (rc != TMED_OK) return rc;
-  e = hipMemcpyAsync(out, c->d_out.p, n_sets * 32, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  return map_err(e);
+  e = launch(e, valset_leaf_kernel, N, s, (const uint8_t *)c->d_a.p, (const int64_t *)c->d_b.p, (uint32_t)N,
+             dev_nodes(c));
+  if (e == hipSuccess) e = build_levels(c, plan, s);
+  if (e == hipSuccess) e = emit_roots(c, plan, (uint8_t *)c->d_out.p, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(out, c->d_out.p, n_sets * 32, hipMemcpyDeviceToHost, s);
+  return finish_call(c, e, /*timed=*/false);
 }
 
 // ValidatorSet.Hash of n_sets validator sets given as structs: their keys and powers are packed
@@ -913,8 +943,7 @@ extern "C" {
 int tmed_commit_hashes(tmed_ctx *c, const tmed_commit *commits, size_t n, uint8_t *out, uint8_t *ok) {
   if (!c || (n && (!commits || !out || !ok))) return TMED_EINVAL;
   if (n == 0) return TMED_OK;
-  int rc;
-  try {
+  return guarded([&] {
     std::vector<uint32_t> counts(n);
     std::vector<size_t> base(n);
     size_t N = 0, all = 0;
@@ -931,61 +960,23 @@ int tmed_commit_hashes(tmed_ctx *c, const tmed_commit *commits, size_t n, uint8_
       N += counts[i];
       if (N > 0xffffffffu) return TMED_EINVAL;
     }
-    {
-      std::lock_guard<std::mutex> lk(c->mu);
-      rc = bs_collect_submitted(c);  // submitted blocksync windows are collected first (the seam's rule)
-      if (rc == TMED_OK) rc = commit_hashes_locked(c, commits, n, counts, base, N, out);
-    }
-    bs_release_collected(c);
-  } catch (const std::bad_alloc &) {
-    return TMED_ENOMEM;
-  } catch (...) {
-    return TMED_EINTERNAL;
-  }
-  if (rc != TMED_OK) return rc;
-  for (size_t i = 0; i < n; i++)
-    if (!ok[i]) memset(out + 32 * i, 0, 32);
-  return TMED_OK;
+    const int rc =
+        locked(c, /*collect=*/true, [&] { return commit_hashes_locked(c, commits, n, counts, base, N, out); });
+    if (rc != TMED_OK) return rc;
+    for (size_t i = 0; i < n; i++)
+      if (!ok[i]) memset(out + 32 * i, 0, 32);
+    return TMED_OK;
+  });
 }
 
 int tmed_txs_hashes(tmed_ctx *c, const uint8_t *txs, const uint64_t *tx_off, const uint32_t *block_off,
                     size_t n_blocks, uint8_t *out) {
-  if (!c || (n_blocks && (!block_off || !out || !tx_off))) return TMED_EINVAL;
-  if (n_blocks == 0) return TMED_OK;
-  const size_t L = block_off[n_blocks];
-  if (block_off[0] != 0 || L > 0xffffffffu) return TMED_EINVAL;
-  try {
-    std::vector<uint32_t> counts(n_blocks);
-    for (size_t b = 0; b < n_blocks; b++) {
-      if (block_off[b + 1] < block_off[b]) return TMED_EINVAL;
-      counts[b] = block_off[b + 1] - block_off[b];
-    }
-    for (size_t i = 0; i < L; i++)
-      if (tx_off[i + 1] < tx_off[i] || tx_off[i + 1] - tx_off[i] > 0xffffffffu - 64) return TMED_EINVAL;
-    if (L && tx_off[L] > tx_off[0] && !txs) return TMED_EINVAL;
-    return roots_from_host_leaves(c, txs, tx_off, L, counts, out, /*txs=*/true);
-  } catch (const std::bad_alloc &) {
-    return TMED_ENOMEM;
-  } catch (...) {
-    return TMED_EINTERNAL;
-  }
+  return forest_roots(c, txs, tx_off, block_off, n_blocks, out, /*txs=*/true);
 }
 
 int tmed_merkle_roots(tmed_ctx *c, const uint8_t *leaves, const uint64_t *leaf_off, const uint32_t *tree_off,
                       size_t n_trees, uint8_t *roots) {
-  if (!c || (n_trees && (!tree_off || !roots || !leaf_off))) return TMED_EINVAL;
-  if (n_trees == 0) return TMED_OK;
-  const size_t L = tree_off[n_trees];
-  if (tree_off[0] != 0 || L > 0xffffffffu) return TMED_EINVAL;
-  std::vector<uint32_t> counts(n_trees);
-  for (size_t t = 0; t < n_trees; t++) {
-    if (tree_off[t + 1] < tree_off[t]) return TMED_EINVAL;
-    counts[t] = tree_off[t + 1] - tree_off[t];
-  }
-  for (size_t i = 0; i < L; i++)
-    if (leaf_off[i + 1] < leaf_off[i] || leaf_off[i + 1] - leaf_off[i] > 0xffffffffu - 64) return TMED_EINVAL;
-  if (L && leaf_off[L] > leaf_off[0] && !leaves) return TMED_EINVAL;
-  return roots_from_host_leaves(c, leaves, leaf_off, L, counts, roots);
+  return forest_roots(c, leaves, leaf_off, tree_off, n_trees, roots, /*txs=*/false);
 }
 
 int tmed_valset_hashes(tmed_ctx *c, const uint8_t *pubkeys, const int64_t *powers, const uint32_t *set_off,
@@ -993,11 +984,12 @@ int tmed_valset_hashes(tmed_ctx *c, const uint8_t *pubkeys, const int64_t *power
   if (!c || (n_sets && (!set_off || !out))) return TMED_EINVAL;
   if (n_sets == 0) return TMED_OK;
   const size_t N = set_off[n_sets];
-  if (set_off[0] != 0 || N > 0xffffffffu || (N && (!pubkeys || !powers))) return TMED_EINVAL;
+  if (set_off[0] != 0 || (N && (!pubkeys || !powers))) return TMED_EINVAL;
   for (size_t t = 0; t < n_sets; t++)
     if (set_off[t + 1] < set_off[t]) return TMED_EINVAL;
-  std::lock_guard<std::mutex> lk(c->mu);
-  return valset_hashes_locked(c, pubkeys, powers, set_off, n_sets, out);
+  return guarded([&] {
+    return locked(c, /*collect=*/false, [&] { return valset_hashes_locked(c, pubkeys, powers, set_off, n_sets, out); });
+  });
 }
 
 int tmed_header_hashes(tmed_ctx *c, const tmed_header *headers, size_t n, uint8_t *out, uint8_t *ok) {
@@ -1005,34 +997,24 @@ int tmed_header_hashes(tmed_ctx *c, const tmed_header *headers, size_t n, uint8_
   if (n == 0) return TMED_OK;
   for (size_t i = 0; i < n; i++)
     if (!header_pointers_ok(headers[i])) return TMED_EINVAL;
-  try {
-    std::lock_guard<std::mutex> lk(c->mu);
-    return header_hashes_locked(c, headers, n, out, ok);
-  } catch (const std::bad_alloc &) {
-    return TMED_ENOMEM;
-  } catch (...) {
-    return TMED_EINTERNAL;
-  }
+  return guarded([&] {
+    return locked(c, /*collect=*/false, [&] { return header_hashes_locked(c, headers, n, out, ok); });
+  });
 }
 
 int tmed_partset_roots(tmed_ctx *c, const uint8_t *data, const uint64_t *data_off, size_t n_blocks,
                        uint32_t part_size, uint8_t *roots) {
   if (!c || part_size == 0 || (n_blocks && (!data_off || !roots))) return TMED_EINVAL;
   if (n_blocks == 0) return TMED_OK;
-  std::vector<uint64_t> off;
-  std::vector<uint32_t> counts(n_blocks);
-  off.push_back(data_off[0]);
-  for (size_t b = 0; b < n_blocks; b++) {
-    if (data_off[b + 1] < data_off[b]) return TMED_EINVAL;
-    const uint64_t len = data_off[b + 1] - data_off[b];
-    const uint64_t parts = (len + part_size - 1) / part_size;  // types/part_set.go:168
-    if (parts > 0xffffffffu) return TMED_EINVAL;
-    counts[b] = (uint32_t)parts;
-    for (uint64_t p = 0; p < parts; p++) off.push_back(std::min(data_off[b] + (p + 1) * part_size, data_off[b + 1]));
-  }
-  const size_t L = off.size() - 1;
-  if (L > 0xffffffffu || (L && !data)) return TMED_EINVAL;
-  return roots_from_host_leaves(c, data, off.data(), L, counts, roots);
+  return guarded([&] {
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> counts;
+    const int rc = split_parts(data, data_off, n_blocks, part_size, off, counts, nullptr);
+    if (rc != TMED_OK) return rc;
+    return locked(c, /*collect=*/false, [&] {
+      return roots_from_host_leaves_locked(c, data, off.data(), off.size() - 1, counts, roots);
+    });
+  });
 }
 
 // ---- Merkle proofs (the generators share proofs_from_host_leaves; arguments checked as the root calls)
@@ -1040,59 +1022,15 @@ int tmed_partset_roots(tmed_ctx *c, const uint8_t *data, const uint64_t *data_of
 int tmed_merkle_proofs(tmed_ctx *c, const uint8_t *leaves, const uint64_t *leaf_off, const uint32_t *tree_off,
                        size_t n_trees, uint8_t *roots, uint8_t *leaf_hashes, uint64_t *aunt_off, uint8_t *aunts,
                        size_t aunts_cap, size_t *aunts_len) {
-  if (!c || !aunt_off || !aunts_len || (n_trees && (!tree_off || !leaf_off))) return TMED_EINVAL;
-  if (n_trees == 0) {
-    aunt_off[0] = 0;
-    *aunts_len = 0;
-    return TMED_OK;
-  }
-  const size_t L = tree_off[n_trees];
-  if (tree_off[0] != 0 || L > 0xffffffffu) return TMED_EINVAL;
-  try {
-    std::vector<uint32_t> counts(n_trees);
-    for (size_t t = 0; t < n_trees; t++) {
-      if (tree_off[t + 1] < tree_off[t]) return TMED_EINVAL;
-      counts[t] = tree_off[t + 1] - tree_off[t];
-    }
-    for (size_t i = 0; i < L; i++)
-      if (leaf_off[i + 1] < leaf_off[i] || leaf_off[i + 1] - leaf_off[i] > 0xffffffffu - 64) return TMED_EINVAL;
-    if (L && leaf_off[L] > leaf_off[0] && !leaves) return TMED_EINVAL;
-    return proofs_from_host_leaves(c, leaves, leaf_off, L, counts, /*txs=*/false,
-                                   ProofOut{roots, leaf_hashes, aunt_off, aunts, aunts_cap, aunts_len});
-  } catch (const std::bad_alloc &) {
-    return TMED_ENOMEM;
-  } catch (...) {
-    return TMED_EINTERNAL;
-  }
+  return forest_proofs(c, leaves, leaf_off, tree_off, n_trees, /*txs=*/false,
+                       ProofOut{roots, leaf_hashes, aunt_off, aunts, aunts_cap, aunts_len});
 }
 
 int tmed_txs_proofs(tmed_ctx *c, const uint8_t *txs, const uint64_t *tx_off, const uint32_t *block_off,
                     size_t n_blocks, uint8_t *roots, uint8_t *leaf_hashes, uint64_t *aunt_off, uint8_t *aunts,
                     size_t aunts_cap, size_t *aunts_len) {
-  if (!c || !aunt_off || !aunts_len || (n_blocks && (!block_off || !tx_off))) return TMED_EINVAL;
-  if (n_blocks == 0) {
-    aunt_off[0] = 0;
-    *aunts_len = 0;
-    return TMED_OK;
-  }
-  const size_t L = block_off[n_blocks];
-  if (block_off[0] != 0 || L > 0xffffffffu) return TMED_EINVAL;
-  try {
-    std::vector<uint32_t> counts(n_blocks);
-    for (size_t b = 0; b < n_blocks; b++) {
-      if (block_off[b + 1] < block_off[b]) return TMED_EINVAL;
-      counts[b] = block_off[b + 1] - block_off[b];
-    }
-    for (size_t i = 0; i < L; i++)
-      if (tx_off[i + 1] < tx_off[i] || tx_off[i + 1] - tx_off[i] > 0xffffffffu - 64) return TMED_EINVAL;
-    if (L && tx_off[L] > tx_off[0] && !txs) return TMED_EINVAL;
-    return proofs_from_host_leaves(c, txs, tx_off, L, counts, /*txs=*/true,
-                                   ProofOut{roots, leaf_hashes, aunt_off, aunts, aunts_cap, aunts_len});
-  } catch (const std::bad_alloc &) {
-    return TMED_ENOMEM;
-  } catch (...) {
-    return TMED_EINTERNAL;
-  }
+  return forest_proofs(c, txs, tx_off, block_off, n_blocks, /*txs=*/true,
+                       ProofOut{roots, leaf_hashes, aunt_off, aunts, aunts_cap, aunts_len});
 }
 
 int tmed_partset_proofs(tmed_ctx *c, const uint8_t *data, const uint64_t *data_off, size_t n_blocks,
@@ -1105,31 +1043,16 @@ int tmed_partset_proofs(tmed_ctx *c, const uint8_t *data, const uint64_t *data_o
     *aunts_len = 0;
     return TMED_OK;
   }
-  try {
+  return guarded([&] {
     std::vector<uint64_t> off;
-    std::vector<uint32_t> counts(n_blocks), poff(n_blocks + 1);
-    off.push_back(data_off[0]);
-    for (size_t b = 0; b < n_blocks; b++) {
-      if (data_off[b + 1] < data_off[b]) return TMED_EINVAL;
-      const uint64_t len = data_off[b + 1] - data_off[b];
-      const uint64_t parts = (len + part_size - 1) / part_size;  // types/part_set.go:168
-      if (parts > 0xffffffffu || off.size() - 1 + parts > 0xffffffffu) return TMED_EINVAL;
-      counts[b] = (uint32_t)parts;
-      poff[b] = (uint32_t)(off.size() - 1);
-      for (uint64_t p = 0; p < parts; p++) off.push_back(std::min(data_off[b] + (p + 1) * part_size, data_off[b + 1]));
-    }
-    const size_t L = off.size() - 1;
-    poff[n_blocks] = (uint32_t)L;
-    if (L && !data) return TMED_EINVAL;
-    const int rc = proofs_from_host_leaves(c, data, off.data(), L, counts, /*txs=*/false,
-                                           ProofOut{roots, leaf_hashes, aunt_off, aunts, aunts_cap, aunts_len});
+    std::vector<uint32_t> counts, poff(n_blocks + 1);
+    int rc = split_parts(data, data_off, n_blocks, part_size, off, counts, poff.data());
+    if (rc != TMED_OK) return rc;
+    rc = proofs_from_host_leaves(c, data, off.data(), off.size() - 1, counts, /*txs=*/false,
+                                 ProofOut{roots, leaf_hashes, aunt_off, aunts, aunts_cap, aunts_len});
     if (rc == TMED_OK) memcpy(part_off, poff.data(), (n_blocks + 1) * 4);
     return rc;
-  } catch (const std::bad_alloc &) {
-    return TMED_ENOMEM;
-  } catch (...) {
-    return TMED_EINTERNAL;
-  }
+  });
 }
 
 int tmed_merkle_proofs_verify(tmed_ctx *c, size_t n, const uint8_t *roots, size_t n_roots, const uint32_t *root_of,
@@ -1148,8 +1071,7 @@ int tmed_merkle_proofs_verify(tmed_ctx *c, size_t n, const uint8_t *roots, size_
   const size_t bytes = leaf_off[n] - leaf_off[0];
   const uint64_t A = aunt_off[n] - aunt_off[0];
   if ((bytes && !leaves) || (A && !aunts) || A > (~(size_t)0 >> 5)) return TMED_EINVAL;
-  int rc;
-  try {
+  return guarded([&] {
     std::vector<uint64_t> off(2 * (n + 1));  // leaf offsets, then aunt offsets, both from 0
     for (size_t i = 0; i <= n; i++) {
       off[i] = leaf_off[i] - leaf_off[0];
@@ -1157,18 +1079,8 @@ int tmed_merkle_proofs_verify(tmed_ctx *c, size_t n, const uint8_t *roots, size_
     }
     const ProofIn in{n, roots, n_roots, root_of, bytes ? leaves + leaf_off[0] : nullptr, bytes, leaf_hashes, totals,
                      indexes, A ? aunts + 32 * aunt_off[0] : nullptr, (size_t)A};
-    {
-      std::lock_guard<std::mutex> lk(c->mu);
-      rc = bs_collect_submitted(c);  // submitted blocksync windows are collected first (the seam's rule)
-      if (rc == TMED_OK) rc = verify_proofs_locked(c, in, off, out_code);
-    }
-    bs_release_collected(c);
-  } catch (const std::bad_alloc &) {
-    return TMED_ENOMEM;
-  } catch (...) {
-    return TMED_EINTERNAL;
-  }
-  return rc;
+    return locked(c, /*collect=*/true, [&] { return verify_proofs_locked(c, in, off, out_code); });
+  });
 }
 
 }  // extern "C"

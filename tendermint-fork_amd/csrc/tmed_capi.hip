@@ -226,9 +226,8 @@ void tmed_destroy(tmed_ctx *c) {
   lane_release(c->lane1);
   for (DevBuf *b : {&c->d_a, &c->d_b, &c->d_msg, &c->d_off, &c->d_out, &c->d_c}) b->release();
   for (HostBuf *b : {&c->h_a, &c->h_b, &c->h_msg, &c->h_off, &c->h_out, &c->h_c}) b->release();
-  for (DevBuf *b : {&c->d_merkle_a, &c->d_merkle_b, &c->d_merkle_idx, &c->d_merkle_lv, &c->d_merkle_tab, &c->d_proof_off,
-                    &c->d_proof_out, &c->d_proof_in, &c->d_korder, &c->d_zip, &c->d_kbases,
-                    &c->d_csig, &c->d_hdr})
+  for (DevBuf *b : {&c->d_merkle_lv, &c->d_merkle_tab, &c->d_proof_off, &c->d_proof_out, &c->d_proof_in, &c->d_korder,
+                    &c->d_zip, &c->d_kbases, &c->d_csig, &c->d_hdr})
     b->release();
   c->h_csig.release();
   c->h_hdr.release();

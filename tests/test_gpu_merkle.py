@@ -74,6 +74,55 @@ def test_header_hashes_gpu(engine):
     assert any(g is None for g in got)
 
 
+MIXED_SIZES = [0, 1, 4097, 1, 0, 2, 3]
+
+
+def test_mixed_depth_forest_roots_gpu(engine):
+    """Every root call over trees of MIXED_SIZES leaves: 13 levels, the 4097th leaf promoted through
+    every one of them, empty and single-node trees carried beside it through the kept levels."""
+    import blockhash_cases as B
+    from tmed.merkle import commit_hashes, merkle_roots, txs_hashes, valset_hashes_arrays
+    rng = random.Random(4097)
+    trees = [[rng.randbytes(rng.randrange(0, 70)) for _ in range(n)] for n in MIXED_SIZES]
+    for t, g in zip(trees, merkle_roots(engine, trees)):
+        assert g == M.hash_from_byte_slices(t), len(t)
+    for t, g in zip(trees, txs_hashes(engine, trees)):
+        assert g == B.txs_hash(t), len(t)
+    nrng = np.random.default_rng(4097)
+    n = sum(MIXED_SIZES)
+    pubs = nrng.integers(0, 256, (n, 32), dtype=np.uint8)
+    powers = nrng.integers(0, 1 << 40, n, dtype=np.int64)
+    powers[::7] = 0
+    off = np.zeros(len(MIXED_SIZES) + 1, np.uint32)
+    off[1:] = np.cumsum(MIXED_SIZES)
+    got = valset_hashes_arrays(engine, pubs, powers, off)
+    for s, size in enumerate(MIXED_SIZES):
+        vals = [(bytes(pubs[i]), int(powers[i])) for i in range(off[s], off[s + 1])]
+        assert bytes(got[s]) == M.valset_hash(vals), size
+    sweep = B.cycle_sigs()
+    stream = sweep * (n // len(sweep) + 1)
+    lists = [stream[int(off[s]):int(off[s + 1])] for s in range(len(MIXED_SIZES))]
+    got = commit_hashes(engine, [B.packed_commit(l) for l in lists])
+    for l, g in zip(lists, got):
+        assert g == B.commit_hash(l), len(l)
+
+
+def test_roots_equal_proof_roots_gpu(engine):
+    """One byte-slice forest through tmed_merkle_roots and tmed_merkle_proofs: byte-equal roots.  Then
+    a root call directly after a proof-verify call (both use the engine's one node buffer: the verify
+    call keeps its aunts there): still the oracle's roots."""
+    from tmed.merkle import merkle_proofs, merkle_roots, verify_proofs
+    rng = random.Random(77)
+    trees = [[rng.randbytes(rng.randrange(0, 40)) for _ in range(n)] for n in [5, 0, 1, 300, 2, 0, 33, 64, 65]]
+    exp = [M.hash_from_byte_slices(t) for t in trees]
+    roots = merkle_roots(engine, trees)
+    proofs = merkle_proofs(engine, trees)
+    assert [r for r, _ in proofs] == roots == exp
+    items = [(root, trees[t][p[1]], p) for t, (root, ps) in enumerate(proofs) for p in ps]
+    assert verify_proofs(engine, items) == [0] * len(items)
+    assert merkle_roots(engine, trees) == exp
+
+
 @pytest.mark.parametrize("part_size", [64, 100, 65536])
 def test_partset_roots_gpu(engine, part_size):
     from tmed.merkle import partset_roots

@@ -3,6 +3,7 @@ checks, the path arithmetic the host sizing and the kernels share (csrc/merkle_p
 the host against that restatement, the argument / sizing / ENOMEM behaviour of the four C-ABI calls
 that runs before any device work, and the static check of the Go binding with its proof tests."""
 import ctypes
+import hashlib
 import os
 import random
 import subprocess
@@ -33,6 +34,9 @@ def proofpath_host(tmp_path_factory):
     l.pp_path.restype = ctypes.c_int
     l.pp_path.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint32),
                           ctypes.POINTER(ctypes.c_uint64)]
+    l.pp_level_plan.restype = ctypes.c_uint32
+    l.pp_level_plan.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+                                ctypes.POINTER(ctypes.c_uint64)]
     return l
 
 
@@ -112,6 +116,108 @@ def test_path_header_large_totals(proofpath_host):
     assert _path(proofpath_host, 0, 2 ** 63 - 1) == (63, 0)
     for total in (0, -1, -2 ** 63):
         assert _path(proofpath_host, 0, total) is None
+
+
+# ---- csrc/merkle_levels.h on the host: the plan walked as the kernels walk it -----------------------
+
+PLAN_FORESTS = [[], [0], [1], [0, 0], [2], [3], [0, 1, 2, 3, 5, 0, 1, 33], [1, 257, 1]] + [[n] for n in range(71)]
+CAP_LEVELS = 40
+
+
+def _level_plan(l, counts):
+    """(nlevels, lvl_off, tab rows, nodes) of csrc/merkle_levels.h for trees of counts leaves."""
+    T = len(counts)
+    c = np.asarray(counts, np.uint32)
+    lvl_off = np.full(CAP_LEVELS, 2 ** 64 - 1, np.uint64)
+    tab = np.full((CAP_LEVELS, T + 1), 2 ** 32 - 1, np.uint32)
+    nodes = ctypes.c_uint64(0)
+    nlevels = l.pp_level_plan(_p(c), T, CAP_LEVELS, _p(lvl_off), _p(tab), ctypes.byref(nodes))
+    assert 1 <= nlevels <= 33
+    return nlevels, [int(x) for x in lvl_off[:nlevels]], [[int(x) for x in r] for r in tab[:nlevels]], nodes.value
+
+
+def _last_tree_at(base, ntrees, j):
+    """The kernels' search: the last t with base[t] <= j (trees with nothing there are skipped)."""
+    lo, hi = 0, ntrees
+    while hi - lo > 1:
+        mid = (lo + hi) >> 1
+        if base[mid] <= j:
+            lo = mid
+        else:
+            hi = mid
+    return lo
+
+
+def _build_levels(counts, nlevels, lvl_off, tab, leaf_hashes, nodes):
+    """merkle_level_kernel, level by level, over one node buffer laid out by the plan."""
+    T = len(counts)
+    buf = [None] * nodes
+    buf[:len(leaf_hashes)] = leaf_hashes
+    for l in range(nlevels - 1):
+        in_base, out_base = tab[l], tab[l + 1]
+        for j in range(out_base[T]):
+            t = _last_tree_at(out_base, T, j)
+            k = j - out_base[t]
+            c = in_base[t + 1] - in_base[t]
+            src = lvl_off[l] + in_base[t] + 2 * k
+            assert 2 * k < c, "an output node without an input"
+            if 2 * k + 1 < c:
+                buf[lvl_off[l + 1] + j] = hashlib.sha256(b"\x01" + buf[src] + buf[src + 1]).digest()
+            else:
+                buf[lvl_off[l + 1] + j] = buf[src]  # odd node promoted
+    return buf
+
+
+def _aunts(counts, nlevels, lvl_off, tab, buf, i, n_aunts):
+    """merkle_aunts_kernel for leaf i, whose aunt range holds n_aunts hashes."""
+    T = len(counts)
+    t = _last_tree_at(tab[0], T, i)
+    p = i - tab[0][t]
+    out = []
+    for l in range(nlevels):
+        if len(out) >= n_aunts:
+            break
+        base, c = tab[l][t], tab[l][t + 1] - tab[l][t]
+        if c <= 1:
+            break
+        if p ^ 1 < c:
+            out.append(buf[lvl_off[l] + base + (p ^ 1)])
+        p >>= 1
+    return out
+
+
+@pytest.mark.parametrize("counts", PLAN_FORESTS, ids=lambda c: "-".join(map(str, c)) or "none")
+def test_level_plan_walked_as_the_kernels_do(proofpath_host, counts):
+    """The plan of merkle_levels.h, walked in Python exactly as merkle_level_kernel, merkle_emit_kernel
+    and merkle_aunts_kernel walk it: the last level holds HashFromByteSlices of every tree, the aunts
+    are the restatement's, and the plan keeps its bounds (nodes <= 2 L + 32 T, nlevels <= 33)."""
+    T, L = len(counts), sum(counts)
+    trees, at = [], 0
+    for n in counts:
+        trees.append([b"leaf %d" % i + bytes(i % 5) for i in range(at, at + n)])
+        at += n
+    nlevels, lvl_off, tab, nodes = _level_plan(proofpath_host, counts)
+    assert nodes <= 2 * L + 32 * T
+    assert tab[0] == [sum(counts[:t]) for t in range(T + 1)] and lvl_off[0] == 0
+    assert nodes == sum(r[T] for r in tab) and lvl_off == [sum(r[T] for r in tab[:l]) for l in range(nlevels)]
+    leaf_hashes = [hashlib.sha256(b"\x00" + x).digest() for t in trees for x in t]
+    buf = _build_levels(counts, nlevels, lvl_off, tab, leaf_hashes, nodes)
+    assert None not in buf
+    last = tab[nlevels - 1]
+    for t, items in enumerate(trees):  # merkle_emit_kernel
+        assert last[t + 1] - last[t] == (1 if items else 0)
+        root = buf[lvl_off[nlevels - 1] + last[t]] if items else hashlib.sha256(b"").digest()
+        assert root == M.hash_from_byte_slices(items), (t, len(items))
+    i = 0
+    for items in trees:
+        n = len(items)
+        sized = np.zeros(n + 1, np.uint32)
+        proofpath_host.pp_aunt_counts(n, _p(sized))
+        _, proofs = P.proofs_from_byte_slices(items)
+        for p in range(n):
+            assert proofs[p][2] == buf[i]  # Proof.LeafHash is the level-0 node
+            assert _aunts(counts, nlevels, lvl_off, tab, buf, i, int(sized[p])) == proofs[p][3], (n, p)
+            i += 1
 
 
 # ---- the C ABI before the device ------------------------------------------------------------------
