@@ -16,6 +16,10 @@
   --config c4   blocksync replay: B blocks x V validators, VerifyCommitLight per block
                 (blockchain/v0/reactor.go:366-367), key-cached; with N ranks the blocks are
                 sharded and the per-rank int64 tallies all-reduced (RCCL; gloo on CPU).
+  --config mt   block time: state.MedianTime (state/validation.go:123-129) for 1,000 commits x 10,000
+                validators and 10,000 x 175, all aligned, one tmed_median_times call per shape: calls/s
+                and the selection kernels' device time, the same pairs through tmed_median_times_host
+                on one thread, and tmed_verify_commits (VerifyCommit) over the same commits for scale.
 Synthetic data (seeded keys, GPU RFC 8032 signer); prints one JSON line per config.
 """
 from __future__ import annotations
@@ -1002,6 +1006,66 @@ def c4(eng, blocks: int, nvals: int, rank: int, world: int, dev, window: int, ba
                        "keyset_build_s": round(t_ks, 3), "generate_s": round(t_gen, 2)}}
 
 
+def mt(eng, runs: int, shapes=((1000, 10_000), (10_000, 175))):
+    """MedianTime of every commit of a window against the window's validator set, per shape
+    (commits, validators): one tmed_median_times call (each commit staged once, the set once), the
+    same PreparedMedian through tmed_median_times_host (one thread, GetByAddress as a hash lookup,
+    a weighted quickselect), and tmed_verify_commits in TMED_MODE_COMMIT over the same commits (all
+    signatures valid; warmed, so the key-set cache holds the set).  Votes are stamped base + i ms
+    for validator i, powers are 1 + (i mod 100).  Medians of `runs` timed calls."""
+    import tmed.state as S
+    import tmed.types as T
+    from tmed.workload import make_valset, pubkeys_of, seeds_from_tag, sign_commits
+    med = lambda xs: float(np.median(xs))
+    out = []
+    for blocks, nvals in shapes:
+        seeds = seeds_from_tag(b"tmed-mt-key", 0, nvals)
+        pubs = pubkeys_of(eng, seeds)
+        vals, order = make_valset(pubs, [1 + i % 100 for i in range(nvals)])
+        addrs = np.array([np.frombuffer(v.address, np.uint8) for v in vals.validators])
+        commits = []
+        step = max(1, 2_500_000 // nvals)  # signatures per signing call
+        for b0 in range(0, blocks, step):
+            specs = [(seeds[order], addrs, b + 1, 0, block_id(b"mt-%d" % (b + 1)), T2023 + b, None)
+                     for b in range(b0, min(blocks, b0 + step))]
+            commits += sign_commits(eng, "test_chain_id", specs)
+        print("mt: %d commits x %d validators generated" % (blocks, nvals), file=sys.stderr, flush=True)
+        pm = S.PreparedMedian([(c, vals) for c in commits])
+        pm.run(eng)  # warm: the staging buffers are allocated
+        wall, dev = [], []
+        for _ in range(runs):
+            t0 = time.perf_counter()
+            pm.run(eng)
+            wall.append(time.perf_counter() - t0)
+            dev.append(eng.last_kernel_ms())
+        got, on_device = pm.results(), int(pm.on_device().sum())
+        host = []
+        for _ in range(min(runs, 3)):
+            t0 = time.perf_counter()
+            pm.run(None)
+            host.append(time.perf_counter() - t0)
+        same = pm.results() == got
+        pb = T.PreparedBatch([(T.MODE_COMMIT, vals, "test_chain_id", c.block_id, c.height, c, 0, 0) for c in commits])
+        for _ in range(2):  # the first call builds the set's keys, the second is keyed
+            pb.run(eng)
+        eng.keycache_wait()
+        ver, ver_dev = [], []
+        for _ in range(min(runs, 3)):
+            t0 = time.perf_counter()
+            pb.run(eng)
+            ver.append(time.perf_counter() - t0)
+            ver_dev.append(eng.last_kernel_ms())
+        out.append({"commits": blocks, "validators": nvals, "pairs_on_device": on_device,
+                    "device_equals_host": bool(same), "all_ok": all(r[0] == 0 for r in got),
+                    "median_call_ms": round(med(wall) * 1e3, 3), "median_calls_per_s": round(1.0 / med(wall), 2),
+                    "median_commits_per_s": round(blocks / med(wall), 1),
+                    "median_kernel_ms": round(med(dev), 4), "median_kernel_us_per_commit": round(med(dev) * 1e3 / blocks, 3),
+                    "host_1thread_ms": round(med(host) * 1e3, 3), "host_us_per_commit": round(med(host) * 1e6 / blocks, 3),
+                    "verify_commits_ms": round(med(ver) * 1e3, 3), "verify_commits_last_kernel_ms": round(med(ver_dev), 4),
+                    "verify_commits_all_ok": bool((pb.codes() == 0).all())})
+    return {"config": "mt", "metric": "state.MedianTime per window, device vs host vs VerifyCommit", "runs": runs, "shapes": out}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="c1,c3,c4")
@@ -1039,6 +1103,8 @@ def main():
             r = c3(eng, args.headers, args.gap, args.c3_policy, args.runs, args.bisect_gap)
         elif cfg == "c3v" and rank == 0:
             r = c3v(eng, args.headers, args.gap, args.c3_policy, args.runs)
+        elif cfg == "mt" and rank == 0:
+            r = mt(eng, args.runs)
         elif cfg == "c4":
             r = c4(eng, args.blocks, args.validators, rank, world, coll, args.window, args.batch, args.corrupt_every,
                        args.pregen, not args.no_pinned, args.c4_policy, not args.no_stream)

@@ -695,6 +695,77 @@ int tmed_light_verify_with(const tmed_light_request *reqs, size_t n, uint32_t fl
                            const uint8_t *header_ok, const uint8_t *vals_hashes, tmed_light_result *out,
                            tmed_batch_verify_fn verify, void *user);
 
+/* ------------------------------------------------- block time: state.MedianTime */
+
+/*
+ * state.MedianTime(commit, validators) (state/state.go:268-285) over tmtime.WeightedMedian
+ * (types/time/time.go:35-58) for n (commit, validator set) pairs in one call: the value
+ * validateBlock compares block.Time with (state/validation.go:123-129) and State.MakeBlock stamps
+ * on a proposal (state/state.go:245-250).
+ *
+ * The rule, per pair:
+ *   - signature i enters iff flags[i] != 1 (only commitSig.Absent() is tested, state.go:273: Nil
+ *     votes and unknown flag values enter) and GetByAddress(address_i) finds a validator
+ *     (state.go:276-278; types/validator_set.go:270-278 compares with bytes.Equal, so an
+ *     address_lens[i] other than 20 matches nothing).  The first validator of the set with that
+ *     address gives the weight w_i = power.  An address that is not in the set is skipped, one that
+ *     occurs twice in the commit enters twice, and n_sigs is never compared with vals->n;
+ *   - total = the sum of the entering weights (state.go:279), median = total / 2 (time.go:36);
+ *   - the sort key is Time.UnixNano() = ts_seconds * 1e9 + ts_nanos (time.go:46);
+ *   - the result is the Time of the smallest entering key t with W(<= t) >= median, W(<= t) being
+ *     the sum of the entering weights with key <= t: what the reference's sort and walk
+ *     (time.go:38-56) return for non-negative weights, whatever the order inside a group of equal
+ *     keys.  With median == 0 that is the smallest entering key.
+ * Outcome codes:
+ *   TMED_MEDIAN_OK         seconds / nanos hold the median Time (Unix(), Nanosecond())
+ *   TMED_MEDIAN_ZERO_TIME  nothing entered: the reference returns time.Time{} (time.go:35 `res`);
+ *                          seconds / nanos hold its Unix() = -62135596800 and 0
+ *   TMED_MEDIAN_GO_PATH    the rule above does not determine the reference's value: an entering
+ *                          timestamp whose UnixNano is not an int64 or whose nanos lie outside
+ *                          [0, 10^9), a negative entering weight, or a total past int64.  The caller
+ *                          runs MedianTime itself; the other pairs are unaffected
+ * entered: the signatures that entered (0 with GO_PATH).  on_device: 1 when the pair's result comes
+ * from the kernels, 0 when the library computed it on the host.
+ *
+ * tmed_median_times stages each commit's flags, addresses and timestamps once and each distinct
+ * tmed_valset pointer's addresses and powers once (one copy in), runs one launch per kernel shape
+ * and copies the outcomes back (one copy out).  The kernels take a pair iff n_sigs == vals->n and
+ * every non-absent signature has a 20-byte address equal to the set's address at the same index,
+ * the pairing VerifyCommit requires (types/validator_set.go:667-714): they compare the two address
+ * arrays, then select without sorting, a search over the bits of the key with exact int64 weight
+ * sums (csrc/median.hip: one wavefront per commit up to 512 signatures, one workgroup per commit
+ * above).  Every other pair of the call, a pair of more than 2^24 signatures, and a pair whose set
+ * holds an address twice (the first match then need not be the validator at the same index) is
+ * computed by the host function below inside the same call; results are identical either way.
+ * Submitted blocksync windows are collected first, as by every seam call.  After the call
+ * tmed_last_kernel_ms reports the selection kernels' device time.  Of the commit the call reads
+ * flags, addresses, address_lens, ts_seconds, ts_nanos and n_sigs; of the set addresses, powers and n.
+ * TMED_EINVAL for malformed calls only: a NULL commit or vals, NULL flags, addresses, ts_seconds or
+ * ts_nanos with n_sigs > 0, NULL addresses or powers with vals->n > 0.
+ *
+ * tmed_median_times_host: the same computation with no device and no context (GetByAddress
+ * through a hash index of the set, a weighted quickselect over the entering pairs): csrc/median_host.h.
+ */
+#define TMED_MEDIAN_OK 0
+#define TMED_MEDIAN_ZERO_TIME 1
+#define TMED_MEDIAN_GO_PATH 2
+
+typedef struct {
+  const tmed_commit *commit; /* block.LastCommit */
+  const tmed_valset *vals;   /* state.LastValidators */
+} tmed_median_request;
+
+typedef struct {
+  int code;
+  int64_t seconds;  /* median.Unix() */
+  int32_t nanos;    /* median.Nanosecond() */
+  uint32_t entered;
+  uint8_t on_device;
+} tmed_median_result;
+
+int tmed_median_times(tmed_ctx *ctx, const tmed_median_request *reqs, size_t n, tmed_median_result *out);
+int tmed_median_times_host(const tmed_median_request *reqs, size_t n, tmed_median_result *out);
+
 /* ------------------------------------------------- blocksync replay (f4) */
 
 /*

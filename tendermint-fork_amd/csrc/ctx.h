@@ -127,6 +127,8 @@ int header_hashes_locked(tmed_ctx *c, const tmed_header *headers, size_t n, uint
 int valset_hashes_locked(tmed_ctx *c, const uint8_t *pubkeys, const int64_t *powers, const uint32_t *set_off,
                          size_t n_sets, uint8_t *out);
 int valsets_hashes_locked(tmed_ctx *c, const tmed_valset *const *sets, size_t n_sets, uint8_t *out);
+// median.hip: tmed_median_times over n checked requests (median_host.h check_request); ctx->mu held.
+int median_times_locked(tmed_ctx *c, const tmed_median_request *reqs, size_t n, tmed_median_result *out);
 struct Lane;
 void lane_release(Lane &L);    // keyset.hip: the second kernel lane's stream and scratch
 bool lanes_on();               // keyset.hip: TMED_LANES != 1
@@ -300,6 +302,10 @@ struct tmed_ctx {
   // the hashes.  Its own buffers, as h_csig / d_csig.
   tmed::HostBuf h_hdr;
   tmed::DevBuf d_hdr;
+  // tmed_median_times (median.hip): the pair table, the commits' and the sets' arrays packed per
+  // kind (pinned) and their device copy, plus the outcomes.  Its own buffers, as h_csig / d_csig.
+  tmed::HostBuf h_med;
+  tmed::DevBuf d_med;
   tmed::DevBuf d_korder;  // key-grouped order of a key-cached batch: counts / cursors + permutation
   tmed::DevBuf d_zip;     // ZIP-215 batch mode scratch (zip215.hip zip_bufs: points, digits, sort, buckets)
   bool zip_dense = false; // ZIP-215: the last large chunk had failures (zip215.hip: decide the next one singly first)

@@ -42,6 +42,7 @@
 #include "commitsig_leaf.h"
 #include "ctx.h"
 #include "header_leaf.h"
+#include "host_for.h"
 #include "merkle_levels.h"
 #include "merkle_path.h"
 #include "sha256.h"
@@ -613,37 +614,6 @@ void commit_pack(const tmed_commit &cm, uint8_t *h, const CsigLayout &lay, size_
     const uint32_t al = cm.address_lens ? cm.address_lens[j] : 20u;
     meta[j] = (uint32_t)cm.flags[j] | (al << 8) | (sl << 16);
   }
-}
-
-// f(i) for i in [0, n) on up to `threads` host threads (contiguous shares).
-template <class F>
-void host_for(size_t n, unsigned threads, F &&f) {
-  if (threads <= 1 || n < 2) {
-    for (size_t i = 0; i < n; i++) f(i);
-    return;
-  }
-  threads = (unsigned)std::min<size_t>(threads, n);
-  std::vector<std::thread> ts;
-  ts.reserve(threads);
-  auto share = [&](unsigned t) {
-    for (size_t i = n * t / threads; i < n * (t + 1) / threads; i++) f(i);
-  };
-  for (unsigned t = 1; t < threads; t++) {
-    try {
-      ts.emplace_back(share, t);
-    } catch (...) {  // no thread to be had: the caller runs that share
-      share(t);
-    }
-  }
-  share(0);
-  for (auto &t : ts) t.join();
-}
-
-unsigned pack_threads(size_t sigs) {
-  if (sigs < (1u << 16)) return 1;
-  const char *v = getenv("TMED_HOST_THREADS");  // as the seam's host pool: 16 by default
-  const unsigned want = v ? (unsigned)std::max(1, atoi(v)) : 16u;
-  return std::min(want, std::max(1u, std::thread::hardware_concurrency()));
 }
 
 // Header.Hash of the headers idx[0 .. m) (all header_fused_ok) into out + 32 * idx[j].  ctx->mu held.

@@ -13,12 +13,14 @@
 #include <algorithm>
 #include <map>
 #include <mutex>
+#include <new>
 #include <string>
 
 #include "../../include/tmed25519.h"
 #include "kernels.h"
 
 #include "ctx.h"
+#include "median_host.h"
 
 using namespace tmed;
 
@@ -227,10 +229,11 @@ void tmed_destroy(tmed_ctx *c) {
   for (DevBuf *b : {&c->d_a, &c->d_b, &c->d_msg, &c->d_off, &c->d_out, &c->d_c}) b->release();
   for (HostBuf *b : {&c->h_a, &c->h_b, &c->h_msg, &c->h_off, &c->h_out, &c->h_c}) b->release();
   for (DevBuf *b : {&c->d_merkle_lv, &c->d_merkle_tab, &c->d_proof_off, &c->d_proof_out, &c->d_proof_in, &c->d_korder,
-                    &c->d_zip, &c->d_kbases, &c->d_csig, &c->d_hdr})
+                    &c->d_zip, &c->d_kbases, &c->d_csig, &c->d_hdr, &c->d_med})
     b->release();
   c->h_csig.release();
   c->h_hdr.release();
+  c->h_med.release();
   c->h_kup.release();
   if (c->kup_ev) hipEventDestroy(c->kup_ev);
   c->h_zip.release();
@@ -267,6 +270,39 @@ void tmed_destroy(tmed_ctx *c) {
 }
 
 float tmed_last_kernel_ms(tmed_ctx *c) { return c ? c->last_ms : 0.f; }
+
+// ---- state.MedianTime (median_host.h: the rule on the host; median.hip: the kernels and their staging)
+
+int tmed_median_times_host(const tmed_median_request *reqs, size_t n, tmed_median_result *out) {
+  try {
+    return tmed_median::median_times_host(reqs, n, out);
+  } catch (const std::bad_alloc &) {
+    return TMED_ENOMEM;
+  } catch (...) {
+    return TMED_EINTERNAL;
+  }
+}
+
+int tmed_median_times(tmed_ctx *c, const tmed_median_request *reqs, size_t n, tmed_median_result *out) {
+  if (!c || (n && (!reqs || !out))) return TMED_EINVAL;
+  if (n == 0) return TMED_OK;
+  for (size_t i = 0; i < n; i++)
+    if (tmed_median::check_request(reqs[i]) != TMED_OK) return TMED_EINVAL;
+  try {
+    int rc;
+    {
+      std::lock_guard<std::mutex> lk(c->mu);
+      rc = bs_collect_submitted(c);  // the seam's rule: submitted blocksync windows first
+      if (rc == TMED_OK) rc = median_times_locked(c, reqs, n, out);
+    }
+    bs_release_collected(c);
+    return rc;
+  } catch (const std::bad_alloc &) {
+    return TMED_ENOMEM;
+  } catch (...) {
+    return TMED_EINTERNAL;
+  }
+}
 
 int tmed_set_kernel_timing(tmed_ctx *c, int on) {
   if (!c) return TMED_EINVAL;

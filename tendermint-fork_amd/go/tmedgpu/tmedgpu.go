@@ -1400,3 +1400,77 @@ func (e *Engine) LightVerify(reqs []LightRequest, flags uint32) ([]LightResult, 
 	}
 	return out, nil
 }
+
+// ---- state.MedianTime (state/state.go:268-285) ----------------------------------------------------
+
+// Outcome codes of MedianTimes (see tmed25519.h, which cites the reference lines of each rule).
+const (
+	MedianOK = C.TMED_MEDIAN_OK
+	// MedianZeroTime: no signature entered; the reference returns time.Time{}.
+	MedianZeroTime = C.TMED_MEDIAN_ZERO_TIME
+	// MedianGoPath: Go's int64 arithmetic would decide (a timestamp whose UnixNano is no int64, a
+	// negative power, a total past int64): the caller runs state.MedianTime itself.
+	MedianGoPath = C.TMED_MEDIAN_GO_PATH
+)
+
+// MedianRequest holds the arguments of one MedianTime call: block.LastCommit and
+// state.LastValidators, as the flat copies the commit verification of the same block uses.
+type MedianRequest struct {
+	Commit *CommitData
+	Vals   *ValSet
+}
+
+// MedianResult is one pair's outcome: with MedianOK the median is time.Unix(Seconds, Nanos).
+type MedianResult struct {
+	Code     int
+	Seconds  int64
+	Nanos    int32
+	Entered  uint32 // signatures that entered the median
+	OnDevice bool   // computed by the kernels (an aligned commit), not by the library's host route
+}
+
+// MedianTimes is state.MedianTime for many (commit, validator set) pairs in one call
+// (tmed_median_times): each distinct *CommitData and *ValSet is marshalled and staged once.  An
+// error means "take the original Go path".
+func (e *Engine) MedianTimes(reqs []MedianRequest) ([]MedianResult, error) {
+	n := len(reqs)
+	if n == 0 {
+		return nil, nil
+	}
+	a := e.getArena()
+	defer e.putArena(a)
+	creqs := (*[1 << 24]C.tmed_median_request)(a.alloc(uintptr(n) * unsafe.Sizeof(C.tmed_median_request{})))[:n:n]
+	cs := (*[1 << 24]C.tmed_commit)(a.alloc(uintptr(n) * unsafe.Sizeof(C.tmed_commit{})))[:n:n]
+	vs := (*[1 << 24]C.tmed_valset)(a.alloc(uintptr(n) * unsafe.Sizeof(C.tmed_valset{})))[:n:n]
+	seenV := make(map[*ValSet]*C.tmed_valset, n)
+	seenC := make(map[*CommitData]*C.tmed_commit, n)
+	for i := range reqs {
+		r := &reqs[i]
+		if r.Commit == nil || r.Vals == nil {
+			return nil, errors.New("tmedgpu: MedianTimes: nil commit or validator set")
+		}
+		cc, ok := seenC[r.Commit]
+		if !ok {
+			cs[i] = a.commitC(r.Commit, nil)
+			cc = &cs[i]
+			seenC[r.Commit] = cc
+		}
+		cv, ok := seenV[r.Vals]
+		if !ok {
+			vs[i] = a.valset(r.Vals)
+			cv = &vs[i]
+			seenV[r.Vals] = cv
+		}
+		creqs[i] = C.tmed_median_request{commit: cc, vals: cv}
+	}
+	res := make([]C.tmed_median_result, n)
+	if rc := C.tmed_median_times(e.ctx, &creqs[0], C.size_t(n), &res[0]); rc != 0 {
+		return nil, errors.New(C.GoString(C.tmed_strerror(rc)))
+	}
+	out := make([]MedianResult, n)
+	for i := range res {
+		out[i] = MedianResult{Code: int(res[i].code), Seconds: int64(res[i].seconds), Nanos: int32(res[i].nanos),
+			Entered: uint32(res[i].entered), OnDevice: res[i].on_device != 0}
+	}
+	return out, nil
+}
