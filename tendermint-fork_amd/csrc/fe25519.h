@@ -18,6 +18,13 @@
 //   mul/sq inputs may be sums/differences of up to THREE carried values
 //   (19 * 3 * (2^25 + 2^16) < 2^31 keeps the pre-multiplied operand in int32; the
 //   column sum stays below 2^61.3).
+//   fe_mul's FIRST operand f (and fe_mul_x2's f0, f1) may be a sum/difference of up to FOUR
+//   carried values while g stays within three: f is only ever doubled (2 * 4 * (2^25 + 2^16)
+//   < 2^31) and the worst column is below 2^61.7, inside check_bounds' 2^62.5.  The allowance is
+//   one-sided — a 4-sum g would leave int32 in its x19 copy — and quad.h's doubling relies on it
+//   (F = B - A - 2C is the f of quad_round2); tests/test_group_host.py and
+//   tests/test_gpu_group.py hold it in place (check_bounds with nsum 4 x 3, and the products at
+//   the limb extremes on both builds).
 //
 // All functions are __host__ __device__ so that the identical code can be
 // exercised on the CPU by the test-only host build (tests/, never the product).

@@ -7,14 +7,22 @@
 // reader) see the same edge inputs as the host build of tests/native/hostsim.cpp.  Never part of
 // the product: nothing in libtmed25519_hip.so links or loads this file.
 //
+// The group layer one step above them: devprim_ge runs each point formula of ge25519.h and the
+// group helpers of verify_core.h (ge_ops.h numbers them; hostsim_ge is the host twin) on raw
+// limbs, one case per lane; devprim_quad runs quad.h (the DPP quad-lane formulas of the latency
+// kernels and the ZIP-215 Horner chain, device-only code) one case per quad of lanes, single
+// operations and chains of doublings and additions.  Both call the product's functions only.
+//
 // Every entry point copies its input arrays to the device, launches one kernel (blocks of 64,
-// every lane guarded by i < n), synchronises, copies the results back and returns the HIP error
-// code (0 = hipSuccess).
+// every lane guarded by i < n; devprim_quad guards whole quads), synchronises, copies the results
+// back and returns the HIP error code (0 = hipSuccess).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "verify_core.h"
 #include "verify_hs.h"
+#include "quad.h"
+#include "ge_ops.h"
 
 using namespace tmed;
 
@@ -238,9 +246,129 @@ __global__ void decode_kernel(size_t n, const uint8_t *p, uint8_t *ok, uint8_t *
   ok[i] = good ? 1 : 0;
 }
 
+// One group-layer call (ge_ops.h) per lane: in [n][8][10], out [n][4][10], enc [n][4][32].
+template <int OP>
+__global__ void ge_kernel(int neg, size_t n, const int32_t *in, int32_t *out, uint8_t *enc) {
+  const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  fe fi[8], fo[4];
+#pragma unroll
+  for (int k = 0; k < 8; k++) load_fe(fi[k], in + 80 * i + 10 * k);
+  ge_op_run<OP>(neg != 0, fi, fo);
+#pragma unroll
+  for (int k = 0; k < 4; k++) store_fe(out + 40 * i + 10 * k, enc + 128 * i + 32 * k, fo[k]);
+}
+
+constexpr int kQuadOps = 7;
+constexpr int kChainSteps = 16;    // steps of a chain program
+constexpr uint32_t kChainMaxDbl = 16;  // doublings per step
+
+// quad.h, one case per quad: lane 4c + r holds field element r of case c.  in [n][2][4][10] (the
+// point v, the cached operand q), out [n][4][10].  op: 0 quad_dbl(v), 1 quad_add(v, q),
+// 2 quad_to_cached(v), 3 quad_identity, 4 quad_identity_cached, 5 comb_take(window, dg[c]),
+// 6 chain: from quad_identity, step s of prog[c][0..16) = ndbl | sel << 8 runs ndbl x quad_dbl,
+// then quad_add of v (sel 1), of q (sel 2) or nothing (sel 0); v and q are both cached operands.
+__global__ void quad_kernel(int op, size_t n, const int32_t *in, const int4 *window, const int32_t *dg,
+                            const uint32_t *prog, int32_t *out) {
+  const size_t c = ((size_t)blockIdx.x * kBlock + threadIdx.x) >> 2;
+  if (c >= n) return;  // the four lanes of a quad share c: a quad is wholly active or wholly idle
+  const QuadK K((int)threadIdx.x);
+  fe v, q, o;
+  load_fe(v, in + 80 * c + 10 * K.r);
+  load_fe(q, in + 80 * c + 40 + 10 * K.r);
+  fe_0(o);
+  switch (op) {
+    case 0: quad_dbl(v, K); o = v; break;
+    case 1: quad_add(v, q, K); o = v; break;
+    case 2: quad_to_cached(o, v, K); break;
+    case 3: quad_identity(o, K.r); break;
+    case 4: quad_identity_cached(o, K.r); break;
+    case 5: comb_take(o, window, dg[c], K); break;
+    default: {
+      quad_identity(o, K.r);
+#pragma unroll 1
+      for (int s = 0; s < kChainSteps; s++) {
+        const uint32_t st = prog[kChainSteps * c + s];
+        const uint32_t nd = st & 0xffu, sel = st >> 8;
+#pragma unroll 1
+        for (uint32_t k = 0; k < nd; k++) quad_dbl(o, K);
+        if (sel == 1) quad_add(o, v, K);
+        else if (sel == 2) quad_add(o, q, K);
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 10; i++) out[40 * c + 10 * K.r + i] = o.v[i];
+}
+
 }  // namespace
 
 extern "C" {
+
+// The group-layer functions (ge_ops.h: op 0..9; neg 0 / 1 where the function takes it), one case
+// per lane: in n x 8 x 10 raw limbs, out n x 4 x 10 raw output limbs, enc n x 4 x 32 their
+// canonical encodings.
+int devprim_ge(int op, int neg, size_t n, const int32_t *in, int32_t *out, uint8_t *enc) {
+  if (n == 0) return 0;
+  if (op < 0 || op >= kGeOps || neg < 0 || neg > 1) return (int)hipErrorInvalidValue;
+  DevBuf din, dout, denc;
+  DP_TRY(din.put(in, 320 * n));
+  DP_TRY(dout.alloc(160 * n));
+  DP_TRY(denc.alloc(128 * n));
+  const unsigned g = grid_of(n);
+  int32_t *o = dout.as<int32_t>();
+  uint8_t *e = denc.as<uint8_t>();
+  const int32_t *i = din.as<int32_t>();
+  switch (op) {
+    case 0: ge_kernel<0><<<g, kBlock>>>(neg, n, i, o, e); break;
+    case 1: ge_kernel<1><<<g, kBlock>>>(neg, n, i, o, e); break;
+    case 2: ge_kernel<2><<<g, kBlock>>>(neg, n, i, o, e); break;
+    case 3: ge_kernel<3><<<g, kBlock>>>(neg, n, i, o, e); break;
+    case 4: ge_kernel<4><<<g, kBlock>>>(neg, n, i, o, e); break;
+    case 5: ge_kernel<5><<<g, kBlock>>>(neg, n, i, o, e); break;
+    case 6: ge_kernel<6><<<g, kBlock>>>(neg, n, i, o, e); break;
+    case 7: ge_kernel<7><<<g, kBlock>>>(neg, n, i, o, e); break;
+    case 8: ge_kernel<8><<<g, kBlock>>>(neg, n, i, o, e); break;
+    default: ge_kernel<9><<<g, kBlock>>>(neg, n, i, o, e); break;
+  }
+  DP_TRY(finish_launch());
+  DP_TRY(dout.get(out, 160 * n));
+  DP_TRY(denc.get(enc, 128 * n));
+  return 0;
+}
+
+// quad.h, one case per quad of lanes (see quad_kernel): in n x 2 x 4 x 10, out n x 4 x 10.
+// window: nrows synthetic 128-byte comb rows (32 int32 each: YpX, YmX, XY2d, two unused) and
+// dg[n] the per-case digit, |dg| < nrows, read by op 5 only; prog n x 16 chain steps, read by
+// op 6 only (at most 16 doublings a step, sel 0..2).  Unused arrays may be null.
+int devprim_quad(int op, size_t n, const int32_t *in, const int32_t *window, size_t nrows, const int32_t *dg,
+                 const uint32_t *prog, int32_t *out) {
+  if (n == 0) return 0;
+  if (op < 0 || op >= kQuadOps) return (int)hipErrorInvalidValue;
+  if (op == 5) {
+    if (!window || !dg || nrows == 0) return (int)hipErrorInvalidValue;
+    for (size_t c = 0; c < n; c++) {
+      const int64_t d = dg[c];
+      if ((d < 0 ? -d : d) >= (int64_t)nrows) return (int)hipErrorInvalidValue;
+    }
+  }
+  if (op == 6) {
+    if (!prog) return (int)hipErrorInvalidValue;
+    for (size_t k = 0; k < (size_t)kChainSteps * n; k++)
+      if ((prog[k] & 0xffu) > kChainMaxDbl || (prog[k] >> 8) > 2) return (int)hipErrorInvalidValue;
+  }
+  DevBuf din, dwin, ddg, dprog, dout;
+  DP_TRY(din.put(in, 320 * n));
+  DP_TRY(dwin.put(window, op == 5 ? 128 * nrows : 0));
+  DP_TRY(ddg.put(dg, op == 5 ? 4 * n : 0));
+  DP_TRY(dprog.put(prog, op == 6 ? 4 * (size_t)kChainSteps * n : 0));
+  DP_TRY(dout.alloc(160 * n));
+  quad_kernel<<<grid_of(4 * n), kBlock>>>(op, n, din.as<int32_t>(), dwin.as<int4>(), ddg.as<int32_t>(),
+                                          dprog.as<uint32_t>(), dout.as<int32_t>());
+  DP_TRY(finish_launch());
+  DP_TRY(dout.get(out, 160 * n));
+  return 0;
+}
 
 // Raw signed limbs (10 per operand, n cases): result limbs and canonical encodings out.  The
 // single-operand ops (op < 4) read a0 / b0 and write out0 / enc0 only; the second set's arrays

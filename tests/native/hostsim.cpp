@@ -11,6 +11,7 @@
 #include "verify_core.h"
 #include "verify_hs.h"
 #include "sha256.h"
+#include "ge_ops.h"
 
 using namespace tmed;
 
@@ -483,6 +484,35 @@ void hostsim_pack256(const int32_t *limbs, const uint8_t *g, int32_t *out_limbs,
   fe_mul(o, u, gf);
   fe_to_words(wo, o);
   to_bytes(prod, wo);
+}
+
+// One group-layer call (ge_ops.h: op 0..9, neg where the function takes it) on raw limbs: in is
+// [8][10], out_limbs [4][10] raw output limbs, out [4][32] their canonical encodings.  Returns 0,
+// or -1 for an unknown op.  The host twin of devprim_ge.
+int hostsim_ge(int op, int neg, const int32_t *in, int32_t *out_limbs, uint8_t *out) {
+  fe fi[8], fo[4];
+  for (int k = 0; k < 8; k++)
+    for (int i = 0; i < 10; i++) fi[k].v[i] = in[10 * k + i];
+  switch (op) {
+    case 0: ge_op_run<0>(neg != 0, fi, fo); break;
+    case 1: ge_op_run<1>(neg != 0, fi, fo); break;
+    case 2: ge_op_run<2>(neg != 0, fi, fo); break;
+    case 3: ge_op_run<3>(neg != 0, fi, fo); break;
+    case 4: ge_op_run<4>(neg != 0, fi, fo); break;
+    case 5: ge_op_run<5>(neg != 0, fi, fo); break;
+    case 6: ge_op_run<6>(neg != 0, fi, fo); break;
+    case 7: ge_op_run<7>(neg != 0, fi, fo); break;
+    case 8: ge_op_run<8>(neg != 0, fi, fo); break;
+    case 9: ge_op_run<9>(neg != 0, fi, fo); break;
+    default: return -1;
+  }
+  for (int k = 0; k < 4; k++) {
+    for (int i = 0; i < 10; i++) out_limbs[10 * k + i] = fo[k].v[i];
+    uint32_t wo[8];
+    fe_to_words(wo, fo[k]);
+    to_bytes(out + 32 * k, wo);
+  }
+  return 0;
 }
 
 int hostsim_decode(const uint8_t *p, uint8_t *out_enc) {

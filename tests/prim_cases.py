@@ -28,6 +28,8 @@ def limb_val(c):
 # and [-2^24, 2^24] from fe_carry, limb 1 [-2^16, 2^25 + 2^16) widened by fe_carry's range.
 CARRIED_LO = tuple(-(2**24) - 2**16 if i == 1 else (-(2**25) if i % 2 == 0 else -(2**24)) for i in range(10))
 CARRIED_HI = tuple(2**25 + 2**16 if i == 1 else 2**25 - 1 for i in range(10))
+# the larger end, either sign: what one term of a sum or DIFFERENCE of carried values can reach
+CARRIED_MAG = tuple(max(-lo, hi) for lo, hi in zip(CARRIED_LO, CARRIED_HI))
 
 # fe_raw operation numbers (hostsim_fe_raw, devprim_fe_raw)
 FE_MUL, FE_SQ, FE_SQ2, FE_SQC, FE_MUL_X2, FE_SQ_X2, FE_SQC_X2, FE_SQ2_SQ = range(8)
@@ -43,20 +45,33 @@ def in_carried_output_range(i, v):
     return CARRIED_LO[i] <= v <= CARRIED_HI[i] or (i % 2 == 1 and 0 <= v < 2**25)
 
 
+def draw_carried(rng):
+    """One carried value; 30 % of the draws sit at the ends of every limb's range."""
+    lo, hi = CARRIED_LO, CARRIED_HI
+    r = rng.random()
+    if r < 0.3:
+        return tuple(lo[i] if rng.random() < 0.5 else hi[i] for i in range(10))
+    return tuple(rng.randint(lo[i], hi[i]) for i in range(10))
+
+
+def draw_nsum(rng, n, signed=False):
+    """A sum of n carried values, limb by limb; signed: each summand added or subtracted."""
+    cs = [draw_carried(rng) for _ in range(n)]
+    if signed:
+        cs = [c if rng.random() < 0.5 else tuple(-v for v in c) for c in cs]
+    return tuple(sum(c[i] for c in cs) for i in range(10))
+
+
 @functools.lru_cache(maxsize=None)
 def _fused():
     lo, hi = CARRIED_LO, CARRIED_HI
     rng = random.Random(23)
 
     def carried():
-        r = rng.random()
-        if r < 0.3:
-            return tuple(lo[i] if rng.random() < 0.5 else hi[i] for i in range(10))
-        return tuple(rng.randint(lo[i], hi[i]) for i in range(10))
+        return draw_carried(rng)
 
     def nsum(n):
-        cs = [carried() for _ in range(n)]
-        return tuple(sum(c[i] for c in cs) for i in range(10))
+        return draw_nsum(rng, n)
 
     hi3, lo3 = tuple(3 * v for v in hi), tuple(3 * v for v in lo)
     pairs = [(hi3, hi3), (lo3, lo3), (hi3, lo3)]
@@ -77,6 +92,23 @@ def fused_carried():
     original fe_sq2 loop and the 1-sums among fused_pairs()."""
     pairs, singles = _fused()
     return (CARRIED_LO, CARRIED_HI) + singles + tuple(a for a, _ in pairs if is_carried(a))
+
+
+@functools.lru_cache(maxsize=None)
+def fused_4sum_pairs():
+    """316 (f, g) pairs for fe_mul with a 4-sum as its FIRST operand (fe25519.h: f takes x2 copies
+    only, so it may be a sum of four carried values; quad.h's doubling passes F = B - A - 2C so):
+    the all-extreme pairs (4 hi, 3 hi), (4 lo, 3 lo), both crossed, and the same four against a
+    2-sum; F is a DIFFERENCE, so also -+4 x the larger end against -+3 x and -+2 x it; then 200
+    (4-sum, 3-sum) and 100 (4-sum, 2-sum) draws of draw_nsum, every other one with signed summands."""
+    lo, hi, mag = CARRIED_LO, CARRIED_HI, CARRIED_MAG
+    rng = random.Random(47)
+    mul = lambda k, c: tuple(k * v for v in c)
+    pairs = [(mul(4, a), mul(k, b)) for k in (3, 2) for a, b in ((hi, hi), (lo, lo), (hi, lo), (lo, hi))]
+    pairs += [(mul(4 * sa, mag), mul(k * sb, mag)) for k in (3, 2) for sa in (1, -1) for sb in (1, -1)]
+    pairs += [(draw_nsum(rng, 4, j % 2 == 1), draw_nsum(rng, 3, j % 2 == 1)) for j in range(200)]
+    pairs += [(draw_nsum(rng, 4, j % 2 == 1), draw_nsum(rng, 2, j % 2 == 1)) for j in range(100)]
+    return tuple(pairs)
 
 
 @functools.lru_cache(maxsize=None)
