@@ -262,6 +262,17 @@ void tmed_test_pool_jitter(int max_us);
 void tmed_test_stream_delay(int us);
 
 /*
+ * Tests only (tests/test_gpu_joint_table.py): the per-lane joint radix-4 table of the half-size
+ * main kernel, built on the device for n <= 65536 triples.  a, r: n x 32-byte point encodings
+ * (decoded like a public key; the identity when one does not decode), dneg: n bytes, the sign of d
+ * (the table is of -A and, for dneg = 0, -R, else +R).  rows: n x 12 x 128 bytes out, row
+ * |5i + j| - 1 of a triple the entry i (-A) + j (-+R) as four packed 32-byte field elements
+ * (Y+X, Y-X, Z, 2dT).
+ */
+int tmed_test_joint_rows(tmed_ctx *ctx, const uint8_t *a, const uint8_t *r, const uint8_t *dneg, size_t n,
+                         uint8_t *rows);
+
+/*
  * With TMED_DEBUG_ZERO set at the first pipelined generic batch: every staged candidate whose
  * device bit is 0 is recorded (request, signature, staging position, the staged and the device
  * copies of its key and signature, the assembled sign-bytes).  Copies up to cap records into out

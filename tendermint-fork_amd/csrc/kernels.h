@@ -27,9 +27,13 @@ constexpr uint32_t kThreadsPerBlock = 256;
 // Variable-base table slab: lane slots (grid-stride loop bounds the grid to
 // slab_slots / kThreadsPerBlock blocks).
 constexpr uint32_t kSlabSlotBytes = 8 * 128;  // cached j*P, j = 1..8, in fe_pack256 form (j = 0: one shared row)
-// The half-size path (main variant 6, the default) keeps two per-lane tables (-A and
-// -sign(d) R): its slab has two slot regions; the full-length fallback (variant 5) one.
-inline uint32_t slab_tables(int main_waves) { return main_waves == 5 ? 1u : 2u; }
+// The half-size path (main variant 6, the default, and the ZIP-215 rule on every context) keeps
+// one joint table of -A and -sign(d) R per lane (verify_core.h build_table_joint: twelve rows),
+// the full-length fallback (variant 5) its eight rows of -A, in the same region [slot][row][128 B].
+constexpr uint32_t kSlabJointSlotBytes = 12 * 128;
+// Bytes of a context's slab: sized for the joint table whatever the variant, since a ZIP-215 batch
+// runs the half-size kernels on a variant-5 context too (1.5 GB at the default 2^20 slots).
+inline size_t slab_bytes(uint32_t slots) { return (size_t)slots * kSlabJointSlotBytes; }
 
 // Batched finish (verify_core.h finish_group): the main kernels hand projective R' over in
 // fin ([q][slot], kFinInt4 int4 per signature, kFinCap slots); the finish kernel runs once per
@@ -168,6 +172,10 @@ hipError_t launch_key_order(const uint32_t *val_idx, uint32_t n, uint32_t nkeys,
 // the work queued after it, so a consumer on another stream that does not wait for that work
 // reads it unfinished.  us = 0: nothing is launched.
 hipError_t launch_test_delay(hipStream_t stream, uint32_t us);
+// Tests (tmed_test_joint_rows): the joint tables of n (A, R, sign of d) triples, one lane each, into
+// rows ([i][12][128 B], n * kSlabJointSlotBytes bytes).
+hipError_t launch_test_joint_rows(const uint8_t *a, const uint8_t *r, const uint8_t *dneg, uint32_t n, int4 *rows,
+                                  hipStream_t stream);
 hipError_t launch_window_stats(const int4 *prep, uint32_t stride, uint32_t count, uint32_t *d_hist,
                                hipStream_t stream);
 

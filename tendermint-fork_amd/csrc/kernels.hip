@@ -13,7 +13,8 @@
 // Memory layout
 //   pub   n x 32 B, sig n x 64 B (16-B aligned rows -> dwordx4 loads)
 //   msgs  concatenated bytes, off[n+1] u32 (or fixed 256-B vote slots)
-//   slab  per-lane variable-base tables: 8 cached points x 128 B (fe_pack256), lane-major [slot][entry][chunk]
+//   slab  per-lane variable-base tables: 12 (joint table of -A and R) or 8 cached points x 128 B (fe_pack256),
+//         lane-major [slot][entry][chunk]
 //   b16   32769 niels multiples of B in 128-B rows in HBM (4.2 MB; the full-length fallback, variant 5)
 //   combs key-set combs [key][window][entry] and the shared combs of B (radix 256, radix 2^16)
 #include "kernels.h"
@@ -25,12 +26,12 @@
 
 namespace tmed {
 
-// Per-lane table in the HBM slab, lane-major [slot][entry 1..8][chunk]: each lane's entry is one
+// Per-lane table in the HBM slab, lane-major [slot][entry 1..ROWS][chunk]: each lane's entry is one
 // aligned 128-B line (the four coordinates in fe_pack256 form), so a divergent lookup reads
 // exactly one line.  The slab does not fit L2/MALL at full occupancy; the 160-B int32 form
 // read 2.25 lines per lookup, and its traffic cost ~10 % of the clock (profiles/r02/s4).
 // Entry 0 (the identity, cached form (1, 1, 1, 0)) is not stored per lane: every lane reads this
-// one row (an L2 hit), so the slab holds entries 1..8.
+// one row (an L2 hit), so the slab holds entries 1..ROWS.
 // (a plain __device__ variable: global address space like the slab, so the row select below stays a
 // global pointer and the table loads are global_load — a select against a constant-address-space
 // row made them flat_load, which also count in lgkmcnt: every s_waitcnt lgkmcnt(0) of the B-row
@@ -44,17 +45,19 @@ __device__ int4 kIdentityRow[8] = {{1, 0, 0, 0}, {0, 0, 0, 0}, {1, 0, 0, 0}, {0,
 __device__ __forceinline__ void slab_st(int4 *p, int4 v) { *p = v; }
 __device__ __forceinline__ int4 slab_ld(const int4 *p) { return *p; }
 
-struct SlabTab {
+// ROWS: 8 (j * (-A), the full-length fallback) or kJointRows (the joint table of the half-size path).
+template <int ROWS>
+struct SlabTabN {
   int4 *base;
   uint32_t slot;
 
   __device__ __forceinline__ const int4 *row(int j) const {
-    return j == 0 ? kIdentityRow : base + ((size_t)slot * 8 + (j - 1)) * 8;
+    return j == 0 ? kIdentityRow : base + ((size_t)slot * ROWS + (j - 1)) * 8;
   }
 
   __device__ __forceinline__ void store(int j, const ge_cached &c) const {
     if (j == 0) return;
-    int4 *r = base + ((size_t)slot * 8 + (j - 1)) * 8;
+    int4 *r = base + ((size_t)slot * ROWS + (j - 1)) * 8;
     const fe *fs[4] = {&c.YpX, &c.YmX, &c.Z, &c.T2d};
 #pragma unroll
     for (int f = 0; f < 4; f++) {
@@ -66,8 +69,7 @@ struct SlabTab {
   }
   // prefetch issues the row's eight 16-B loads into registers (swap: Y+X and Y-X exchanged by
   // the load addresses — a negative digit's entry, ge_add_cached_pre); take unpacks them.
-  // hs_straus (verify_hs.h) prefetches the -A row before the last doubling and the R row before
-  // the -A addition, not right before use.
+  // hs_straus_joint (verify_hs.h) prefetches every row two doublings before its take.
   int4 pv[8];
   __device__ __forceinline__ void prefetch(int j, bool swap = false) {
     const int4 *r = row(j);
@@ -86,6 +88,9 @@ struct SlabTab {
     }
   }
 };
+using SlabTab = SlabTabN<8>;
+using SlabTabJ = SlabTabN<kJointRows>;
+static_assert(kSlabSlotBytes == 8 * 128 && kSlabJointSlotBytes == kJointRows * 128, "slab rows are 128 B");
 
 typedef __attribute__((address_space(1))) void global_void;
 typedef __attribute__((address_space(3))) void lds_void;
@@ -315,8 +320,8 @@ struct HsDigitsDev {
   __device__ __forceinline__ uint32_t dword(int w) const { return w < 5 ? word(8 + w) : 0x88888888u; }
 };
 
-// Phase 2: tables of -A and -sign(d) R in the slab (two lane-major regions), the 3-point
-// Straus sum over the wave's largest window count, B digits from windows 0 and 8 of the
+// Phase 2: the joint radix-4 table of -A and -sign(d) R in the slab (twelve rows per lane), the
+// 3-point Straus sum over the wave's largest window count, B digits from windows 0 and 8 of the
 // radix-2^16 comb (each entry fetched into LDS 16 doublings ahead), identity test.  Every
 // lane of the grid stays to the end (the wave maximum of W is a shuffle reduction); lanes
 // past count run on the identity and store nothing.
@@ -368,13 +373,12 @@ __global__ __launch_bounds__(kHsBlock, kHsWaves) void verify_main_hs_kernel(
   if (W > 64) W = 64;
   const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
   const HsDigitsDev ds{prep2, stride, slot, active};
-  SlabTab ta{slab, slot};
-  SlabTab tr{slab + (size_t)stride * 64, slot};
+  SlabTabJ tj{slab, slot};
   // the high table: the second radix-2^26 table, or window 8 (j * 2^128 B) of the 2^16 comb
   const size_t hi = BB == 26 ? (size_t)kB26Entries * kCombEntryInt4 : (size_t)8 * kB16Entries * kCombEntryInt4;
   BPf<BB> bl{btab, sbl[wv], lane};
   BPf<BB> bh{btab + hi, sbh[wv], lane};
-  const bool id = verify_main_hs(ds, (flags & 2) != 0, er, W, A, Rx, Ry, ta, tr, bl, bh, zip215 != 0);
+  const bool id = verify_main_hsj(ds, (flags & 2) != 0, er, W, A, Rx, Ry, tj, bl, bh, zip215 != 0);
   if (active) out[base + (uint32_t)w[42]] = ((flags & 1) && id) ? 1 : 0;
 }
 
@@ -405,6 +409,34 @@ __global__ __launch_bounds__(kThreadsPerBlock) void window_stats_kernel(const in
     if (lh[b]) atomicAdd(&lane_hist[b], lh[b]);
     if (wh[b]) atomicAdd(&wave_hist[b], wh[b]);
   }
+}
+
+// Tests (tmed_test_joint_rows): lane i builds the joint table of the points encoded in a[i] and
+// r[i] (Point.SetBytes; the identity when one does not decode) with dneg[i] as d's sign, as
+// verify_main_hs_kernel does, into rows ([i][kJointRows][128 B]).
+__global__ __launch_bounds__(kHsBlock) void test_joint_rows_kernel(const uint8_t *__restrict__ a,
+                                                                   const uint8_t *__restrict__ r,
+                                                                   const uint8_t *__restrict__ dneg, uint32_t n,
+                                                                   int4 *__restrict__ rows) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t aw[8], rw[8];
+  load_row_words(aw, a + 32 * (size_t)i, 2);
+  load_row_words(rw, r + 32 * (size_t)i, 2);
+  ge_p3 A, R, P, Q;
+  ge_frombytes_go(A, aw);
+  ge_frombytes_go(R, rw);
+  hs_points(P, Q, dneg[i] != 0, A, R.X, R.Y);
+  SlabTabJ tj{rows, i};
+  build_table_joint(tj, P, Q);
+}
+
+hipError_t launch_test_joint_rows(const uint8_t *a, const uint8_t *r, const uint8_t *dneg, uint32_t n, int4 *rows,
+                                  hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(test_joint_rows_kernel, dim3((n + kHsBlock - 1) / kHsBlock), dim3(kHsBlock), 0, stream, a, r,
+                     dneg, n, rows);
+  return hipGetLastError();
 }
 
 // (s_sleep 127 is ~8k clocks, ~3.4 us at 2.4 GHz; a bounded loop, no memory access)

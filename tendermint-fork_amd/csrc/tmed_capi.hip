@@ -146,7 +146,7 @@ int tmed_init(int device, tmed_ctx **out) {
   if (e == hipSuccess) e = hipEventCreate(&c->ev1);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&c->scratch_ev, hipEventDisableTiming);
   // Lane slots for the per-lane tables and the prep hand-off: 2^20 signatures per
-  // prep/main pair (default path: 3.0 GB slab of two tables + 369 MB hand-off, of the 288 GB
+  // prep/main pair (1.5 GB slab of one joint table per lane + 369 MB hand-off, of the 288 GB
   // HBM), so a BASELINE C2 batch is one launch of each kernel: +2.6 % over 131,072-signature
   // chunks, which paid a drain/ramp bubble per launch (profiles/r01/session2/variants_chunk.txt).
   // Both sizes are kept multiples of the block size (every lane of a launched block owns a slot
@@ -167,7 +167,7 @@ int tmed_init(int device, tmed_ctx **out) {
   if (const char *v = getenv("TMED_GLAT_MAX")) c->glat_max = (uint32_t)strtoul(v, nullptr, 10);
   if (c->glat_max > kGLatMax) c->glat_max = kGLatMax;
   if (e == hipSuccess)
-    e = hipMalloc((void **)&c->d_slab, (size_t)c->slab_slots * kSlabSlotBytes * slab_tables(c->main_waves));
+    e = hipMalloc((void **)&c->d_slab, slab_bytes(c->slab_slots));
   if (e == hipSuccess) e = hipMalloc((void **)&c->d_prep, (size_t)c->slab_slots * kPrepSlotBytes + kPrepTailBytes);
   if (e == hipSuccess) e = hipMalloc((void **)&c->d_fin, kFinBytes);          // 128 MB: projective R'
   if (e == hipSuccess) e = hipMalloc((void **)&c->d_fin_pre, kFinPreBytes);   // 48 MB: prefix products
@@ -439,6 +439,28 @@ int tmed_window_stats(tmed_ctx *c, uint32_t lane_hist[65], uint32_t wave_hist[65
   if (e != hipSuccess) return map_err(e);
   for (int w = 0; w < 65; w++) { lane_hist[w] = h[w]; wave_hist[w] = h[65 + w]; }
   return TMED_OK;
+}
+
+int tmed_test_joint_rows(tmed_ctx *c, const uint8_t *a, const uint8_t *r, const uint8_t *dneg, size_t n,
+                         uint8_t *rows) {
+  if (!c || !a || !r || !dneg || !rows || n == 0 || n > 65536) return TMED_EINVAL;
+  std::lock_guard<std::mutex> lk(c->mu);
+  (void)hipSetDevice(c->device);
+  uint8_t *d_in = nullptr;  // a (32 n), r (32 n), dneg (n)
+  int4 *d_rows = nullptr;
+  const size_t row_bytes = n * kSlabJointSlotBytes;
+  hipError_t e = hipMalloc((void **)&d_in, 65 * n);
+  if (e == hipSuccess) e = hipMalloc((void **)&d_rows, row_bytes);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_in, a, 32 * n, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_in + 32 * n, r, 32 * n, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_in + 64 * n, dneg, n, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = launch_test_joint_rows(d_in, d_in + 32 * n, d_in + 64 * n, (uint32_t)n, d_rows, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(rows, d_rows, row_bytes, hipMemcpyDeviceToHost, c->stream);
+  const hipError_t es = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess) e = es;
+  if (d_in) (void)hipFree(d_in);
+  if (d_rows) (void)hipFree(d_rows);
+  return e == hipSuccess ? TMED_OK : map_err(e);
 }
 
 int tmed_sign_batch_device(tmed_ctx *c, const uint8_t *d_seeds, const uint8_t *d_msgs, const uint32_t *d_off,

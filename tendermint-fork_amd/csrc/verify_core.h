@@ -101,6 +101,155 @@ TMED_HD void build_table_affine(T &tab, const ge_p3 &P) {
   }
 }
 
+// ---- joint radix-4 table of two affine points (the half-size throughput path, verify_hs.h) ----
+// Rows i*P + j*Q, (i, j) in [-2, 2]^2 up to sign: row |5i + j| holds the entry of the pair whose
+// 5i + j is positive (i > 0, or i = 0 and j > 0); the pair (-i, -j) is that row negated.  Twelve
+// rows, 1..12 = (0,1) (0,2) (1,-2) (1,-1) (1,0) (1,1) (1,2) (2,-2) (2,-1) (2,0) (2,1) (2,2);
+// row 0 is the identity.
+constexpr int kJointRows = 12;
+TMED_HD int joint_index(int i, int j) { return 5 * i + j; }
+
+// r = 2 (x, y) for an affine point (Z = 1) from its sums alone, s = y + x and d = y - x, so the
+// coordinates need not stay live: with S = s^2, D = d^2, M = s d = y^2 - x^2 the doubling
+// (2xy : y^2 + x^2 : y^2 - x^2 : 2 - (y^2 - x^2)) completed, every coordinate doubled, is
+// (S - D : S + D : 2M : 4 - 2M).  Two squarings and one product.
+TMED_HD void ge_affine_dbl(ge_p1p1 &r, const fe &s, const fe &d) {
+  fe S, D, M, four;
+  fe_sq_x2(S, s, D, d);
+  fe_mul(M, s, d);
+  fe_0(four);
+  four.v[0] = 4;
+  fe_sub(r.X, S, D);
+  fe_add(r.Y, S, D);
+  fe_add(r.Z, M, M);
+  fe_sub(r.T, four, r.Z);
+}
+
+// s = p + q and m = p - q (FLIP: m = q - p) for q affine niels, five products for the pair: the
+// sum's a = (Y+X)(y+x), b = (Y-X)(y-x) and the difference's a' = (Y+X)(y-x), b' = (Y-X)(y+x)
+// share their operands, and c = 2d T xy only changes sign.  p is given by t = Y + X, t2 = Y - X,
+// T and Z (null: Z = 1, so d = 2 without a doubling).  -(X : Y : Z : T) completed is
+// (-X : Y : Z : T): FLIP exchanges a' and b' in X.
+template <bool FLIP>
+TMED_HD void ge_madd_niels_pm(ge_p1p1 &s, ge_p1p1 &m, const fe &t, const fe &t2, const fe &pT, const fe *pZ,
+                              const ge_niels &q) {
+  fe a, b, ap, bp, c, d;
+  fe_mul_x2(a, t, q.YpX, bp, t2, q.YpX);
+  fe_mul_x2(ap, t, q.YmX, b, t2, q.YmX);
+  fe_mul(c, q.XY2d, pT);
+  if (pZ) {
+    fe_add(d, *pZ, *pZ);
+  } else {
+    fe_0(d);
+    d.v[0] = 2;
+  }
+  fe_sub(s.X, a, b);
+  fe_add(s.Y, a, b);
+  fe_add(s.Z, d, c);
+  fe_sub(s.T, d, c);
+  if (FLIP) fe_sub(m.X, bp, ap); else fe_sub(m.X, ap, bp);
+  fe_add(m.Y, ap, bp);
+  fe_sub(m.Z, d, c);
+  fe_add(m.T, d, c);
+}
+template <bool FLIP>
+TMED_HD void ge_madd_niels_pm(ge_p1p1 &s, ge_p1p1 &m, const ge_p3 &p, const ge_niels &q) {
+  fe t, t2;
+  fe_add(t, p.Y, p.X);
+  fe_sub(t2, p.Y, p.X);
+  ge_madd_niels_pm<FLIP>(s, m, t, t2, p.T, &p.Z, q);
+}
+
+// completed -> extended (left in p) -> cached -> row
+template <class T>
+TMED_HD void joint_store(T &tab, int row, ge_p3 &p, const ge_p1p1 &t) {
+  ge_cached c;
+  ge_p1p1_to_p3(p, t);
+  ge_p3_to_cached(c, p);
+  tab.store(row, c);
+}
+
+// The joint table of P and Q, both AFFINE (Z = 1, T = xy; a coordinate may be a negated carried
+// value: -A, -R).  T: store(row, const ge_cached&), prefetch(row, false) / take(ge_cached&) for
+// rows 0..kJointRows.
+// Field products: 71 M + 12 S, the two T = xy of the caller included —
+//   P, Q as cached                      2 x (xy, 2d xy)                                   4 M
+//   P +- Q, P +- 2Q, 2P +- Q            3 x (5 M for the pair, 2 x (->p3 4 M, 2dT 1 M))  45 M
+//   2P +- 2Q = 2 (P +- Q)               2 x (4 S, ->p3 4 M, 2dT 1 M)                     10 M + 8 S
+//   2Q, 2P                              2 x (2 S + 1 M, ->p3 4 M, 2dT 1 M)               12 M + 4 S
+// against 2 x 57 M + the two xy for the two 8-row tables of build_table_affine.
+// Nothing of P and Q stays in registers between the steps: the main kernel has none to spare
+// (with the two niels forms live through the steps it spilled 50 VGPRs), so the later steps read
+// the rows of P and Q back from the table they were just stored to — a lane's own 128-B lines,
+// fetched a step ahead — and the affine doublings work from y + x and y - x (ge_affine_dbl)
+// rather than from x^2, y^2, (x + y)^2, which would keep the coordinates themselves.
+// Operands stay inside fe25519.h's bounds as in build_table_affine: rows are packed from 2-sums
+// (Y + X of product outputs or of decoded coordinates), unpacked rows are within a 2-sum, and
+// products take those and the completed coordinates (3-sums).  Complete formulas throughout, so
+// P = +-Q, small-order points and the identity come out exact.
+template <class T>
+TMED_HD void build_table_joint(T &tab, const ge_p3 &P, const ge_p3 &Q) {
+  ge_cached c;
+  ge_p1p1 s, m;
+  ge_p3 u;
+  ge_p2 v;
+  ge_niels n;
+  ge_cached_0(c);
+  tab.store(0, c);
+  {
+    fe d2, t, t2;
+    fe_const_d2(d2);
+    fe_add(t, P.Y, P.X);
+    fe_sub(t2, P.Y, P.X);
+    fe_add(n.YpX, Q.Y, Q.X);
+    fe_sub(n.YmX, Q.Y, Q.X);
+    fe_mul_x2(c.T2d, P.T, d2, n.XY2d, Q.T, d2);
+    fe_1(c.Z);
+    fe_copy(c.YpX, t);
+    fe_copy(c.YmX, t2);
+    tab.store(joint_index(1, 0), c);
+    fe_copy(c.YpX, n.YpX);
+    fe_copy(c.YmX, n.YmX);
+    fe_copy(c.T2d, n.XY2d);
+    tab.store(joint_index(0, 1), c);
+    ge_madd_niels_pm<false>(s, m, t, t2, P.T, nullptr, n);  // P + Q, P - Q
+  }
+  joint_store(tab, joint_index(1, 1), u, s);
+  ge_p3_to_p2(v, u);
+  ge_p2_dbl(s, v);
+  joint_store(tab, joint_index(2, 2), u, s);
+  joint_store(tab, joint_index(1, -1), u, m);
+  ge_p3_to_p2(v, u);
+  ge_p2_dbl(s, v);
+  tab.prefetch(joint_index(0, 1), false);
+  joint_store(tab, joint_index(2, -2), u, s);
+  // 2Q, then 2Q + P and P - 2Q
+  tab.take(c);
+  tab.prefetch(joint_index(1, 0), false);
+  ge_affine_dbl(s, c.YpX, c.YmX);
+  joint_store(tab, joint_index(0, 2), u, s);
+  tab.take(c);
+  fe_copy(n.YpX, c.YpX);
+  fe_copy(n.YmX, c.YmX);
+  fe_copy(n.XY2d, c.T2d);
+  ge_madd_niels_pm<true>(s, m, u, n);
+  joint_store(tab, joint_index(1, 2), u, s);
+  tab.prefetch(joint_index(1, 0), false);
+  joint_store(tab, joint_index(1, -2), u, m);
+  // 2P, then 2P + Q and 2P - Q
+  tab.take(c);
+  tab.prefetch(joint_index(0, 1), false);
+  ge_affine_dbl(s, c.YpX, c.YmX);
+  joint_store(tab, joint_index(2, 0), u, s);
+  tab.take(c);
+  fe_copy(n.YpX, c.YpX);
+  fe_copy(n.YmX, c.YmX);
+  fe_copy(n.XY2d, c.T2d);
+  ge_madd_niels_pm<false>(s, m, u, n);
+  joint_store(tab, joint_index(2, 1), u, s);
+  joint_store(tab, joint_index(2, -1), u, m);
+}
+
 // out = [k](-A) + [S]B  (Straus, most-significant first).
 // k: signed radix-16 digits (64 windows) from the per-lane table of j*(-A), j=0..8;
 // S: signed radix-2^BBITS digits from a shared table of j*B (niels), added once per

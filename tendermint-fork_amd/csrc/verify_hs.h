@@ -17,8 +17,19 @@
 //
 //   The check is then a 3-point Straus sum with ~130-bit scalars for A and R (4 doublings
 //   and two cached additions per radix-16 window, ~33 windows instead of 64) and the full
-//   scalar e for B from two radix-2^16 tables (j*B and j*2^128*B, 8 windows each), and
+//   scalar e for B from two radix-2^26 (or 2^16) tables (j*B and j*2^128*B), and
 //   the comparison with the identity is projective (X = 0, Y = Z): no inversion.
+//
+//   The throughput kernel takes the two additions of a window from ONE per-lane table: the
+//   joint signed radix-4 (Straus-Shamir) table of P = -A and Q = -sign(d) R, rows i P + j Q for
+//   (i, j) in [-2, 2]^2 up to sign — twelve rows (verify_core.h build_table_joint, 71 M + 12 S)
+//   instead of two tables of eight (j P and j Q, j <= 8: 116 M).  A radix-16 digit D of the
+//   recodings splits as D = 4h + l, l in [-2, 1], h in [-2, 2] (hs_split4), and a window is
+//   two sub-steps (2 doublings, then the row of the two scalars' h, or l, digits): the same
+//   16 S + 28 M per window, 3.9k fewer multiply-adds per signature in the table and a quarter
+//   fewer table rows written and resident (hs_straus_joint).  The hand-off, the window count
+//   and the recodings are those of the two-table form (hs_straus), which stays as the host
+//   reference; the latency kernels (latency.hip) build their own tables in LDS.
 //
 // (c, d) comes from the extended Euclidean algorithm on (N, k): r_i = t_i k (mod N),
 // stopped at the first r_i < 2^128, where |t_i| <= N / r_{i-1} <= 2^127.  If t_i is
@@ -393,6 +404,8 @@ TMED_HD void hs_b26_add(ge_p1p1 &t, ge_p3 &r, int m, const int dl[5], const int 
   ge_madd_niels(t, r, nb, false);
 }
 
+// The two-table form of the sum, which the kernels ran before the joint table (hs_straus_joint
+// below): kept as the reference tests/test_joint_table_host.py compares the joint sum with.
 // Q = [e]B + [c](-A) + [|d|](-sign(d) R) over W radix-16 windows (Straus, most significant
 // first).  DS: cword(w) / dword(w), word w (0..7) of the recoded c / |d| — read once per
 // eight windows, before the doublings that hide the read; the top window's digit also takes
@@ -495,6 +508,124 @@ TMED_HD void hs_straus(ge_p2 &out, const DS &ds, const uint32_t er[8], int W, TA
   out = q;
 }
 
+// A radix-16 digit D (regular windows [-8, 8], the top window [0, 16]) as two radix-4 digits,
+// D = 4h + l with l in [-2, 1]: h in [-2, 2], the top window's in [0, 4].
+TMED_HD void hs_split4(int D, int &h, int &l) {
+  l = ((D + 2) & 3) - 2;
+  h = (D - l) >> 2;
+}
+
+// The same sum as hs_straus from ONE joint radix-4 table (build_table_joint, verify_core.h) of
+// P = -A and Q = -sign(d) R: a radix-16 window is two sub-steps of two doublings and one cached
+// addition of row i P + j Q, (i, j) the high, then the low radix-4 digits of c and |d| — 16 S + 28 M
+// per window like hs_straus, with half the rows looked up.  TJ: prefetch(row, neg) / take(ge_cached&)
+// for rows 0..kJointRows, as TA / TR above.  The top window's high digits lie in [0, 4]: two rows,
+// (min(h, 2)) and the rest, the first taken as the accumulator itself (cached -> extended).
+// Every row is in flight two doublings before its take: the low row from the high sub-step's take,
+// the next window's high row from the low sub-step's (its digits from a word read a window ahead).
+// The radix-2^26 B steps at 26m doublings left fall between sub-steps: after the high one of
+// windows 6 and 19, at the end of windows 0, 13 and 26.
+template <class DS, class TJ, class BL, class BH>
+TMED_HD void hs_straus_joint(ge_p2 &out, const DS &ds, const uint32_t er[8], int W, TJ &tj, BL &bl, BH &bh) {
+  constexpr bool b26 = BL::kBits == 26;
+  static_assert(BL::kBits == 16 || BL::kBits == 26, "B windows of radix 2^16 or 2^26");
+  uint32_t el[4] = {er[0], er[1], er[2], er[3]}, eh[4] = {er[4], er[5], er[6], er[7]};
+  int d26l[5] = {0, 0, 0, 0, 0}, d26h[5] = {0, 0, 0, 0, 0};
+  if (b26) {
+    hs_b26_digits(d26l, d26h, er);
+    bl.prefetch(d26l[4] < 0 ? -d26l[4] : d26l[4]);
+    bh.prefetch(d26h[4] < 0 ? -d26h[4] : d26h[4]);
+  } else {
+    const int dl = (int)(el[3] >> 16) - 32768, dh = (int)(eh[3] >> 16) - 32768;
+    bl.prefetch(dl < 0 ? -dl : dl);
+    bh.prefetch(dh < 0 ? -dh : dh);
+  }
+  ge_p2 q;
+  ge_p1p1 t;
+  ge_p3 r;
+  ge_cached ca;
+  ge_niels nb;
+  uint32_t cw = ds.cword((W - 1) >> 3), dw = ds.dword((W - 1) >> 3), cwn = cw, dwn = dw;
+  int ih = 0, il;  // signed joint indices (joint_index) of the window's high and low digit pairs
+  {
+    // The top window's high part: digits in [0, 16] (word W >> 3 holds nibble W; at W = 64, the
+    // (k, 1) fallback, there is none and no carry).
+    const int dc = hs_top_digit(cw, W < 64 ? ((W & 7) ? cw : ds.cword(W >> 3)) : 0u, W);
+    const int dd = hs_top_digit(dw, W < 64 ? ((W & 7) ? dw : ds.dword(W >> 3)) : 0u, W);
+    int hc, lc, hd, ld;
+    hs_split4(dc, hc, lc);
+    hs_split4(dd, hd, ld);
+    const int c1 = hc < 2 ? hc : 2, d1 = hd < 2 ? hd : 2;
+    tj.prefetch(joint_index(c1, d1), false);
+    tj.take(ca);
+    tj.prefetch(joint_index(hc - c1, hd - d1), false);
+    ge_cached_to_p3(r, ca);
+    tj.take(ca);
+    il = joint_index(lc, ld);
+    tj.prefetch(il < 0 ? -il : il, il < 0);
+    ge_add_cached_pre(t, r, ca, false);
+    ge_p1p1_to_p2(q, t);
+  }
+#pragma unroll 1
+  for (int n = W - 1; n >= 0; n--) {
+    if (n > 0 && ((n - 1) & 7) == 7) {  // the next window's word, a window before its digits are split
+      cwn = ds.cword((n - 1) >> 3);
+      dwn = ds.dword((n - 1) >> 3);
+    }
+    if (n != W - 1) {  // high sub-step
+      ge_p2_dbl(t, q);
+      ge_p1p1_to_p2(q, t);
+      ge_p2_dbl(t, q);
+      ge_p1p1_to_p3(r, t);
+      tj.take(ca);
+      tj.prefetch(il < 0 ? -il : il, il < 0);
+      ge_add_cached_pre(t, r, ca, ih < 0);
+      if (b26 && (n == 6 || n == 19)) hs_b26_add(t, r, n == 19 ? 3 : 1, d26l, d26h, bl, bh);  // 26m left
+      ge_p1p1_to_p2(q, t);
+    }
+    // low sub-step
+    ge_p2_dbl(t, q);
+    ge_p1p1_to_p2(q, t);
+    ge_p2_dbl(t, q);
+    ge_p1p1_to_p3(r, t);
+    tj.take(ca);
+    const bool lneg = il < 0;
+    if (n > 0) {
+      cw = cwn;
+      dw = dwn;
+      const int sh = 4 * ((n - 1) & 7);
+      int hc, lc, hd, ld;
+      hs_split4((int)((cw >> sh) & 15u) - 8, hc, lc);
+      hs_split4((int)((dw >> sh) & 15u) - 8, hd, ld);
+      ih = joint_index(hc, hd);
+      il = joint_index(lc, ld);
+      tj.prefetch(ih < 0 ? -ih : ih, ih < 0);
+    }
+    ge_add_cached_pre(t, r, ca, lneg);
+    if (b26) {
+      if (n == 0 || n == 13 || n == 26) hs_b26_add(t, r, n / 13 * 2, d26l, d26h, bl, bh);
+    } else if ((n & 3) == 0 && n <= 28) {
+      const int dl = (int)(el[3] >> 16) - 32768, dh = (int)(eh[3] >> 16) - 32768;
+      words4_shl16(el);
+      words4_shl16(eh);
+      ge_p1p1_to_p3(r, t);
+      bl.take(nb);
+      const int nl = (int)(el[3] >> 16) - 32768;  // BL and BH each own a prefetch buffer: the next
+      bl.prefetch(nl < 0 ? -nl : nl);             // low row is in flight from here
+      niels_apply_sign(nb, dl < 0);
+      ge_madd_niels(t, r, nb, false);
+      ge_p1p1_to_p3(r, t);
+      bh.take(nb);
+      const int nh = (int)(eh[3] >> 16) - 32768;
+      bh.prefetch(nh < 0 ? -nh : nh);
+      niels_apply_sign(nb, dh < 0);
+      ge_madd_niels(t, r, nb, false);
+    }
+    ge_p1p1_to_p2(q, t);
+  }
+  out = q;
+}
+
 // (X : Y : Z) is the identity: X = 0 and Y = Z (Z != 0 for the complete formulas).
 TMED_HD bool p2_is_identity(const ge_p2 &q) { return fe_iszero(q.X) && fe_equal(q.Y, q.Z) && !fe_iszero(q.Z); }
 
@@ -510,26 +641,52 @@ TMED_HD void p2_mul8(ge_p2 &q) {
   }
 }
 
-// Phase 2 of the half-size path: tables of -A and -sign(d) R, the 3-point sum, the
-// identity test (of [8] times the sum when cofactor8: ZIP-215).  A: affine extended (Z = 1,
-// T set); R: affine (x, y).
-template <class DS, class TA, class TR, class BL, class BH>
-TMED_HD bool verify_main_hs(const DS &ds, bool dneg, const uint32_t er[8], int W, const ge_p3 &A, const fe &Rx,
-                            const fe &Ry, TA &ta, TR &tr, BL &bl, BH &bh, bool cofactor8 = false) {
-  ge_p3 P;  // -A (affine: the decoded key)
+// P = -A and Q = -sign(d) R, affine extended (Z = 1, T = xy), from the decoded A (T set) and R.
+TMED_HD void hs_points(ge_p3 &P, ge_p3 &Q, bool dneg, const ge_p3 &A, const fe &Rx, const fe &Ry) {
   fe_neg(P.X, A.X);
   fe_copy(P.Y, A.Y);
   fe_1(P.Z);
   fe_neg(P.T, A.T);
-  build_table_affine(ta, P);
-  if (dneg) fe_copy(P.X, Rx); else fe_neg(P.X, Rx);  // -sign(d) R (affine)
-  fe_copy(P.Y, Ry);
-  fe_mul(P.T, P.X, P.Y);
-  build_table_affine(tr, P);
+  if (dneg) fe_copy(Q.X, Rx); else fe_neg(Q.X, Rx);
+  fe_copy(Q.Y, Ry);
+  fe_1(Q.Z);
+  fe_mul(Q.T, Q.X, Q.Y);
+}
+
+// Phase 2 of the half-size path: the joint table of -A and -sign(d) R, the 3-point sum, the
+// identity test (of [8] times the sum when cofactor8: ZIP-215).  A: affine extended (Z = 1,
+// T set); R: affine (x, y).
+template <class DS, class TJ, class BL, class BH>
+TMED_HD bool verify_main_hsj(const DS &ds, bool dneg, const uint32_t er[8], int W, const ge_p3 &A, const fe &Rx,
+                             const fe &Ry, TJ &tj, BL &bl, BH &bh, bool cofactor8 = false) {
+  ge_p3 P, Q;
+  hs_points(P, Q, dneg, A, Rx, Ry);
+  build_table_joint(tj, P, Q);
   ge_p2 q;
-  hs_straus(q, ds, er, W, ta, tr, bl, bh);
+  hs_straus_joint(q, ds, er, W, tj, bl, bh);
   if (cofactor8) p2_mul8(q);
   return p2_is_identity(q);
+}
+
+// The joint table's rows over two 8-row accessors (rows 1..8 in ta, 9..12 in tr's 1..4): the host
+// build's tables (tests/native/hostsim.cpp) are pairs of the two-table form.
+template <class TA, class TR>
+struct HsJointPair {
+  TA &ta;
+  TR &tr;
+  bool hi = false;
+  TMED_HDM void store(int j, const ge_cached &c) { if (j <= 8) ta.store(j, c); else tr.store(j - 8, c); }
+  TMED_HDM void prefetch(int j, bool swap = false) {
+    hi = j > 8;
+    if (hi) tr.prefetch(j - 8, swap); else ta.prefetch(j, swap);
+  }
+  TMED_HDM void take(ge_cached &c) const { if (hi) tr.take(c); else ta.take(c); }
+};
+template <class DS, class TA, class TR, class BL, class BH>
+TMED_HD bool verify_main_hs(const DS &ds, bool dneg, const uint32_t er[8], int W, const ge_p3 &A, const fe &Rx,
+                            const fe &Ry, TA &ta, TR &tr, BL &bl, BH &bh, bool cofactor8 = false) {
+  HsJointPair<TA, TR> tj{ta, tr};
+  return verify_main_hsj(ds, dneg, er, W, A, Rx, Ry, tj, bl, bh, cofactor8);
 }
 
 }  // namespace tmed
