@@ -11,7 +11,7 @@
 #include "keycache.h"
 
 struct tmed_ctx;
-struct BsStream;  // commit.hip: the context's blocksync batch stream
+struct BsStream;  // blocksync.h: the context's blocksync batch stream
 
 namespace tmed {
 
@@ -113,7 +113,7 @@ Keyset *find_keyset(tmed_ctx *c, uint64_t handle);
 // The commit seam's key-set cache (keycache.hip, keycache.h); every call below holds ctx->mu.
 struct KeyCacheDev;
 void keycache_destroy(tmed_ctx *c);
-void bs_destroy(tmed_ctx *c);  // commit.hip: the blocksync batch stream (before keycache_destroy)
+void bs_destroy(tmed_ctx *c);  // blocksync.h: the blocksync batch stream (before keycache_destroy)
 // The seam's rule for a call that is not itself a blocksync window: collect every batch of the
 // submitted windows first (ctx->mu held), and after the lock is dropped release the windows that
 // completed (their key-set cache pins take the lock).
@@ -280,7 +280,7 @@ struct tmed_ctx {
   tmed::KernelTimer timer;
   tmed::DevBuf d_a, d_b, d_msg, d_off, d_out, d_c;
   tmed::HostBuf h_a, h_b, h_msg, h_off, h_out, h_c;
-  tmed::VoteSlot vslot[3];  // the blocksync pipeline (commit.hip BsStream: two slots, three when the signatures go direct)
+  tmed::VoteSlot vslot[3];  // the blocksync pipeline (blocksync.h BsStream: two slots, three when the signatures go direct)
   BsStream *bs = nullptr;   // batches of submitted blocksync windows in flight (tmed_blocksync_submit)
   tmed::Lane lane1;         // the pipelined seam's second kernel lane (VoteStage::lane)
   // Merkle roots and proofs (merkle.hip), one builder for both: every node of every level of every

@@ -109,7 +109,7 @@ void keycache_destroy(tmed_ctx *c) {  // ctx->mu not held: the worker may be wai
   // the pool's Keyset is freed with the context's key sets
 }
 
-// ---- the seam's side (commit.hip keycache_resolve); the caller holds ctx->mu -----------------
+// ---- the seam's side (kc_resolve.h keycache_resolve); the caller holds ctx->mu -----------------
 uint64_t keycache_pool_handle(const tmed_ctx *c) { return c->kc ? c->kc->kc.be.handle : 0; }
 const KcSet *keycache_find(tmed_ctx *c, const KcKey &key) { return cache_of(c).find(key); }
 bool keycache_same_keys(const tmed_ctx *c, const KcSet &e, const uint8_t *pubs, size_t n) {

@@ -1,6 +1,7 @@
-// seam_host.h — the host half of the commit seam (commit.hip): planning (the reference
+// seam_host.h — the host half of the commit seam (commit.hip, blocksync.h): planning (the reference
 // prechecks and candidate selection), the parallel merge of the planning parts, candidate
-// aliasing, staging groups, scatter and the replay of every reference loop.  Host C++ only (no
+// aliasing, staging groups (by key set too), scatter, the replay of every reference loop and the
+// finish of a pipelined batch.  Host C++ only (no
 // HIP): commit.hip includes it, and tests/native/seam_race.cpp compiles the same code under
 // ThreadSanitizer with the pool jitter on, so a read of what another part of the same parallel
 // region writes is a reported race on the CPU suite, not a rare wrong bit on the GPU box.
@@ -17,6 +18,10 @@
 //   finish_parts           grp / cands / plans (planning, finished before the batch was staged);
 //                          part t scatters, aliases and replays only its own requests' candidates
 //                          (every alias lies inside its part: pair_request pairs within a part)
+//   finish_batch           finish_parts, or scatter_bits -> copy_aliases -> seam_replay, each a region
+//                          of its own that reads what the one before it wrote
+//   group_by_keyset        serial, but for build_group when the call has one key set and aliases
+// (The set numbering of the key-set cache's resolution has its own table: set_index.h.)
 #pragma once
 
 #include <string.h>
@@ -104,7 +109,7 @@ struct Cands {
   std::vector<uint32_t> tmpl_of;
   // the planning workers' parts when the batch was aliased with a staging group (seam_plan):
   // part t holds requests [preq[t], preq[t+1]), aliases [pal[t], pal[t+1]) and group segments
-  // [pseg[t], pseg[t+1]), every alias inside its part (bs_finish works part by part); else empty
+  // [pseg[t], pseg[t+1]), every alias inside its part (finish_batch works part by part); else empty
   std::vector<size_t> preq, pal, pseg;
   size_t size() const { return off.empty() ? 0 : off.back(); }
   uint32_t tmpl_row(uint32_t q) const { return tmpl_of.empty() ? q : tmpl_of[q]; }
@@ -392,7 +397,8 @@ static int build_cand_batch(const tmed_commit_request *reqs, size_t n, const Can
 // caller may rewrite its buffers between calls).  The plan records every lookup result the
 // replay needs (the candidate's validator, kNoValidator, the double vote), so the index is
 // never read after planning.
-// Sets resolved through the key-set cache (KcCall, below) carry their entry's address index.
+// Sets resolved through the key-set cache (KcCall: kc_resolve.h, or the harness's stub) carry their
+// entry's address index.
 struct KcCall;
 static const AddrIndex *kc_addr_index(const KcCall *kc, const tmed_valset &vs);
 struct AddrScratch {
@@ -1137,7 +1143,7 @@ static void scatter_bits(const tmed_commit_request *reqs, const Cands &cands, co
 }
 
 
-// The part-wise finish of a pipelined batch (bs_finish): the planning workers' parts of an aliased
+// The part-wise finish of a pipelined batch (finish_batch): the planning workers' parts of an aliased
 // batch, each in one fork-join — its staged bits -> valid[] by candidate, its aliased bits, then the
 // replay of its requests.  Part t reads only candidates of its own requests: its staging segments
 // [pseg[t], pseg[t+1]) hold exactly its runs, and every alias lies inside its part (pair_request
@@ -1157,4 +1163,66 @@ static int finish_parts(const tmed_commit_request *rq, const Cands &cd, const Gr
   for (int rc : rcs)
     if (rc != TMED_OK) return rc;
   return TMED_OK;
+}
+
+// The host finish of one pipelined batch whose bits were collected (blocksync.h bs_finish): an
+// aliased staged batch planned by several workers goes part by part (finish_parts); otherwise the
+// staged bits are scattered by candidate and the aliases copied when there are any, and one replay
+// reads `bits` (staged, nothing aliased: already in candidate order) or `valid` (scattered here, or
+// filled by the caller's host verifier when the batch was not staged).
+static int finish_batch(const tmed_commit_request *rq, size_t n, tmed_commit_result *out, const Plans &plans,
+                        const Cands &cands, const Group &grp, const uint8_t *bits, std::vector<uint8_t> &valid,
+                        bool staged) {
+  PhaseClock clk;
+  const size_t m = cands.size();
+  const bool aliased = staged && !cands.alias.empty();
+  const size_t np = cands.preq.size() ? cands.preq.size() - 1 : 0;
+  int r;
+  if (aliased && np && !grp.rix.empty()) {
+    // part by part (the planning workers' parts: each alias inside its part): the part's staged
+    // bits -> by candidate, its aliased bits, then the replay of its requests — one fork-join
+    valid.resize(m);
+    r = finish_parts(rq, cands, grp, bits, valid.data(), plans, out);
+    clk.lap("scatter_aliases_replay");
+  } else {
+    if (aliased) {       // bits by staged segment -> by candidate
+      valid.resize(m);  // scatter_bits writes every staged candidate, copy_aliases the rest
+      scatter_bits(rq, cands, grp, bits, valid.data());
+      clk.lap("scatter");
+      copy_aliases(cands, valid.data());
+      clk.lap("aliases");
+    }
+    // the device bits are in candidate order: replay reads them directly (it applies the
+    // signature-length rule itself)
+    r = seam_replay(rq, n, out, plans, staged && !aliased ? bits : valid.data());
+    clk.lap("replay");
+  }
+  if (staged) clk.emit("blocksync finish", n, m);
+  return r;
+}
+
+// The runs of one seam call grouped by key set, one device launch sequence per group (commit.hip
+// ctx_verify); aliased candidates are left out (copy_aliases).  Usually a single group: then it is
+// every run, in order.
+static void group_by_keyset(const tmed_commit_request *reqs, const Cands &cands, std::vector<uint64_t> &gkeys,
+                            std::vector<Group> &groups) {
+  gkeys.clear();
+  groups.clear();
+  size_t ap = 0;
+  bool one_set = !cands.runs.empty();
+  for (size_t r = 1; r < cands.runs.size() && one_set; r++)
+    one_set = reqs[cands.runs[r].req].vals->keyset == reqs[cands.runs[0].req].vals->keyset;
+  if (one_set && !cands.alias.empty()) {
+    gkeys.push_back(reqs[cands.runs[0].req].vals->keyset);
+    groups.emplace_back();
+    build_group(cands, groups[0]);
+  }
+  for (size_t r = 0; r < cands.runs.size() && !(one_set && !cands.alias.empty()); r++) {
+    const uint64_t ks = reqs[cands.runs[r].req].vals->keyset;
+    size_t g = 0;
+    while (g < gkeys.size() && gkeys[g] != ks) g++;
+    if (g == gkeys.size()) { gkeys.push_back(ks); groups.emplace_back(); groups.back().start(); }
+    groups[g].add_run(cands, (uint32_t)r, cands.alias, ap);
+  }
+  if (groups.size() == 1 && cands.alias.empty()) groups[0] = Group();  // every run in order: the call's own offsets
 }

@@ -1,7 +1,7 @@
 // keycache_fuzz.cpp — TEST-ONLY randomized check of the seam's key-set cache policy
 // (tendermint-fork_amd/csrc/keycache.h) over a host stand-in for the device pool, built with
 // AddressSanitizer + UndefinedBehaviorSanitizer by tests/test_native_sanitizers.py.  Calls are
-// emulated as the seam makes them (commit.hip keycache_resolve): pin, resolve sets (fast path or
+// emulated as the seam makes them (kc_resolve.h keycache_resolve): pin, resolve sets (fast path or
 // lookup, may_reset only before the call's first keyed set), hold the entries, check at the end of
 // the call that every held index still names the set's own key in the pool, unpin.  Two calls may
 // overlap.  Between calls: deferred builds drained, failing appends, budget / LRU limits changed.

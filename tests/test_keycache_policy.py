@@ -71,7 +71,7 @@ class Cache:
         return bool(k), idx[:n]
 
     def call(self, sets_sigs, **kw):
-        """One seam call: pin, look every set up, unpin, drain (as commit.hip KcCall does)."""
+        """One seam call: pin, look every set up, unpin, drain (as kc_resolve.h KcCall does)."""
         self.l.kct_pin(self.h)
         out = []
         any_keyed = False
@@ -153,7 +153,7 @@ def test_light_client_sets_share_pooled_keys(kct):
 
 def test_call_level_amortisation(kct):
     """A call is keyed when its signatures pay for ALL its missing keys, even if one set alone
-    would not (commit.hip keycache_resolve: build_all)."""
+    would not (kc_resolve.h keycache_resolve: build_all)."""
     c = Cache(kct, 100_000)
     pool = keys(b"am", 0, 400)
     sets = [pool[h:h + 100] for h in range(0, 300, 100)]
@@ -254,7 +254,7 @@ def test_entries_dropped_while_pinned_are_retired(kct):
 
 
 def test_deferred_first_commit_of_a_new_set(kct):
-    """The seam's fast path for a single commit on a new set (commit.hip keycache_resolve): one
+    """The seam's fast path for a single commit on a new set (kc_resolve.h keycache_resolve): one
     pool probe (all_pooled stops at the first missing key), the keys copied (defer), the call
     generic; the worker's drain then queues and builds exactly the missing keys, and the next
     commit on the set is keyed.  Counted as the deferred lookup path counts."""

@@ -7,7 +7,10 @@ own key in the pool until the call ends.  tests/native/pool_stress.cpp runs the 
 worker pool (csrc/host_pool.h) from several caller threads with nested calls and throwing parts
 under ThreadSanitizer.  tests/native/seam_race.cpp runs the commit seam's host half
 (csrc/seam_host.h: planning, the parallel merge, aliasing, staging groups, the part-wise finish)
-under ThreadSanitizer with the pool jitter on, and is shown to catch round 5's add_run race.
+under ThreadSanitizer with the pool jitter on, as a pipelined batch and as one call over several key
+sets, and is shown to catch round 5's add_run race.  tests/native/set_index_race.cpp does the same
+for the set numbering of the key-set cache's resolution (csrc/set_index.h), and is shown to catch a
+plain store in place of its min-CAS.
 Either binary exits non-zero on a broken invariant; a sanitizer report aborts it."""
 import os
 import shutil
@@ -100,3 +103,65 @@ def test_seam_race_harness_catches_round5_add_run(tmp_path):
     env = dict(os.environ, TMED_HOST_THREADS="8", TSAN_OPTIONS="halt_on_error=1")
     r = subprocess.run([exe] + SEAM_ARGS + ["200", "7"], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode != 0 and "data race" in r.stderr and "add_run" in r.stderr, r.stderr[-3000:]
+
+
+def test_seam_host_keyset_groups_race_free_tsan(tmp_path):
+    """One seam call on sets of three key sets (handles 0, 1, 2 in blocks of 50 headers), as ctx_verify
+    runs it: group_by_keyset, per group the bits in staging order and scatter_bits, then copy_aliases
+    and seam_replay once — under ThreadSanitizer with the pool jitter on.  Outcomes depend only on
+    (key, signature), so the digest equals that of the one-key-set batch on one host thread."""
+    tsan = _build_seam(tmp_path, CSRC, "seam_race_tsan", ["-fsanitize=thread"])
+    plain = _build_seam(tmp_path, CSRC, "seam_race", [])
+    serial = _run([plain] + SEAM_ARGS + ["0", "7"], dict(os.environ, TMED_HOST_THREADS="1"))
+    for threads, jitter in (("8", "200"), ("5", "50")):
+        env = dict(os.environ, TMED_HOST_THREADS=threads, TSAN_OPTIONS="halt_on_error=1")
+        out = _run([tsan] + SEAM_ARGS + [jitter, "7", "3"], env)
+        assert int(out.split("groups")[1].split()[0]) > 1, out
+        assert int(out.split("aliases")[1].split()[0]) > 0, out
+        assert _digest(out) == _digest(serial), (out, serial)
+
+
+def _build_set_index(tmp_path, csrc, name, flags):
+    """tests/native/set_index_race.cpp against the set numbering in `csrc` (set_index.h)."""
+    exe = str(tmp_path / name)
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", *flags, "-I", csrc, os.path.join(NATIVE, "set_index_race.cpp"),
+                    "-o", exe, "-lpthread"], check=True, capture_output=True, timeout=300)
+    return exe
+
+
+def test_set_numbering_race_free_tsan(tmp_path):
+    """The set numbering of the key-set cache's resolution (csrc/set_index.h number_sets: the lock-free
+    pointer table filled from the host pool) at the product's parallelism, under ThreadSanitizer with
+    the pool jitter on: a few shared sets, one set per request, no set.  The program checks the set
+    order and the per-set sums itself; its digest equals that of one host thread."""
+    tsan = _build_set_index(tmp_path, CSRC, "set_index_race_tsan", ["-fsanitize=thread"])
+    plain = _build_set_index(tmp_path, CSRC, "set_index_race", [])
+    serial = _run([plain, "0", "7"], dict(os.environ, TMED_HOST_THREADS="1"))
+    assert "misses 0" in serial and "sets 5" in serial and "sets 2048" in serial and "sets 0" in serial, serial
+    for threads, jitter in (("8", "200"), ("5", "50")):
+        env = dict(os.environ, TMED_HOST_THREADS=threads, TSAN_OPTIONS="halt_on_error=1")
+        out = _run([tsan, jitter, "7"], env)
+        assert _digest(out) == _digest(serial), (out, serial)
+
+
+def test_set_index_harness_catches_plain_min_store(tmp_path):
+    """The harness fails a numbering whose smallest-request-index update is a plain compare-and-store
+    instead of the atomic min-CAS: ThreadSanitizer reports the race inside number_sets."""
+    bad = tmp_path / "csrc"
+    shutil.copytree(CSRC, str(bad), ignore=shutil.ignore_patterns("*.hip"))
+    inc = os.path.abspath(os.path.join(CSRC, "..", "..", "include", "tmed25519.h"))
+    cas = ("      int32_t f = __atomic_load_n(&tval[h], __ATOMIC_RELAXED);  // the slot's smallest request index\n"
+           "      while ((int32_t)q < f && !__atomic_compare_exchange_n(&tval[h], &f, (int32_t)q, true, __ATOMIC_RELAXED,\n"
+           "                                                            __ATOMIC_RELAXED)) {\n"
+           "      }\n")
+    for f in os.listdir(str(bad)):
+        p = bad / f
+        s = p.read_text().replace('"../../include/tmed25519.h"', '"%s"' % inc)
+        if f == "set_index.h":
+            assert cas in s
+            s = s.replace(cas, "      if ((int32_t)q < tval[h]) tval[h] = (int32_t)q;\n")
+        p.write_text(s)
+    exe = _build_set_index(tmp_path, str(bad), "set_index_race_bad", ["-fsanitize=thread"])
+    env = dict(os.environ, TMED_HOST_THREADS="8", TSAN_OPTIONS="halt_on_error=1")
+    r = subprocess.run([exe, "200", "7"], capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode != 0 and "data race" in r.stderr and "number_sets" in r.stderr, r.stderr[-3000:]

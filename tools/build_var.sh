@@ -8,7 +8,7 @@ name=$1; shift
 cd "$(dirname "$0")/../tendermint-fork_amd"
 make -s >/dev/null
 mkdir -p lib_var/$name /tmp/tmed_var_$name
-all="kernels kernels_tables latency tmed_capi signbytes microbench commit keyset merkle zip215 keycache"
+all=$(sed -n 's/^SRCS := //p' Makefile | tr ' ' '\n' | sed 's|^csrc/||; s|\.hip$||' | tr '\n' ' ')  # the Makefile's units
 objs=""
 for s in $all; do
   if [[ " ${VAR_SRCS:-kernels kernels_tables} " == *" $s "* ]]; then

@@ -9,7 +9,7 @@ import os
 import sys
 import time
 
-os.environ.setdefault("TMED_DEBUG_ZERO", "1")  # commit.hip debug_record_zeros
+os.environ.setdefault("TMED_DEBUG_ZERO", "1")  # debug_zero.h debug_record_zeros
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -25,7 +25,7 @@ import tmed.types as T  # noqa: E402
 from tmed._native import lib  # noqa: E402
 
 
-class ZeroRec(ctypes.Structure):  # commit.hip ZeroRec
+class ZeroRec(ctypes.Structure):  # debug_zero.h ZeroRec
     _fields_ = [("req", ctypes.c_uint64), ("sig", ctypes.c_int32), ("pos", ctypes.c_uint32),
                 ("msg_len", ctypes.c_uint32), ("batch_m", ctypes.c_uint32),
                 ("key_host", ctypes.c_uint8 * 32), ("sig_host", ctypes.c_uint8 * 64),
