@@ -273,6 +273,31 @@ int tmed_test_joint_rows(tmed_ctx *ctx, const uint8_t *a, const uint8_t *r, cons
                          uint8_t *rows);
 
 /*
+ * Tests only (tests/test_gpu_table_rows.py): the fixed-base tables of B, row by row.  table: 0 the
+ * radix-256 comb (32 windows x 129 rows), 1 the radix-2^16 table (32769 rows), 2 the radix-2^16
+ * comb (16 x 32769), 3 the two radix-2^26 tables (2 x (2^25 + 1)), 4 the radix-2^24 comb
+ * (11 x (2^23 + 1), present after the first key-set load).
+ *
+ * tmed_test_b_table_entry: row j of window `window` as the 30 int32 limbs the kernels read (y + x,
+ * y - x, 2d x y of the affine point, as tmed_keyset_comb_entry).  Drains the device first.
+ * TMED_EINVAL for a table this context does not hold or an index out of range.
+ *
+ * tmed_test_table_chain: one device lane per row of a whole table: B table `table` (handle = 0), or
+ * every key's comb of key set `handle` (radix_bits 8, or tmed_keyset_a_window_bits once that comb is
+ * built).  Row (w, 0) must be the identity (1, 1, 0); row (w, j) = row (w, j - 1) + row (w, 1) for
+ * j >= 2 (the kernels' own mixed addition, all three coordinates compared fully reduced);
+ * row (w + 1, 1) = 2^r row (w, 1) (table 3: 2^128).  Table 4's window 10 follows the chain up to
+ * j = 32767 and is the identity beyond; a key that does not decode has every row the identity.
+ * *rows: the rows checked; *n_bad: the rows that fail; first_bad: up to 16 of them as
+ * window << 32 | j, in any order.  corrupt_j != 0 (tables 0..2 only, handle = 0): the check runs on
+ * a scratch copy of the table whose row (corrupt_window, corrupt_j) has limb 0 of its first
+ * coordinate one off, so a caller sees the check fail.
+ */
+int tmed_test_b_table_entry(tmed_ctx *ctx, int table, uint32_t window, uint32_t j, int32_t out[30]);
+int tmed_test_table_chain(tmed_ctx *ctx, int table, uint64_t handle, int radix_bits, uint32_t corrupt_window,
+                          uint32_t corrupt_j, uint64_t *rows, uint64_t *n_bad, uint64_t first_bad[16]);
+
+/*
  * With TMED_DEBUG_ZERO set at the first pipelined generic batch: every staged candidate whose
  * device bit is 0 is recorded (request, signature, staging position, the staged and the device
  * copies of its key and signature, the assembled sign-bytes).  Copies up to cap records into out

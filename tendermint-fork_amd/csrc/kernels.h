@@ -176,6 +176,22 @@ hipError_t launch_test_delay(hipStream_t stream, uint32_t us);
 // rows ([i][12][128 B], n * kSlabJointSlotBytes bytes).
 hipError_t launch_test_joint_rows(const uint8_t *a, const uint8_t *r, const uint8_t *dneg, uint32_t n, int4 *rows,
                                   hipStream_t stream);
+// Tests (tmed_test_table_chain): one lane per row of a whole table of `units` x `windows` windows,
+// window w's rows at w * entries (the last window holds top_entries rows), one unit after the
+// other from base, or key by key through a key set's chunk table.  Row (w, 0) must be the
+// identity, row (w, j) = row (w, j - 1) + row (w, 1) for 2 <= j, row (w + 1, 1) = 2^step_bits
+// row (w, 1); the last window's rows past top_chain_last, and every row of a unit whose ok byte
+// is 0, must be the identity.  d_out (18 words, zeroed by the caller): rows checked, rows that
+// fail, up to 16 of those as window << 32 | j.
+struct ChainPlan {
+  const int4 *base;
+  const int4 *const *chunks;  // non-null: unit u at chunks[u >> kKeyChunkBits] (device table)
+  const uint8_t *ok;          // null: every unit decodes
+  uint64_t units, rows_per_unit;
+  uint32_t windows, entries, top_entries, top_chain_last, step_bits;
+};
+hipError_t launch_table_chain(const ChainPlan &p, uint64_t *d_out, hipStream_t stream);
+hipError_t launch_table_corrupt(int4 *row, hipStream_t stream);  // limb 0 of the row's first coordinate += 1
 hipError_t launch_window_stats(const int4 *prep, uint32_t stride, uint32_t count, uint32_t *d_hist,
                                hipStream_t stream);
 

@@ -667,21 +667,6 @@ struct CombRowPf {
   }
 };
 
-// (x, y) affine niels (y+x, y-x, 2dxy) -> extended (4x : 4y : 4 : 4xy): X = 2(a - b), Y = 2(a + b),
-// T = (a - b)(a + b) with a = y+x, b = y-x.
-__device__ __forceinline__ void ge_niels_to_p3(ge_p3 &r, const ge_niels &e) {
-  fe d, s;
-  fe_sub(d, e.YpX, e.YmX);
-  fe_add(s, e.YpX, e.YmX);
-  fe_mul(r.T, d, s);
-  fe_add(r.X, d, d);
-  fe_carry(r.X, r.X);  // the next addition's Y +- X must stay a 3-sum of carried values
-  fe_add(r.Y, s, s);
-  fe_carry(r.Y, r.Y);
-  fe_0(r.Z);
-  r.Z.v[0] = 4;
-}
-
 __device__ __forceinline__ const int4 *ks_arow(const int4 *ak, int w, uint32_t byte, bool &neg) {
   const int d = (int)byte - 128;
   neg = d < 0;

@@ -214,8 +214,10 @@ hipError_t launch_build_b26(const int4 *comb16, int4 *tab, hipStream_t stream) {
 // Entry (w, j) of the radix-2^24 comb: j * 2^(24w) B for j = 0..2^23.  24w = 16v + r (r = 0 or 8):
 // J = j 2^r < 2^31 as two signed 16-bit digits at windows v, v + 1 of the radix-2^16 comb (two mixed
 // additions), then affine niels with one inversion.  Window 10 (bits 240..263) only ever needs
-// j <= 2^16 (S < 2^256); its entries whose second digit would fall past the comb's last window are
-// left as the identity.
+// j <= 4097 (S < L < 2^252 + 2^125, plus the bit below); it sits on the comb's last window (v = 15),
+// so an entry with a second digit has nowhere to take it from and is left as the identity: that is
+// every j >= 2^15, where d0 >= 32768 carries into d1 (tests/test_gpu_table_rows.py pins both the
+// chain up to 32767 and the identity beyond).
 __global__ __launch_bounds__(256) void b24_fill_kernel(const int4 *__restrict__ comb16, int4 *__restrict__ tab) {
   const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= (uint32_t)kB24Windows * kB24Entries) return;
@@ -323,6 +325,99 @@ hipError_t launch_build_comba(const uint8_t *pubs, uint32_t n, int32_t *bases, i
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(comba_bases_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, pubs, n, bases);
   hipLaunchKernelGGL(comba_fill_kernel, dim3(n * kCombABlocksPerKey), dim3(64), 0, stream, bases, comba);
+  return hipGetLastError();
+}
+
+// ---- tests: the chain check of a whole table (kernels.h ChainPlan) ------------------------
+__device__ __forceinline__ bool niels_is_identity(const ge_niels &e) {
+  fe one;
+  fe_1(one);
+  return fe_equal(e.YpX, one) && fe_equal(e.YmX, one) && fe_iszero(e.XY2d);
+}
+// the affine niels row e is the projective point P: e (Y+X, Y-X, 2dXY / Z^2) against P's
+// (Y + X) / Z, (Y - X) / Z, 2d T / Z, cross-multiplied and compared fully reduced
+__device__ __forceinline__ bool niels_equals_p3(const ge_niels &e, const ge_p3 &P) {
+  fe l, r, d2;
+  fe_mul(l, e.YpX, P.Z);
+  fe_add(r, P.Y, P.X);
+  bool same = fe_equal(l, r);
+  fe_mul(l, e.YmX, P.Z);
+  fe_sub(r, P.Y, P.X);
+  same = fe_equal(l, r) && same;
+  fe_const_d2(d2);
+  fe_mul(l, e.XY2d, P.Z);
+  fe_mul(r, d2, P.T);
+  same = fe_equal(l, r) && same;
+  return same && !fe_iszero(P.Z);
+}
+
+// One lane per row (unit u, window w, entry j).  Reads the table only; writes out[0] (rows
+// checked), out[1] (rows that fail) and out[2..17] (the first failing rows, window << 32 | j).
+__global__ __launch_bounds__(256) void table_chain_kernel(ChainPlan p, unsigned long long *__restrict__ out) {
+  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = g < p.rows_per_unit * p.units;
+  bool bad = false;
+  uint32_t w = 0, j = 0;
+  if (live) {
+    const uint64_t u = g / p.rows_per_unit;
+    const uint32_t rr = (uint32_t)(g % p.rows_per_unit);
+    w = rr / p.entries;
+    if (w >= p.windows) w = p.windows - 1;
+    j = rr - w * p.entries;
+    const int4 *unit = p.chunks ? p.chunks[u >> kKeyChunkBits] + (u & (kKeyChunkKeys - 1)) * p.rows_per_unit * kCombEntryInt4
+                                : p.base;
+    const int4 *win = unit + (size_t)w * p.entries * kCombEntryInt4;
+    const bool top = w + 1 == p.windows;
+    ge_niels e;
+    niels_load(e, win + (size_t)j * kCombEntryInt4);
+    if (j == 0 || (p.ok && !p.ok[u]) || (top && j > p.top_chain_last)) {
+      bad = !niels_is_identity(e);
+    } else if (j == 1) {
+      if (!top) {  // the next window's base: step_bits doublings of this one
+        ge_p3 P;
+        ge_p2 q;
+        ge_p1p1 t;
+        ge_niels_to_p3(P, e);
+        ge_p3_to_p2(q, P);
+#pragma unroll 1
+        for (uint32_t d = 0; d + 1 < p.step_bits; d++) { ge_p2_dbl(t, q); ge_p1p1_to_p2(q, t); }
+        ge_p2_dbl(t, q);
+        ge_p1p1_to_p3(P, t);
+        niels_load(e, win + (size_t)(p.entries + 1) * kCombEntryInt4);
+        bad = !niels_equals_p3(e, P);
+      }
+    } else {  // row j = row (j - 1) + row 1
+      ge_niels prev, one;
+      ge_p3 P;
+      ge_p1p1 t;
+      niels_load(prev, win + (size_t)(j - 1) * kCombEntryInt4);
+      niels_load(one, win + kCombEntryInt4);
+      ge_niels_to_p3(P, prev);
+      ge_madd_niels(t, P, one, false);
+      ge_p1p1_to_p3(P, t);
+      bad = !niels_equals_p3(e, P);
+    }
+  }
+  const unsigned long long lanes = __ballot(live);
+  if (live && (threadIdx.x & 63u) == (uint32_t)(__ffsll(lanes) - 1))
+    atomicAdd(out, (unsigned long long)__popcll(lanes));
+  if (bad) {
+    const unsigned long long slot = atomicAdd(out + 1, 1ull);
+    if (slot < 16) out[2 + slot] = (unsigned long long)w << 32 | j;
+  }
+}
+
+__global__ void table_corrupt_kernel(int4 *row) { row->x += 1; }
+
+hipError_t launch_table_chain(const ChainPlan &p, uint64_t *d_out, hipStream_t stream) {
+  const uint64_t blocks = (p.rows_per_unit * p.units + 255) / 256;
+  if (blocks == 0 || blocks > 0x7fffffffu) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(table_chain_kernel, dim3((uint32_t)blocks), dim3(256), 0, stream, p,
+                     reinterpret_cast<unsigned long long *>(d_out));
+  return hipGetLastError();
+}
+hipError_t launch_table_corrupt(int4 *row, hipStream_t stream) {
+  hipLaunchKernelGGL(table_corrupt_kernel, dim3(1), dim3(1), 0, stream, row);
   return hipGetLastError();
 }
 

@@ -463,6 +463,101 @@ int tmed_test_joint_rows(tmed_ctx *c, const uint8_t *a, const uint8_t *r, const 
   return e == hipSuccess ? TMED_OK : map_err(e);
 }
 
+// The B tables by the index tmed_test_b_table_entry / tmed_test_table_chain take; false: no
+// such table on this context.
+static bool b_table_plan(const tmed_ctx *c, int table, ChainPlan &p) {
+  p = ChainPlan{};
+  p.units = 1;
+  switch (table) {
+    case 0: p.base = c->d_bcomb; p.windows = kCombWindows; p.entries = kCombEntries; p.step_bits = 8; break;
+    case 1: p.base = c->d_b16; p.windows = 1; p.entries = kB16Entries; p.step_bits = 16; break;
+    case 2: p.base = c->d_bcomb16; p.windows = 16; p.entries = kB16Entries; p.step_bits = 16; break;
+    case 3: p.base = c->d_b26; p.windows = 2; p.entries = kB26Entries; p.step_bits = 128; break;
+    case 4: p.base = c->d_b24; p.windows = kB24Windows; p.entries = kB24Entries; p.step_bits = 24; break;
+    default: return false;
+  }
+  p.top_entries = p.entries;
+  // b24_fill_kernel: window 10's entries from 2^15 up are the identity
+  p.top_chain_last = table == 4 ? 32767u : p.entries - 1;
+  p.rows_per_unit = (uint64_t)p.windows * p.entries;
+  return p.base != nullptr;
+}
+
+int tmed_test_b_table_entry(tmed_ctx *c, int table, uint32_t window, uint32_t j, int32_t out[30]) {
+  if (!c || !out) return TMED_EINVAL;
+  std::lock_guard<std::mutex> lk(c->mu);
+  ChainPlan p;
+  if (!b_table_plan(c, table, p) || window >= p.windows || j >= p.entries) return TMED_EINVAL;
+  (void)hipSetDevice(c->device);
+  int4 row[kCombEntryInt4];
+  if (hipStreamSynchronize(c->stream) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return TMED_EHIP;
+  const int4 *src = p.base + ((size_t)window * p.entries + j) * kCombEntryInt4;
+  if (hipMemcpy(row, src, sizeof(row), hipMemcpyDeviceToHost) != hipSuccess) return TMED_EHIP;
+  const int32_t *w = reinterpret_cast<const int32_t *>(row);
+  for (int i = 0; i < 30; i++) out[i] = w[i];
+  return TMED_OK;
+}
+
+int tmed_test_table_chain(tmed_ctx *c, int table, uint64_t handle, int radix_bits, uint32_t corrupt_window,
+                          uint32_t corrupt_j, uint64_t *rows, uint64_t *n_bad, uint64_t first_bad[16]) {
+  if (!c || !rows || !n_bad || !first_bad) return TMED_EINVAL;
+  std::lock_guard<std::mutex> lk(c->mu);
+  ChainPlan p;
+  if (handle != 0) {
+    const Keyset *k = find_keyset(c, handle);
+    if (!k || k->n == 0 || corrupt_j != 0) return TMED_EINVAL;
+    p = ChainPlan{};
+    p.units = k->n;
+    p.ok = k->d_ok;
+    if (radix_bits == 8) {
+      p.chunks = k->comb_tab();
+      p.windows = kCombWindows;
+      p.entries = p.top_entries = kCombEntries;
+    } else if (radix_bits == kCombABits) {
+      if (k->comba.empty() || k->comba_n != k->n) return TMED_EINVAL;
+      p.chunks = k->comba_tab();
+      p.windows = kCombAWindows;
+      p.entries = kCombAEntries;
+      p.top_entries = kCombATopEntries;
+    } else {
+      return TMED_EINVAL;
+    }
+    p.step_bits = (uint32_t)radix_bits;
+    p.top_chain_last = p.top_entries - 1;
+    p.rows_per_unit = (uint64_t)(p.windows - 1) * p.entries + p.top_entries;
+  } else {
+    if (!b_table_plan(c, table, p)) return TMED_EINVAL;
+    if (corrupt_j != 0 && (table > 2 || corrupt_window >= p.windows || corrupt_j >= p.entries)) return TMED_EINVAL;
+  }
+  (void)hipSetDevice(c->device);
+  // the builds are queued on the context stream / the key worker's stream: drain both first
+  if (hipStreamSynchronize(c->stream) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return TMED_EHIP;
+  uint64_t *d_out = nullptr;
+  int4 *copy = nullptr;
+  uint64_t h[18] = {0};
+  hipError_t e = hipMalloc((void **)&d_out, sizeof h);
+  if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, sizeof h, c->stream);
+  if (e == hipSuccess && corrupt_j != 0) {  // the negative control: check a copy with one row off by one
+    const size_t bytes = (size_t)p.rows_per_unit * kCombEntryInt4 * 16;
+    e = hipMalloc((void **)&copy, bytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(copy, p.base, bytes, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess)
+      e = launch_table_corrupt(copy + ((size_t)corrupt_window * p.entries + corrupt_j) * kCombEntryInt4, c->stream);
+    p.base = copy;
+  }
+  if (e == hipSuccess) e = launch_table_chain(p, d_out, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(h, d_out, sizeof h, hipMemcpyDeviceToHost, c->stream);
+  const hipError_t es = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess) e = es;
+  if (d_out) (void)hipFree(d_out);
+  if (copy) (void)hipFree(copy);
+  if (e != hipSuccess) return map_err(e);
+  *rows = h[0];
+  *n_bad = h[1];
+  for (int i = 0; i < 16; i++) first_bad[i] = h[2 + i];
+  return TMED_OK;
+}
+
 int tmed_sign_batch_device(tmed_ctx *c, const uint8_t *d_seeds, const uint8_t *d_msgs, const uint32_t *d_off,
                            size_t n, uint8_t *d_sig_out, uint8_t *d_pub_out, void *stream) {
   if (!c) return TMED_EINVAL;

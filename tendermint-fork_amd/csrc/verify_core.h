@@ -554,6 +554,21 @@ TMED_HD void ge_p3_to_niels(ge_niels &out, const ge_p3 &p) {
   fe_mul(out.XY2d, xy, d2);
 }
 
+// (x, y) affine niels (y+x, y-x, 2dxy) -> extended (4x : 4y : 4 : 4xy): X = 2(a - b), Y = 2(a + b),
+// T = (a - b)(a + b) with a = y+x, b = y-x.
+TMED_HD void ge_niels_to_p3(ge_p3 &r, const ge_niels &e) {
+  fe d, s;
+  fe_sub(d, e.YpX, e.YmX);
+  fe_add(s, e.YpX, e.YmX);
+  fe_mul(r.T, d, s);
+  fe_add(r.X, d, d);
+  fe_carry(r.X, r.X);  // the next addition's Y +- X must stay a 3-sum of carried values
+  fe_add(r.Y, s, s);
+  fe_carry(r.Y, r.Y);
+  fe_0(r.Z);
+  r.Z.v[0] = 4;
+}
+
 // out = j * base (j in 1..255) in niels form; branch-free double-and-add.
 TMED_HD void comb_entry(ge_niels &out, const ge_p3 &base, uint32_t j, int nbits = 8) {
   ge_cached cP;

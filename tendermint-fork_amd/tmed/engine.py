@@ -314,5 +314,27 @@ class Engine:
             raise TmedError(rc, "tmed_keyset_comb_entry")
         return out
 
+    def b_table_entry(self, table: int, window: int, j: int) -> np.ndarray:
+        """Tests: one row of a B table as its 30 int32 limbs (tmed_test_b_table_entry; table 0 the
+        radix-256 comb, 1 the radix-2^16 table, 2 the radix-2^16 comb, 3 radix 2^26, 4 radix 2^24)."""
+        out = np.zeros(30, np.int32)
+        rc = lib().tmed_test_b_table_entry(self._h, table, window, j, out.ctypes.data)
+        if rc != 0:
+            raise TmedError(rc, "tmed_test_b_table_entry")
+        return out
+
+    def table_chain(self, table: int = 0, handle: int = 0, radix_bits: int = 0, corrupt=None):
+        """Tests: the chain check of a whole B table, or of every key's comb of a key set
+        (tmed_test_table_chain) -> (rows checked, rows that fail, [(window, j)] of up to 16 of them).
+        corrupt = (window, j): check a copy with that row one off instead (tables 0..2)."""
+        rows, bad = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        first = np.zeros(16, np.uint64)
+        cw, cj = corrupt if corrupt is not None else (0, 0)
+        rc = lib().tmed_test_table_chain(self._h, table, handle, radix_bits, cw, cj, ctypes.byref(rows),
+                                         ctypes.byref(bad), first.ctypes.data)
+        if rc != 0:
+            raise TmedError(rc, "tmed_test_table_chain")
+        return rows.value, bad.value, [(int(v) >> 32, int(v) & 0xffffffff) for v in first[:min(bad.value, 16)]]
+
     def last_kernel_ms(self) -> float:
         return float(lib().tmed_last_kernel_ms(self._h))

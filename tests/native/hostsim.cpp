@@ -251,6 +251,16 @@ int hostsim_halfsize_tight(const uint8_t *k32, uint8_t *c32, uint8_t *d32, int *
   return hostsim_halfsize_impl(k32, c32, d32, dneg, fast, tight);
 }
 
+// The radix-2^26 digits of e (hs_b26_digits) at a chosen e: the half-size path's e = d S mod L
+// cannot be chosen end to end (tests/test_scalar_edges_host.py).
+void hostsim_b26_digits(const uint8_t *e32, int32_t *dl, int32_t *dh) {
+  uint32_t er[8];
+  load_words8(er, e32);
+  int l[5], h[5];
+  hs_b26_digits(l, h, er);
+  for (int m = 0; m < 5; m++) { dl[m] = l[m]; dh[m] = h[m]; }
+}
+
 void hostsim_verify_batch(const uint8_t *pub, const uint8_t *sig, const uint8_t *msgs, const uint32_t *off,
                           size_t n, uint8_t *out) {
   hostsim_verify_batch_g(pub, sig, msgs, off, n, out, 16);
