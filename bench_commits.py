@@ -20,6 +20,11 @@
                 validators and 10,000 x 175, all aligned, one tmed_median_times call per shape: calls/s
                 and the selection kernels' device time, the same pairs through tmed_median_times_host
                 on one thread, and tmed_verify_commits (VerifyCommit) over the same commits for scale.
+  --config votes  free-standing votes: one round's prevotes and precommits (2 x 10,000 against a
+                10,000-validator set, and 2 x 175) through tmed_verify_votes (VoteSet.addVote's checks and
+                Vote.Verify on the device), beside the route there was before (the sign-bytes of every vote
+                on the host, then tmed_verify_batch_keyset) and oracle.port on one thread, in one run:
+                votes/s, vote_prepare_kernel's device time, the call's host share.
 Synthetic data (seeded keys, GPU RFC 8032 signer); prints one JSON line per config.
 """
 from __future__ import annotations
@@ -1066,6 +1071,100 @@ def mt(eng, runs: int, shapes=((1000, 10_000), (10_000, 175))):
     return {"config": "mt", "metric": "state.MedianTime per window, device vs host vs VerifyCommit", "runs": runs, "shapes": out}
 
 
+def votes(eng, runs: int, cpu: bool, shapes=(10_000, 175)):
+    """One round of free-standing votes per shape: nvals prevotes and nvals precommits at one step
+    against an nvals-validator set held as an explicit key set (the key-cached kernels on both routes).
+      new   one tmed_verify_votes call over both requests (TMED_VOTES_ADDVOTE);
+      old   tmed_votes_sign_bytes for every vote on the host (standing in for the sign-bytes a node
+            builds in Go), then one tmed_verify_batch_keyset call over the 2 x nvals tuples: no
+            address checks, no error kinds;
+      cpu   oracle.port's verify over the same tuples on one thread.
+    Every 97th vote carries a flipped signature byte; the three routes must agree on every vote.
+    Medians of `runs` timed calls."""
+    import tmed.votes as V
+    from tmed import pack_messages
+    from tmed.workload import make_valset, pubkeys_of, seeds_from_tag
+    med = lambda xs: float(np.median(xs))
+    chain, height, rnd = "test_chain_id", 1_000_000, 1
+    out = []
+    for nvals in shapes:
+        seeds = seeds_from_tag(b"tmed-votes-key", 0, nvals)
+        pubs = pubkeys_of(eng, seeds)
+        vals, order = make_valset(pubs, [10] * nvals)
+        vpubs, _, vaddrs = vals.packed()
+        handle = eng.keyset_load(vpubs[:nvals])
+        vals.keyset = handle
+        bid = block_id(b"votes-%d" % nvals)
+        idx = np.arange(nvals)
+        packed = []
+        for type_ in (1, 2):
+            packed.append(V.PackedVotes.from_arrays(
+                types=np.full(nvals, type_), heights=np.full(nvals, height), rounds=np.full(nvals, rnd),
+                block_hashes=np.tile(np.frombuffer(bid.hash, np.uint8), (nvals, 1)), block_hash_lens=np.full(nvals, 32),
+                psh_totals=np.full(nvals, bid.psh_total), psh_hashes=np.tile(np.frombuffer(bid.psh_hash, np.uint8), (nvals, 1)),
+                psh_hash_lens=np.full(nvals, 32), ts_seconds=T2023 + idx // 1000 + type_, ts_nanos=(idx % 1000) * 1_000_000,
+                addresses=vaddrs[:nvals], address_lens=np.full(nvals, 20), validator_indexes=idx,
+                sigs=np.zeros((nvals, 64), np.uint8), sig_lens=np.full(nvals, 64)))
+        # sign every vote over its own sign-bytes (the GPU signer), then flip a byte of every 97th
+        for pv in packed:
+            msgs = V.sign_bytes(chain, pv)
+            flat, off = pack_messages(msgs)
+            sigs, _ = eng.sign_arrays(seeds[order], np.concatenate([flat, np.zeros(16, np.uint8)]), off)
+            pv.sigs[:] = sigs
+            pv.sigs[::97, 5] ^= 1
+        reqs = [V.VoteRequest(chain, vals, packed[0], True, height, rnd, 1),
+                V.VoteRequest(chain, vals, packed[1], True, height, rnd, 2)]
+        n = 2 * nvals
+        prep = V.PreparedVotes(reqs)
+        prep.run(eng)  # warm: the staging buffers are allocated
+        wall, dev, pdev = [], [], []
+        for _ in range(runs):
+            t0 = time.perf_counter()
+            codes = prep.run(eng)
+            wall.append(time.perf_counter() - t0)
+            dev.append(eng.last_kernel_ms())
+            pdev.append(V.last_prepare_ms(eng))
+        codes = codes.copy()
+        want_bad = np.zeros(n, bool)
+        want_bad[:nvals][::97] = True
+        want_bad[nvals:][::97] = True
+        assert ((codes == V.VOTE_INVALID_SIGNATURE) == want_bad).all() and ((codes == V.VOTE_OK) == ~want_bad).all()
+        # the route there was before
+        all_sigs = np.concatenate([packed[0].sigs, packed[1].sigs])
+        vidx = np.concatenate([idx, idx]).astype(np.uint32)
+        old_wall, old_sb, old_dev = [], [], []
+        for _ in range(runs):
+            t0 = time.perf_counter()
+            (f0, o0, _), (f1, o1, _) = V.sign_bytes_arrays(chain, packed[0]), V.sign_bytes_arrays(chain, packed[1])
+            flat = np.concatenate([f0, f1, np.zeros(16, np.uint8)])
+            off = np.concatenate([o0, o1[1:] + o0[-1]]).astype(np.uint32)
+            t1 = time.perf_counter()
+            bits = eng.verify_keyset_arrays(handle, vidx, all_sigs, flat, off)
+            old_wall.append(time.perf_counter() - t0)
+            old_sb.append(t1 - t0)
+            old_dev.append(eng.last_kernel_ms())
+        assert ((codes == V.VOTE_OK) == bits.astype(bool)).all(), "tmed_verify_votes and the old route disagree"
+        r = {"validators": nvals, "votes": n, "invalid": int(want_bad.sum()),
+             "verify_votes_ms": round(med(wall) * 1e3, 3), "verify_votes_per_s": round(n / med(wall), 1),
+             "kernels_ms": round(med(dev), 4), "vote_prepare_kernel_ms": round(med(pdev), 4),
+             "host_share": round(1.0 - med(dev) * 1e-3 / med(wall), 3),
+             "old_route_ms": round(med(old_wall) * 1e3, 3), "old_route_votes_per_s": round(n / med(old_wall), 1),
+             "old_route_sign_bytes_ms": round(med(old_sb) * 1e3, 3), "old_route_kernels_ms": round(med(old_dev), 4),
+             "decisions_equal": True}
+        if cpu:
+            from oracle import port
+            both = np.concatenate([vpubs[:nvals], vpubs[:nvals]])
+            t0 = time.perf_counter()
+            exp = port.verify_batch(both, all_sigs, flat, off.astype(np.uint64), 1)
+            t_cpu = time.perf_counter() - t0
+            assert (exp.astype(bool) == bits.astype(bool)).all(), "device and oracle.port disagree"
+            r.update({"cpu_1thread_ms": round(t_cpu * 1e3, 2), "cpu_1thread_votes_per_s": round(n / t_cpu, 1)})
+        eng.keyset_free(handle)
+        out.append(r)
+    return {"config": "votes", "metric": "free-standing votes per second: tmed_verify_votes vs host sign-bytes + "
+            "tmed_verify_batch_keyset vs oracle.port on one thread", "runs": runs, "shapes": out}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="c1,c3,c4")
@@ -1105,6 +1204,8 @@ def main():
             r = c3v(eng, args.headers, args.gap, args.c3_policy, args.runs)
         elif cfg == "mt" and rank == 0:
             r = mt(eng, args.runs)
+        elif cfg == "votes" and rank == 0:
+            r = votes(eng, args.runs, not args.no_cpu)
         elif cfg == "c4":
             r = c4(eng, args.blocks, args.validators, rank, world, coll, args.window, args.batch, args.corrupt_every,
                        args.pregen, not args.no_pinned, args.c4_policy, not args.no_stream)

@@ -802,6 +802,112 @@ typedef struct {
 int tmed_median_times(tmed_ctx *ctx, const tmed_median_request *reqs, size_t n, tmed_median_result *out);
 int tmed_median_times_host(const tmed_median_request *reqs, size_t n, tmed_median_result *out);
 
+/* ------------------------------------------------- free-standing votes */
+
+/*
+ * Vote.Verify (types/vote.go:147-156) and the checks VoteSet.addVote runs in front of it
+ * (types/vote_set.go:156-218) for batches of free-standing votes: a drained peerMsgQueue, the
+ * last commit rebuilt by CommitToVoteSet (types/block.go:767), a WAL replay, the two votes of
+ * every DuplicateVoteEvidence of a block (evidence/verify.go:211-219).  Unlike a Commit's, these
+ * votes share nothing: each carries its own type, height, round, BlockID and timestamp.
+ *
+ * tmed_votes: n votes as flat arrays (a cgo caller fills them in place).  A hash longer than 32
+ * bytes or an address longer than 20 is described by its length alone; the slot's bytes are ignored.
+ */
+typedef struct {
+  size_t n;
+  const int32_t *types;            /* SignedMsgType (any int32: the encoding is the reference's for every value) */
+  const int64_t *heights;
+  const int32_t *rounds;
+  const uint8_t *block_hashes;     /* n x 32 */
+  const uint32_t *block_hash_lens; /* NULL = all 32; else len(BlockID.Hash) */
+  const uint32_t *psh_totals;      /* BlockID.PartSetHeader.Total */
+  const uint8_t *psh_hashes;       /* n x 32 */
+  const uint32_t *psh_hash_lens;   /* NULL = all 32 */
+  const int64_t *ts_seconds;       /* Timestamp.Unix() */
+  const int32_t *ts_nanos;         /* Timestamp.Nanosecond() */
+  const uint8_t *addresses;        /* n x 20 ValidatorAddress */
+  const uint32_t *address_lens;    /* NULL = all 20 */
+  const int32_t *validator_indexes;
+  const uint8_t *sigs;             /* n x 64 (first sig_lens[i] bytes meaningful) */
+  const uint32_t *sig_lens;        /* NULL = all 64 */
+} tmed_votes;
+
+#define TMED_VOTES_ADDVOTE 1u /* flags: the checks of VoteSet.addVote (2, 3 and 5 below) in front of Vote.Verify */
+
+typedef struct {
+  const char *chain_id;
+  uint32_t chain_id_len;
+  const tmed_valset *vals;  /* the VoteSet's valSet; keyset 0 = the key-set cache decides, as for commits.
+                               `addresses` is read under TMED_VOTES_ADDVOTE only (NULL otherwise); `powers`
+                               and `total_power` are not read */
+  const tmed_votes *votes;
+  uint32_t flags;
+  int64_t height;           /* TMED_VOTES_ADDVOTE: voteSet.height, .round, .signedMsgType */
+  int32_t round;
+  int32_t msg_type;
+} tmed_vote_request;
+
+/* One outcome per vote: the FIRST check that fails, in the reference's order. */
+#define TMED_VOTE_OK 0
+#define TMED_VOTE_INDEX_NEGATIVE 1      /* "index < 0: %w" ErrVoteInvalidValidatorIndex (types/vote_set.go:165-166) */
+#define TMED_VOTE_ADDRESS_EMPTY 2       /* ADDVOTE: "empty address: %w" ErrVoteInvalidValidatorAddress (:167-168) */
+#define TMED_VOTE_UNEXPECTED_STEP 3     /* ADDVOTE: height, round or type differ from the VoteSet's: ErrVoteUnexpectedStep
+                                           (:172-178) */
+#define TMED_VOTE_INDEX_NOT_IN_SET 4    /* GetByIndex finds no validator (validator_index >= vals->n):
+                                           ErrVoteInvalidValidatorIndex (:181-186) */
+#define TMED_VOTE_ADDRESS_NOT_IN_SET 5  /* ADDVOTE: !bytes.Equal(valAddr, lookupAddr), any length but 20 included:
+                                           ErrVoteInvalidValidatorAddress (:189-194) */
+#define TMED_VOTE_ADDRESS_NOT_OF_KEY 6  /* Vote.Verify: pubKey.Address() = SHA-256(key)[:20] differs from the vote's
+                                           address: ErrVoteInvalidValidatorAddress (types/vote.go:148-150,
+                                           crypto/ed25519/ed25519.go:136-141) */
+#define TMED_VOTE_PANIC 7               /* VoteSignBytes panics: a BlockID hash or part-set hash whose length is
+                                           neither 0 nor 32 (CanonicalizeBlockID, types/canonical.go:19-22).  Only
+                                           when no earlier check fails; the caller runs the original Go path, which
+                                           panics exactly as before */
+#define TMED_VOTE_INVALID_SIGNATURE 8   /* ErrVoteInvalidSignature (types/vote.go:152-154); a signature of any length
+                                           but 64 included (crypto/ed25519/ed25519.go:150-152) */
+#define TMED_VOTE_GO_PATH 9             /* the structs do not determine the reference's outcome: a timestamp outside
+                                           google.protobuf.Timestamp's range (seconds in [-62135596800,
+                                           253402300800), nanos in [0, 1e9)), which StdTimeMarshal refuses (VoteSignBytes
+                                           then panics, types/vote.go:95-98).  Only when no earlier check fails; the
+                                           caller runs the original Go path for this vote */
+
+/*
+ * codes[k]: the outcome of vote k, request r's votes starting at the sum of the vote counts of the
+ * requests before it.  All requests go to the device as ONE batch: vote_prepare_kernel
+ * (csrc/votes.hip) runs the checks 1-7 one lane per vote and writes each vote's sign-bytes, the
+ * verify kernels of the commit seam (key-cached when the set resolves to a key set, generic
+ * otherwise) decide the signatures.  The duplicate lookup of vote_set.go:197-202, between checks 5
+ * and 6 in the reference, reads the VoteSet's state: it stays in Go, as do conflicting votes, maj23
+ * and addVerifiedVote.  A request whose chain ID is longer than 50 bytes (MaxChainIDLen) has its
+ * messages assembled on the host by the same source; decisions are identical.
+ * Submitted blocksync windows are collected first, as by every seam call.  After the call
+ * tmed_last_kernel_ms reports vote_prepare_kernel's device time plus the verify kernels'.
+ * TMED_EINVAL for malformed calls only (a NULL array with n > 0, NULL vals, NULL vals->pubkeys with
+ * vals->n > 0, NULL vals->addresses under ADDVOTE, a keyset_index past the key set).
+ */
+int tmed_verify_votes(tmed_ctx *ctx, const tmed_vote_request *reqs, size_t n_reqs, uint8_t *codes);
+/* vote_prepare_kernel's share of tmed_last_kernel_ms after tmed_verify_votes (benches). */
+float tmed_votes_last_prepare_ms(tmed_ctx *ctx);
+
+/*
+ * Host entries, no device and no context (csrc/votes_host.h over csrc/vote_free.h, the source the
+ * kernel compiles):
+ * tmed_votes_sign_bytes: VoteSignBytes(chainID, vote) of the n votes, message i at
+ *   out[out_off[i] .. out_off[i+1]) (sizing and TMED_ENOMEM as tmed_vote_sign_bytes).  A vote whose
+ *   BlockID is malformed encodes nothing (an empty range) and sets malformed[i] = 1; with malformed
+ *   NULL such a vote is TMED_EINVAL.
+ * tmed_verify_votes_host: the checks in front of the signature for every vote of the requests, lane
+ *   by lane: codes[k] = the first failing check, 0 where the signature would decide; msg_lens[k]
+ *   (nullable) = the length of the vote's sign-bytes (0 where a check fails); device_route[r]
+ *   (nullable) = 1 when tmed_verify_votes assembles request r's messages on the device.
+ */
+int tmed_votes_sign_bytes(const char *chain_id, uint32_t chain_id_len, const tmed_votes *votes, uint8_t *out,
+                          size_t out_cap, uint32_t *out_off, size_t *out_len, uint8_t *malformed);
+int tmed_verify_votes_host(const tmed_vote_request *reqs, size_t n_reqs, uint8_t *codes, uint32_t *msg_lens,
+                           uint8_t *device_route);
+
 /* ------------------------------------------------- blocksync replay (f4) */
 
 /*

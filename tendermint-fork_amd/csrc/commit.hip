@@ -35,6 +35,7 @@
 #include "ctx.h"
 #include "host_pool.h"
 #include "signbytes.h"
+#include "votes_host.h"
 
 // One translation unit, by role (each header is included here only, in this order):
 //   seam_host.h   planning, aliasing, staging groups, scatter, replay: host C++ only
@@ -335,6 +336,43 @@ extern "C" int tmed_light_verify(tmed_ctx *ctx, const tmed_light_request *reqs, 
         [&](const tmed_commit_request *rq, size_t m, tmed_commit_result *res) {
           return verify_commits_impl(ctx, rq, m, res);
         });
+  });
+}
+
+// ---- free-standing votes: Vote.Verify and the checks of VoteSet.addVote (votes.hip) ---------------
+// The requests' sets go through the key-set cache as a commit's do: each request stands in as a
+// commit request of as many signatures as it has votes (the cache reads the set and that count only),
+// and the device batch runs against the sets the cache resolved.
+extern "C" int tmed_verify_votes(tmed_ctx *ctx, const tmed_vote_request *reqs, size_t n_reqs, uint8_t *codes) {
+  if (!ctx || (n_reqs && !reqs)) return TMED_EINVAL;
+  return c_guard(ctx, [&] {
+    size_t total = 0;
+    for (size_t q = 0; q < n_reqs; q++) {
+      if (tmed_votes_host::check_request(reqs[q]) != TMED_OK) return (int)TMED_EINVAL;
+      total += reqs[q].votes->n;
+    }
+    if (total && !codes) return (int)TMED_EINVAL;
+    int rc;
+    {
+      std::vector<tmed_commit> shadow_commits(n_reqs);
+      std::vector<tmed_commit_request> shadow(n_reqs);
+      for (size_t q = 0; q < n_reqs; q++) {
+        memset(&shadow_commits[q], 0, sizeof(tmed_commit));
+        memset(&shadow[q], 0, sizeof(tmed_commit_request));
+        shadow_commits[q].n_sigs = reqs[q].votes->n;
+        shadow[q].vals = reqs[q].vals;
+        shadow[q].commit = &shadow_commits[q];
+      }
+      KcCall kc;  // pins the cache's pool until the batch below is collected
+      const tmed_commit_request *resolved = keycache_resolve(ctx, shadow.data(), n_reqs, kc);
+      std::vector<tmed_vote_request> rq(reqs, reqs + n_reqs);
+      for (size_t q = 0; q < n_reqs; q++) rq[q].vals = resolved[q].vals;
+      std::lock_guard<std::mutex> lk(ctx->mu);
+      rc = bs_drain(ctx);  // the seam's rule: submitted blocksync windows first
+      if (rc == TMED_OK) rc = tmed::verify_votes_locked(ctx, rq.data(), n_reqs, codes);
+    }
+    bs_reap(ctx);
+    return rc;
   });
 }
 

@@ -129,6 +129,13 @@ int valset_hashes_locked(tmed_ctx *c, const uint8_t *pubkeys, const int64_t *pow
 int valsets_hashes_locked(tmed_ctx *c, const tmed_valset *const *sets, size_t n_sets, uint8_t *out);
 // median.hip: tmed_median_times over n checked requests (median_host.h check_request); ctx->mu held.
 int median_times_locked(tmed_ctx *c, const tmed_median_request *reqs, size_t n, tmed_median_result *out);
+// votes.hip: tmed_verify_votes over n checked requests (votes_host.h check_request) whose sets the
+// key-set cache has resolved; ctx->mu held.
+int verify_votes_locked(tmed_ctx *c, const tmed_vote_request *reqs, size_t n, uint8_t *codes);
+// keyset.hip: a key-cached batch of device-resident tuples on stream s, as the commit seam runs it
+// (latency kernels up to lat_max, the throughput kernels above); inside a scratch_acquire/release pair.
+hipError_t keyset_verify_batch(tmed_ctx *c, Keyset &k, const uint32_t *d_idx, const uint8_t *d_sig, const uint8_t *d_msgs,
+                               const uint32_t *d_off, uint32_t n, uint8_t *d_out, hipStream_t s, bool msg_slots);
 struct Lane;
 void lane_release(Lane &L);    // keyset.hip: the second kernel lane's stream and scratch
 bool lanes_on();               // keyset.hip: TMED_LANES != 1
@@ -306,6 +313,13 @@ struct tmed_ctx {
   // kind (pinned) and their device copy, plus the outcomes.  Its own buffers, as h_csig / d_csig.
   tmed::HostBuf h_med;
   tmed::DevBuf d_med;
+  // tmed_verify_votes (votes.hip): the votes' records, the requests' steps and set addresses, keys and
+  // signatures (pinned) and their device copy, plus the slots, lengths, codes and validity bits.  Its
+  // own buffers, as h_csig / d_csig.  vote_ev: the end of vote_prepare_kernel (last_vote_prep_ms).
+  tmed::HostBuf h_vfree;
+  tmed::DevBuf d_vfree;
+  hipEvent_t vote_ev = nullptr;
+  float last_vote_prep_ms = 0.f;
   tmed::DevBuf d_korder;  // key-grouped order of a key-cached batch: counts / cursors + permutation
   tmed::DevBuf d_zip;     // ZIP-215 batch mode scratch (zip215.hip zip_bufs: points, digits, sort, buckets)
   bool zip_dense = false; // ZIP-215: the last large chunk had failures (zip215.hip: decide the next one singly first)

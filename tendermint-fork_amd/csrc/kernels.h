@@ -235,4 +235,23 @@ hipError_t launch_assemble_votes(const uint8_t *tmpl, const uint32_t *tmpl_idx, 
                                  const int64_t *ts_sec, const int32_t *ts_nanos, uint32_t n, uint8_t *out,
                                  uint32_t *out_len, hipStream_t stream);
 
+
+// Free-standing votes (votes.hip vote_prepare_kernel; vote_free.h holds the record layouts and the
+// checks): one lane per vote stages its VoteRec, runs the checks of VoteSet.addVote / Vote.Verify in
+// front of the signature and writes the vote's sign-bytes into its kVoteSlot-byte slot, the length
+// (0 where a check fails) and the precheck code.  The verify launchers above then read the slots in
+// their msg_slots mode (off = lens).
+struct VoteStep;
+struct VotePrep {
+  const int4 *recs;          // n VoteRec records (nine 16-byte rows each)
+  const VoteStep *steps;     // the call's requests (VoteRec::req)
+  const uint8_t *set_addr;   // the requests' set addresses, packed (VoteStep::addr_base; ADDVOTE)
+  const uint8_t *pubs;       // generic route: n x 32, the key at each vote's validator index
+  const uint8_t *key_pub;    // keyed route (pubs == nullptr): the key set's encodings (VoteRec::key)
+  uint8_t *slots;            // n x kVoteSlot
+  uint32_t *lens;            // n
+  uint8_t *codes;            // n
+};
+hipError_t launch_vote_prepare(const VotePrep &p, uint32_t n, hipStream_t stream);
+
 }  // namespace tmed

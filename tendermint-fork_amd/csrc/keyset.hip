@@ -302,6 +302,11 @@ static hipError_t keyset_verify(tmed_ctx *c, Keyset &k, const uint32_t *d_idx, c
                               comba);
 }
 
+hipError_t keyset_verify_batch(tmed_ctx *c, Keyset &k, const uint32_t *d_idx, const uint8_t *d_sig, const uint8_t *d_msgs,
+                               const uint32_t *d_off, uint32_t n, uint8_t *d_out, hipStream_t s, bool msg_slots) {
+  return keyset_verify(c, k, d_idx, d_sig, d_msgs, d_off, n, d_out, s, msg_slots);
+}
+
 static std::atomic<uint32_t> g_test_stream_delay{0};
 uint32_t test_stream_delay_us() { return g_test_stream_delay.load(std::memory_order_relaxed); }
 

@@ -229,11 +229,13 @@ void tmed_destroy(tmed_ctx *c) {
   for (DevBuf *b : {&c->d_a, &c->d_b, &c->d_msg, &c->d_off, &c->d_out, &c->d_c}) b->release();
   for (HostBuf *b : {&c->h_a, &c->h_b, &c->h_msg, &c->h_off, &c->h_out, &c->h_c}) b->release();
   for (DevBuf *b : {&c->d_merkle_lv, &c->d_merkle_tab, &c->d_proof_off, &c->d_proof_out, &c->d_proof_in, &c->d_korder,
-                    &c->d_zip, &c->d_kbases, &c->d_csig, &c->d_hdr, &c->d_med})
+                    &c->d_zip, &c->d_kbases, &c->d_csig, &c->d_hdr, &c->d_med, &c->d_vfree})
     b->release();
   c->h_csig.release();
   c->h_hdr.release();
   c->h_med.release();
+  c->h_vfree.release();
+  if (c->vote_ev) hipEventDestroy(c->vote_ev);
   c->h_kup.release();
   if (c->kup_ev) hipEventDestroy(c->kup_ev);
   c->h_zip.release();

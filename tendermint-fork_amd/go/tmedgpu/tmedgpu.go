@@ -1474,3 +1474,178 @@ func (e *Engine) MedianTimes(reqs []MedianRequest) ([]MedianResult, error) {
 	}
 	return out, nil
 }
+
+// ---- Vote.Verify and the checks of VoteSet.addVote (types/vote.go:147-156, vote_set.go:156-218) ----
+
+// Outcome codes of VerifyVotes: the first check that fails, in the reference's order (see
+// tmed25519.h, which cites the reference line of each).
+const (
+	VoteOK = C.TMED_VOTE_OK
+	// VoteIndexNegative / VoteIndexNotInSet: addVote wraps ErrVoteInvalidValidatorIndex.
+	VoteIndexNegative = C.TMED_VOTE_INDEX_NEGATIVE
+	// VoteAddressEmpty / VoteAddressNotInSet / VoteAddressNotOfKey: ErrVoteInvalidValidatorAddress.
+	VoteAddressEmpty = C.TMED_VOTE_ADDRESS_EMPTY
+	// VoteUnexpectedStep: ErrVoteUnexpectedStep.
+	VoteUnexpectedStep  = C.TMED_VOTE_UNEXPECTED_STEP
+	VoteIndexNotInSet   = C.TMED_VOTE_INDEX_NOT_IN_SET
+	VoteAddressNotInSet = C.TMED_VOTE_ADDRESS_NOT_IN_SET
+	VoteAddressNotOfKey = C.TMED_VOTE_ADDRESS_NOT_OF_KEY
+	// VotePanic: VoteSignBytes panics (a malformed BlockID hash); the caller runs the original Go
+	// path, which panics as before.
+	VotePanic = C.TMED_VOTE_PANIC
+	// VoteInvalidSignature: ErrVoteInvalidSignature.
+	VoteInvalidSignature = C.TMED_VOTE_INVALID_SIGNATURE
+	// VoteGoPath: the flat fields do not determine the reference's outcome (a timestamp outside the
+	// proto Timestamp range): the caller runs the original Go path for this vote.
+	VoteGoPath = C.TMED_VOTE_GO_PATH
+)
+
+// VoteData is a flat copy of n free-standing types.Vote values (filled by the caller in package
+// types).  Hashes and addresses sit in fixed slots; the *Lens arrays give the real lengths.
+type VoteData struct {
+	Types            []int32
+	Heights          []int64
+	Rounds           []int32
+	BlockHashes      []byte   // n x 32
+	BlockHashLens    []uint32 // len(BlockID.Hash)
+	PSHTotals        []uint32
+	PSHHashes        []byte   // n x 32
+	PSHHashLens      []uint32
+	TsSeconds        []int64
+	TsNanos          []int32
+	Addresses        []byte   // n x 20
+	AddrLens         []uint32 // len(ValidatorAddress)
+	ValidatorIndexes []int32
+	Sigs             []byte   // n x 64 (zero padded)
+	SigLens          []uint32
+	cmem             bool // every array already lives in C memory (Batch.NewVotes)
+}
+
+// NewVoteData: a VoteData of n votes in Go memory (copied into the call's arena once).
+func NewVoteData(n int) *VoteData {
+	return &VoteData{Types: make([]int32, n), Heights: make([]int64, n), Rounds: make([]int32, n),
+		BlockHashes: make([]byte, 32*n), BlockHashLens: make([]uint32, n), PSHTotals: make([]uint32, n),
+		PSHHashes: make([]byte, 32*n), PSHHashLens: make([]uint32, n), TsSeconds: make([]int64, n),
+		TsNanos: make([]int32, n), Addresses: make([]byte, 20*n), AddrLens: make([]uint32, n),
+		ValidatorIndexes: make([]int32, n), Sigs: make([]byte, 64*n), SigLens: make([]uint32, n)}
+}
+
+// NewVotes: a VoteData of n votes whose arrays are allocated in the batch's C memory, for the caller
+// to fill in place (as Batch.NewCommit).
+func (b *Batch) NewVotes(n int) *VoteData {
+	a := b.a
+	v := &VoteData{cmem: true}
+	v.Types = unsafe.Slice((*int32)(a.alloc(uintptr(4*n))), n)
+	v.Heights = unsafe.Slice((*int64)(a.alloc(uintptr(8*n))), n)
+	v.Rounds = unsafe.Slice((*int32)(a.alloc(uintptr(4*n))), n)
+	v.BlockHashes = unsafe.Slice((*byte)(a.alloc(uintptr(32*n))), 32*n)
+	v.BlockHashLens = unsafe.Slice((*uint32)(a.alloc(uintptr(4*n))), n)
+	v.PSHTotals = unsafe.Slice((*uint32)(a.alloc(uintptr(4*n))), n)
+	v.PSHHashes = unsafe.Slice((*byte)(a.alloc(uintptr(32*n))), 32*n)
+	v.PSHHashLens = unsafe.Slice((*uint32)(a.alloc(uintptr(4*n))), n)
+	v.TsSeconds = unsafe.Slice((*int64)(a.alloc(uintptr(8*n))), n)
+	v.TsNanos = unsafe.Slice((*int32)(a.alloc(uintptr(4*n))), n)
+	v.Addresses = unsafe.Slice((*byte)(a.alloc(uintptr(20*n))), 20*n)
+	v.AddrLens = unsafe.Slice((*uint32)(a.alloc(uintptr(4*n))), n)
+	v.ValidatorIndexes = unsafe.Slice((*int32)(a.alloc(uintptr(4*n))), n)
+	v.Sigs = unsafe.Slice((*byte)(a.alloc(uintptr(64*n))), 64*n)
+	v.SigLens = unsafe.Slice((*uint32)(a.alloc(uintptr(4*n))), n)
+	return v
+}
+
+// votesC: the C struct of v (its arrays passed as they are when they live in C memory, else copied
+// into the arena once).
+func (a *arena) votesC(v *VoteData) C.tmed_votes {
+	n := len(v.Types)
+	t := C.tmed_votes{n: C.size_t(n)}
+	if n == 0 {
+		return t
+	}
+	if v.cmem {
+		t.types = (*C.int32_t)(unsafe.Pointer(&v.Types[0]))
+		t.heights = (*C.int64_t)(unsafe.Pointer(&v.Heights[0]))
+		t.rounds = (*C.int32_t)(unsafe.Pointer(&v.Rounds[0]))
+		t.block_hashes, t.psh_hashes = ptr8(v.BlockHashes), ptr8(v.PSHHashes)
+		t.block_hash_lens = (*C.uint32_t)(unsafe.Pointer(&v.BlockHashLens[0]))
+		t.psh_totals = (*C.uint32_t)(unsafe.Pointer(&v.PSHTotals[0]))
+		t.psh_hash_lens = (*C.uint32_t)(unsafe.Pointer(&v.PSHHashLens[0]))
+		t.ts_seconds = (*C.int64_t)(unsafe.Pointer(&v.TsSeconds[0]))
+		t.ts_nanos = (*C.int32_t)(unsafe.Pointer(&v.TsNanos[0]))
+		t.addresses, t.sigs = ptr8(v.Addresses), ptr8(v.Sigs)
+		t.address_lens = (*C.uint32_t)(unsafe.Pointer(&v.AddrLens[0]))
+		t.validator_indexes = (*C.int32_t)(unsafe.Pointer(&v.ValidatorIndexes[0]))
+		t.sig_lens = (*C.uint32_t)(unsafe.Pointer(&v.SigLens[0]))
+		return t
+	}
+	t.types, t.heights, t.rounds = a.i32(v.Types), a.i64(v.Heights), a.i32(v.Rounds)
+	t.block_hashes, t.block_hash_lens = a.bytes(v.BlockHashes), a.u32(v.BlockHashLens)
+	t.psh_totals, t.psh_hashes, t.psh_hash_lens = a.u32(v.PSHTotals), a.bytes(v.PSHHashes), a.u32(v.PSHHashLens)
+	t.ts_seconds, t.ts_nanos = a.i64(v.TsSeconds), a.i32(v.TsNanos)
+	t.addresses, t.address_lens = a.bytes(v.Addresses), a.u32(v.AddrLens)
+	t.validator_indexes = a.i32(v.ValidatorIndexes)
+	t.sigs, t.sig_lens = a.bytes(v.Sigs), a.u32(v.SigLens)
+	return t
+}
+
+// VoteRequest is one batch of votes against a validator set.  AddVote: the checks of
+// VoteSet.addVote against the VoteSet's step (Height, Round, Type) in front of Vote.Verify; else
+// Vote.Verify alone, with the key at each vote's ValidatorIndex.
+type VoteRequest struct {
+	ChainID string
+	Vals    *ValSet
+	Votes   *VoteData
+	AddVote bool
+	Height  int64
+	Round   int32
+	Type    int32
+}
+
+// VerifyVotes decides every vote of every request in ONE device batch (tmed_verify_votes) and
+// returns the Vote* outcome codes, one slice per request.  VoteSet's own state (duplicates,
+// conflicting votes, maj23) stays with the caller.  An error means "take the original Go path".
+func (e *Engine) VerifyVotes(reqs []VoteRequest) ([][]uint8, error) {
+	n := len(reqs)
+	if n == 0 {
+		return nil, nil
+	}
+	a := e.getArena()
+	defer e.putArena(a)
+	creqs := (*[1 << 24]C.tmed_vote_request)(a.alloc(uintptr(n) * unsafe.Sizeof(C.tmed_vote_request{})))[:n:n]
+	cv := (*[1 << 24]C.tmed_votes)(a.alloc(uintptr(n) * unsafe.Sizeof(C.tmed_votes{})))[:n:n]
+	vs := (*[1 << 24]C.tmed_valset)(a.alloc(uintptr(n) * unsafe.Sizeof(C.tmed_valset{})))[:n:n]
+	seenV := make(map[*ValSet]*C.tmed_valset, n)
+	total := 0
+	for i := range reqs {
+		r := &reqs[i]
+		if r.Vals == nil || r.Votes == nil {
+			return nil, errors.New("tmedgpu: VerifyVotes: nil votes or validator set")
+		}
+		set, ok := seenV[r.Vals]
+		if !ok {
+			vs[i] = a.valset(r.Vals)
+			set = &vs[i]
+			seenV[r.Vals] = set
+		}
+		cv[i] = a.votesC(r.Votes)
+		var flags C.uint32_t
+		if r.AddVote {
+			flags = C.TMED_VOTES_ADDVOTE
+		}
+		creqs[i] = C.tmed_vote_request{chain_id: a.cstring(r.ChainID), chain_id_len: C.uint32_t(len(r.ChainID)),
+			vals: set, votes: &cv[i], flags: flags, height: C.int64_t(r.Height), round: C.int32_t(r.Round),
+			msg_type: C.int32_t(r.Type)}
+		total += len(r.Votes.Types)
+	}
+	codes := make([]uint8, total+1)
+	if rc := C.tmed_verify_votes(e.ctx, &creqs[0], C.size_t(n), (*C.uint8_t)(unsafe.Pointer(&codes[0]))); rc != 0 {
+		return nil, errors.New(C.GoString(C.tmed_strerror(rc)))
+	}
+	out := make([][]uint8, n)
+	at := 0
+	for i := range reqs {
+		m := len(reqs[i].Votes.Types)
+		out[i] = codes[at : at+m : at+m]
+		at += m
+	}
+	return out, nil
+}

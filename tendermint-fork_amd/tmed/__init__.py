@@ -7,3 +7,4 @@ over the gfx950 C ABI in ``include/tmed25519.h``.
 from ._native import LIB_PATH, TmedError, lib  # noqa: F401
 from .engine import Engine, PinnedBuffer, pack_messages  # noqa: F401
 from .state import median_times  # noqa: F401
+from .votes import Vote, VoteRequest, verify_votes  # noqa: F401
