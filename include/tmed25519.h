@@ -298,6 +298,31 @@ int tmed_test_table_chain(tmed_ctx *ctx, int table, uint64_t handle, int radix_b
                           uint32_t corrupt_j, uint64_t *rows, uint64_t *n_bad, uint64_t first_bad[16]);
 
 /*
+ * Tests only (tests/test_gpu_zip_msm.py): the ZIP-215 batch mode's multi-scalar multiplication
+ * (csrc/zip215.hip zip_msm: the column sums of c, the two-pass sort, the bucket accumulation, the
+ * bucket weights, the wavefront reduction, the final check) on rows a caller gives, over the group
+ * [lo, lo + cnt) of a chunk of n <= 65536 signatures.  A small kernel writes the rows, digits and c
+ * into the context's ZIP-215 scratch in the layout the prep kernel writes; the call then runs the
+ * same launches on the same scratch as a group of tmed_verify_batch_zip215.
+ *
+ * points: 2n x 32-byte encodings, the n A rows then the n R rows, decoded permissively (as ZIP-215
+ * decodes R: y >= p and x = 0 with the sign bit accepted).  The row of a point P holds -P, as the
+ * product's rows hold -A and -R, so window w comes out as sum_i digits[w][i] (-P_i) over the rows
+ * lo .. lo + cnt - 1 and n + lo .. n + lo + cnt - 1.  digits: [16][2n] int16, signed radix-2^16
+ * digits taken as given: any value in windows 0..14 of an A row, 0..4097 in window 15; the R rows'
+ * digits of windows 8..15 are ignored.  c: n x 32 bytes, c_i as 8 little-endian words (the product's
+ * z_i S_i mod L).
+ *
+ * windows: 16 x 40 int32 out, window w's value as the limbs of X, Y, Z, T (10 each, radix 2^25.5)
+ * that the final kernel reads; ctot: sum of c_i mod L over the group, 8 words; *flag: 1 when
+ * [8](sum_w 2^(16 w) window_w + [ctot] B) is the identity, else 0.
+ * TMED_EINVAL: n, lo, cnt out of range, a window-15 A digit outside 0..4097, a row that does not
+ * decode.
+ */
+int tmed_test_zip_msm(tmed_ctx *ctx, uint32_t n, const uint8_t *points, const int16_t *digits, const uint8_t *c,
+                      uint32_t lo, uint32_t cnt, int32_t windows[640], uint32_t ctot[8], uint32_t *flag);
+
+/*
  * With TMED_DEBUG_ZERO set at the first pipelined generic batch: every staged candidate whose
  * device bit is 0 is recorded (request, signature, staging position, the staged and the device
  * copies of its key and signature, the assembled sign-bytes).  Copies up to cap records into out

@@ -27,9 +27,9 @@
 //                       two trees over shuffles, sum (d i S_i + T_i) -> one item; 3 levels in 2 launches
 //   zip_final_kernel    Horner over the 16 windows, + [sum z S] B (radix-2^16 comb), x8, = O?
 // A chunk whose equation fails is bisected (the same MSM over halves of its signatures, prep
-// data reused); a group that still fails is decided signature by signature by the exact ZIP-215
-// single check (the half-size kernels with a permissive R decode and a [8] before the identity
-// test).  Every accepted group is all-valid with probability >= 1 - 2^-125 per failing signature
+// data reused; the group bookkeeping is host code of its own, zip_plan.h); a group that still
+// fails is decided signature by signature by the exact ZIP-215 single check (the half-size kernels
+// with a permissive R decode and a [8] before the identity test).  Every accepted group is all-valid with probability >= 1 - 2^-125 per failing signature
 // (the z are secret); every rejected signature comes from the exact single check.
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -45,6 +45,7 @@
 #include "verify_core.h"
 #include "verify_hs.h"
 #include "quad.h"
+#include "zip_plan.h"
 
 namespace tmed {
 
@@ -731,6 +732,35 @@ __global__ __launch_bounds__(256) void zip_count_fail_kernel(const uint8_t *__re
   if ((threadIdx.x & 63u) == 0 && c) atomicAdd(cnt, c);
 }
 
+// Tests (tmed_test_zip_msm): the rows, digits and c of a chunk of N signatures, written where and
+// how zip_prep_r_kernel writes them.  Thread j < 2N: row j (A rows, then R rows) is the niels row
+// of -P for the point enc[j] decodes to (permissively, as R is); its 16 digits are copied as given;
+// threads j < N also copy c_j.  A row that does not decode is counted in *bad and left unwritten.
+__global__ __launch_bounds__(256) void zip_test_fill_kernel(const uint8_t *__restrict__ enc,
+                                                            const int16_t *__restrict__ din,
+                                                            const uint8_t *__restrict__ cin, uint32_t N,
+                                                            int4 *__restrict__ pts, int16_t *__restrict__ dig,
+                                                            int4 *__restrict__ cs, uint32_t cs_stride,
+                                                            uint32_t *__restrict__ bad) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t rows = 2 * (size_t)N;
+  if (j >= rows) return;
+  uint32_t w[8];
+  load_row_words(w, enc + 32 * (size_t)j, 2);
+  ge_p3 p;
+  if (!ge_frombytes_go(p, w)) {
+    atomicAdd(bad, 1u);
+    return;
+  }
+  niels_row_store(pts + (size_t)j * kZipRow, p.X, p.Y);
+  for (int wi = 0; wi < kZipWin; wi++) dig[(size_t)wi * rows + j] = din[(size_t)wi * rows + j];
+  if (j < N) {
+    load_row_words(w, cin + 32 * (size_t)j, 2);
+    cs[j] = make_int4((int)w[0], (int)w[1], (int)w[2], (int)w[3]);
+    cs[(size_t)cs_stride + j] = make_int4((int)w[4], (int)w[5], (int)w[6], (int)w[7]);
+  }
+}
+
 }  // namespace tmed
 
 // ================================================================ host orchestration
@@ -904,33 +934,22 @@ int zip215_verify_device(tmed_ctx *c, const uint8_t *pub, const uint8_t *sig, co
                        c->slab_slots, z.seed, (uint64_t)base, z.pts, z.dig, z.cs, kZipMax, out);
     // Groups [lo, lo + cnt) of the chunk: one equation each.  A failing group is split in halves
     // while the failures look sparse (at most half of a level's groups fail) and halves stay
-    // >= kZipMinGroup; the remaining failing groups are decided signature by signature.
+    // >= kZipMinGroup; the remaining failing groups are decided signature by signature.  The rule
+    // is zip_plan.h's (tested without a device, tests/test_zip_plan_host.py).
     constexpr uint32_t kZipMinGroup = 1u << 14;
-    std::vector<std::pair<uint32_t, uint32_t>> level{{0u, N}}, single;
-    while (!level.empty()) {
-      std::vector<std::pair<uint32_t, uint32_t>> failed;
-      for (auto &g : level) {
-        e = zip_msm(c, z, N, g.first, g.second, s);
-        if (e != hipSuccess) return map_err(e);
-        bool ok = false;
-        int rc = zip_read_flag(c, z, s, &ok);
-        if (rc != TMED_OK) return rc;
-        g_zip_stats[1]++;
-        if (!ok) failed.push_back(g);
-      }
-      const bool dense = level.size() >= 2 && failed.size() * 2 > level.size();
-      std::vector<std::pair<uint32_t, uint32_t>> next;
-      for (auto &g : failed) {
-        if (!dense && g.second >= 2 * kZipMinGroup) {
-          const uint32_t h = g.second / 2;
-          next.push_back({g.first, h});
-          next.push_back({g.first + h, g.second - h});
-        } else {
-          single.push_back(g);
-        }
-      }
-      level.swap(next);
-    }
+    std::vector<ZipGroup> single;
+    uint32_t equations = 0;
+    const int prc = zip_plan_run(
+        N, kZipMinGroup,
+        [&](uint32_t, uint32_t lo, uint32_t cnt, bool *ok) {
+          const hipError_t me = zip_msm(c, z, N, lo, cnt, s);
+          if (me != hipSuccess) return map_err(me);
+          const int rc = zip_read_flag(c, z, s, ok);
+          if (rc == TMED_OK) g_zip_stats[1]++;
+          return rc;
+        },
+        single, equations);
+    if (prc != TMED_OK) return prc;
     if (N >= kZipSinglyMin) c->zip_dense = !single.empty();  // a failing group always ends in `single`
     for (auto &g : single) {  // the exact ZIP-215 single check on the group's signatures
       g_zip_stats[2]++;
@@ -968,6 +987,69 @@ int tmed_zip215_set_seed(const uint8_t *seed32) {
 int tmed_zip215_stats(uint32_t out[4]) {
   if (!out) return TMED_EINVAL;
   memcpy(out, g_zip_stats, sizeof g_zip_stats);
+  return TMED_OK;
+}
+
+int tmed_test_zip_msm(tmed_ctx *c, uint32_t n, const uint8_t *points, const int16_t *digits, const uint8_t *cvals,
+                      uint32_t lo, uint32_t cnt, int32_t windows[640], uint32_t ctot[8], uint32_t *flag) {
+  if (!c || !points || !digits || !cvals || !windows || !ctot || !flag) return TMED_EINVAL;
+  if (n == 0 || n > 65536 || cnt == 0 || lo > n || cnt > n - lo) return TMED_EINVAL;
+  const size_t rows = 2 * (size_t)n;
+  for (size_t i = 0; i < n; i++) {  // the top A digit: 13 bits of a < L plus the recoding's carry
+    const int d = digits[(size_t)(kZipWin - 1) * rows + i];
+    if (d < 0 || d > 4097) return TMED_EINVAL;
+  }
+  std::lock_guard<std::mutex> lk(c->mu);
+  (void)hipSetDevice(c->device);
+  hipStream_t s = c->stream;
+  ZipBufs z;
+  hipError_t e = zip_bufs(c, z);
+  if (e != hipSuccess) return map_err(e);
+  // staged inputs: encodings (32 B per row), c (32 B per signature), digits, the bad-row count
+  const size_t b_enc = 32 * rows, b_c = 32 * (size_t)n, b_dig = (size_t)kZipWin * rows * 2;
+  uint8_t *d_in = nullptr;
+  uint32_t bad = 0, h_flag = 0, h_ctot[8];
+  int4 h_win[20 * kZipWin];  // the last level's one item per window: [S, T][q][w]
+  e = hipMalloc((void **)&d_in, b_enc + b_c + b_dig + 16);
+  if (e != hipSuccess) return map_err(e);
+  uint32_t *d_bad = (uint32_t *)(d_in + b_enc + b_c + b_dig);
+  e = hipMemcpyAsync(d_in, points, b_enc, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_in + b_enc, cvals, b_c, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_in + b_enc + b_c, digits, b_dig, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, 16, s);
+  if (e == hipSuccess) e = scratch_acquire(c, s);
+  bool acquired = e == hipSuccess;
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(zip_test_fill_kernel, dim3((uint32_t)((rows + 255) / 256)), dim3(256), 0, s, d_in,
+                       (const int16_t *)(d_in + b_enc + b_c), d_in + b_enc, n, z.pts, z.dig, z.cs, kZipMax, d_bad);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e == hipSuccess && bad == 0) {
+    e = zip_msm(c, z, n, lo, cnt, s);  // the product's own launches, on the product's scratch
+    if (e == hipSuccess) e = hipMemcpyAsync(h_win, z.items[3], sizeof h_win, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(h_ctot, z.ctot, sizeof h_ctot, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&h_flag, z.flag, 4, hipMemcpyDeviceToHost, s);
+  }
+  if (acquired) {
+    const hipError_t er = scratch_release(c, s);
+    if (e == hipSuccess) e = er;
+  }
+  const hipError_t es = hipStreamSynchronize(s);
+  if (e == hipSuccess) e = es;
+  (void)hipFree(d_in);
+  if (e != hipSuccess) return map_err(e);
+  if (bad != 0) return TMED_EINVAL;
+  // window w = the T point of its last item (what zip_final_kernel reads): int4 q of [1][q][w]
+  for (int w = 0; w < kZipWin; w++)
+    for (int q = 0; q < 10; q++) {
+      const int4 v = h_win[(10 + q) * kZipWin + w];
+      int32_t *o = windows + 40 * w + 4 * q;
+      o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+    }
+  memcpy(ctot, h_ctot, sizeof h_ctot);
+  *flag = h_flag;
   return TMED_OK;
 }
 

@@ -336,5 +336,21 @@ class Engine:
             raise TmedError(rc, "tmed_test_table_chain")
         return rows.value, bad.value, [(int(v) >> 32, int(v) & 0xffffffff) for v in first[:min(bad.value, 16)]]
 
+    def zip_msm(self, points: np.ndarray, digits: np.ndarray, c: np.ndarray, lo: int, cnt: int):
+        """Tests: the ZIP-215 batch mode's own MSM over the group [lo, lo + cnt) of a chunk of n rows a
+        caller gives (tmed_test_zip_msm).  points (2n, 32) uint8: the A rows then the R rows, decoded
+        permissively, each row holding -P; digits (16, 2n) int16; c (n, 32) uint8.
+        -> (windows (16, 4, 10) int32: X, Y, Z, T limbs of every window, ctot (8,) uint32, flag)."""
+        n = c.shape[0]
+        points = np.ascontiguousarray(points, dtype=np.uint8).reshape(2 * n, 32)
+        digits = np.ascontiguousarray(digits, dtype=np.int16).reshape(16, 2 * n)
+        c = np.ascontiguousarray(c, dtype=np.uint8).reshape(n, 32)
+        win, ctot, flag = np.zeros((16, 4, 10), np.int32), np.zeros(8, np.uint32), ctypes.c_uint32(2)
+        rc = lib().tmed_test_zip_msm(self._h, n, _p(points), _p(digits), _p(c), lo, cnt, _p(win), _p(ctot),
+                                     ctypes.byref(flag))
+        if rc != 0:
+            raise TmedError(rc, "tmed_test_zip_msm")
+        return win, ctot, int(flag.value)
+
     def last_kernel_ms(self) -> float:
         return float(lib().tmed_last_kernel_ms(self._h))

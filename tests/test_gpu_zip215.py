@@ -8,7 +8,11 @@ this parity is "derived from the ZIP-215 rule, unpinned by the reference".  Cove
     ZIP-215 accepts and Go rejects: mixed-order R and A, non-canonical and negative-zero R,
     small-order A and R with S = 0) — one MSM, no single checks;
   * bisection down to groups decided signature by signature (one bad signature in 70k);
-  * dense failures (the golden classes, the C5 mix) decided by the exact single check."""
+  * dense failures (the golden classes, the C5 mix) decided by the exact single check;
+  * soundness by position: one bad signature at the ends of the halves of the smallest bisected
+    chunk, of chunks that are not bisected and of a chunk boundary, and an all-invalid group.
+The multi-scalar multiplication itself is tested stage by stage in tests/test_gpu_zip_msm.py, the
+bisection plan without a device in tests/test_zip_plan_host.py."""
 import json
 import os
 
@@ -206,3 +210,124 @@ def test_failure_policy_across_chunks_of_one_call():
         assert st["single_sigs"] == 3 * 65536 and st["equations"] == 4, st
     finally:
         eng.close()
+
+
+# ----------------------------------------------------------------------------- soundness by position
+# One signature's verdict depends on other signatures' data only here: a contribution an equation
+# leaves out (the first or last row of a group, of a half, of a chunk) would let a bad signature
+# pass.  Every test below runs on its own context (zip_dense starts false) with a fixed seed.
+
+def _own_engine(**env):
+    from conftest import engine_with_env
+    from tmed import Engine
+    eng = engine_with_env(**env)
+    Engine.zip215_set_seed(bytes(range(100, 132)))
+    return eng
+
+
+def _close(eng):
+    from tmed import Engine
+    Engine.zip215_set_seed(None)
+    eng.close()
+
+
+def _flipped(sigs, bad):
+    s = sigs.copy()
+    s[bad, 33 + bad % 20] ^= 0x04  # a bit of S
+    return s
+
+
+def test_bad_signature_at_the_ends_of_the_halves():
+    """The smallest chunk that is bisected: 32,769 = 16,384 + 16,385.  One flipped signature at the
+    first and last index of either half: three equations, and exactly the half that holds it is
+    decided singly.  An all-valid call in between clears the failure cut-off (it is decided singly)."""
+    from tmed import Engine
+    n = 32_769
+    eng = _own_engine()
+    try:
+        rng, pubs, sigs, msgs, offs = _signed_batch(eng, n, 0xB15)
+        for bad, half in ((0, 16_384), (16_383, 16_384), (16_384, 16_385), (32_768, 16_385)):
+            one = _flipped(sigs, bad)
+            out = eng.verify_zip215_arrays(pubs, one, msgs, offs)
+            st = Engine.zip215_stats()
+            exp = port.verify_batch(pubs, one, msgs, offs.astype(np.uint64), 16, zip215=True)
+            assert int(exp.sum()) == n - 1 and exp[bad] == 0
+            assert int((out != exp).sum()) == 0, bad
+            assert st["equations"] == 3 and st["single_sigs"] == half, (bad, st)
+            out = eng.verify_zip215_arrays(pubs, sigs, msgs, offs)
+            st = Engine.zip215_stats()
+            assert out.all() and st["equations"] == 0 and st["single_sigs"] == n, (bad, st)
+    finally:
+        _close(eng)
+
+
+@pytest.mark.parametrize("n", [1, 2, 64, 65, 257, 2049, 4097])
+def test_bad_signature_first_and_last_of_a_small_chunk(n):
+    """Chunks that are not bisected: the bad signature first, then last; one equation, which fails,
+    and the whole chunk decided singly."""
+    from tmed import Engine
+    eng = _own_engine()
+    try:
+        rng, pubs, sigs, msgs, offs = _signed_batch(eng, n, 0xF1 + n)
+        out = eng.verify_zip215_arrays(pubs, sigs, msgs, offs)
+        st = Engine.zip215_stats()
+        assert out.all() and st["equations"] == 1 and st["single_sigs"] == 0, st
+        for bad in (0, n - 1):
+            one = _flipped(sigs, bad)
+            out = eng.verify_zip215_arrays(pubs, one, msgs, offs)
+            st = Engine.zip215_stats()
+            exp = port.verify_batch(pubs, one, msgs, offs.astype(np.uint64), 16, zip215=True)
+            assert int(exp.sum()) == n - 1 and exp[bad] == 0
+            assert int((out != exp).sum()) == 0, bad
+            assert st["equations"] == 1 and st["single_sigs"] == n, (bad, st)
+    finally:
+        _close(eng)
+
+
+def test_bad_signature_at_a_chunk_boundary():
+    """Chunks of 65,536 (TMED_SLAB_SLOTS) and 65,537 signatures: the bad signature last of chunk 0,
+    then alone in chunk 1 (a chunk of one signature whose index base is not 0)."""
+    from tmed import Engine
+    n = 65_537
+    eng = _own_engine(TMED_SLAB_SLOTS=65536)
+    try:
+        rng, pubs, sigs, msgs, offs = _signed_batch(eng, n, 0xCB)
+        stats = []
+        for bad in (65_535, None, 65_536):
+            one = sigs if bad is None else _flipped(sigs, bad)
+            out = eng.verify_zip215_arrays(pubs, one, msgs, offs)
+            stats.append(Engine.zip215_stats())
+            exp = port.verify_batch(pubs, one, msgs, offs.astype(np.uint64), 16, zip215=True)
+            assert int(exp.sum()) == n - (bad is not None) and (bad is None or exp[bad] == 0)
+            assert int((out != exp).sum()) == 0, bad
+        assert all(st["chunks"] == 2 for st in stats), stats
+        # chunk 0 halved twice (1 + 2 + 2 equations, its last quarter singly), chunk 1 one equation
+        assert stats[0]["equations"] == 6 and stats[0]["single_sigs"] == 16_384, stats
+        # all valid: chunk 0 singly (its predecessor failed), chunk 1 (below the cut-off's size) one equation
+        assert stats[1]["equations"] == 1 and stats[1]["single_sigs"] == 65_536, stats
+        # chunk 0's equation holds; chunk 1's fails and its one signature is decided singly
+        assert stats[2]["equations"] == 2 and stats[2]["single_sigs"] == 1, stats
+    finally:
+        _close(eng)
+
+
+def test_all_invalid_group():
+    """Three tuples whose A does not decode and one with S >= L: nothing enters the equation, which
+    then holds over no point at all; every verdict is the 0 the prep wrote."""
+    from oracle import ed25519_go as E
+    from tmed import Engine
+    eng = _own_engine()
+    try:
+        rng, pubs, sigs, msgs, offs = _signed_batch(eng, 4, 0xA11)
+        ys = [y for y in range(2, 40) if E.decode(y.to_bytes(32, "little")) is None][:3]
+        assert len(ys) == 3
+        for i, y in enumerate(ys):
+            pubs[i] = np.frombuffer(y.to_bytes(32, "little"), np.uint8)
+        sigs[3, 32:] = np.frombuffer(E.L.to_bytes(32, "little"), np.uint8)
+        out = eng.verify_zip215_arrays(pubs, sigs, msgs, offs)
+        st = Engine.zip215_stats()
+        assert not out.any()
+        assert not port.verify_batch(pubs, sigs, msgs, offs.astype(np.uint64), 4, zip215=True).any()
+        assert st["equations"] == 1 and st["single_sigs"] == 0, st
+    finally:
+        _close(eng)
