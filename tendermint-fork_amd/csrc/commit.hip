@@ -32,7 +32,7 @@
 #include <vector>
 
 #include "../../include/tmed25519.h"
-#include "ctx.h"
+#include "call_frame.h"
 #include "host_pool.h"
 #include "signbytes.h"
 #include "votes_host.h"
@@ -307,15 +307,11 @@ static int light_hashes_device(tmed_ctx *ctx, const tmed_light_request *reqs, co
   }
   std::vector<uint8_t> ho(32 * std::max<size_t>(m, 1)), ok(std::max<size_t>(m, 1));
   std::vector<uint8_t> so(32 * std::max<size_t>(sets.size(), 1));
-  int rc;
-  {
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    rc = bs_drain(ctx);
-    if (rc == TMED_OK && m) rc = tmed::header_hashes_locked(ctx, hs.data(), m, ho.data(), ok.data());
-    if (rc == TMED_OK && !sets.empty())
-      rc = tmed::valsets_hashes_locked(ctx, sets.data(), sets.size(), so.data());
-  }
-  bs_reap(ctx);
+  const int rc = tmed::locked(ctx, /*collect=*/true, [&] {
+    int r = m ? tmed::header_hashes_locked(ctx, hs.data(), m, ho.data(), ok.data()) : TMED_OK;
+    if (r == TMED_OK && !sets.empty()) r = tmed::valsets_hashes_locked(ctx, sets.data(), sets.size(), so.data());
+    return r;
+  });
   if (rc != TMED_OK) return rc;
   for (size_t j = 0; j < m; j++) {
     memcpy(hdr_hash + 32 * need_hdr[j], ho.data() + 32 * j, 32);
@@ -352,27 +348,20 @@ extern "C" int tmed_verify_votes(tmed_ctx *ctx, const tmed_vote_request *reqs, s
       total += reqs[q].votes->n;
     }
     if (total && !codes) return (int)TMED_EINVAL;
-    int rc;
-    {
-      std::vector<tmed_commit> shadow_commits(n_reqs);
-      std::vector<tmed_commit_request> shadow(n_reqs);
-      for (size_t q = 0; q < n_reqs; q++) {
-        memset(&shadow_commits[q], 0, sizeof(tmed_commit));
-        memset(&shadow[q], 0, sizeof(tmed_commit_request));
-        shadow_commits[q].n_sigs = reqs[q].votes->n;
-        shadow[q].vals = reqs[q].vals;
-        shadow[q].commit = &shadow_commits[q];
-      }
-      KcCall kc;  // pins the cache's pool until the batch below is collected
-      const tmed_commit_request *resolved = keycache_resolve(ctx, shadow.data(), n_reqs, kc);
-      std::vector<tmed_vote_request> rq(reqs, reqs + n_reqs);
-      for (size_t q = 0; q < n_reqs; q++) rq[q].vals = resolved[q].vals;
-      std::lock_guard<std::mutex> lk(ctx->mu);
-      rc = bs_drain(ctx);  // the seam's rule: submitted blocksync windows first
-      if (rc == TMED_OK) rc = tmed::verify_votes_locked(ctx, rq.data(), n_reqs, codes);
+    std::vector<tmed_commit> shadow_commits(n_reqs);
+    std::vector<tmed_commit_request> shadow(n_reqs);
+    for (size_t q = 0; q < n_reqs; q++) {
+      memset(&shadow_commits[q], 0, sizeof(tmed_commit));
+      memset(&shadow[q], 0, sizeof(tmed_commit_request));
+      shadow_commits[q].n_sigs = reqs[q].votes->n;
+      shadow[q].vals = reqs[q].vals;
+      shadow[q].commit = &shadow_commits[q];
     }
-    bs_reap(ctx);
-    return rc;
+    KcCall kc;  // pins the cache's pool until the batch below is collected
+    const tmed_commit_request *resolved = keycache_resolve(ctx, shadow.data(), n_reqs, kc);
+    std::vector<tmed_vote_request> rq(reqs, reqs + n_reqs);
+    for (size_t q = 0; q < n_reqs; q++) rq[q].vals = resolved[q].vals;
+    return tmed::locked(ctx, /*collect=*/true, [&] { return tmed::verify_votes_locked(ctx, rq.data(), n_reqs, codes); });
   });
 }
 

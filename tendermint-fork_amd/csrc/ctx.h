@@ -1,4 +1,6 @@
-// ctx.h — tmed_ctx internals shared by the host-side translation units.
+// ctx.h — tmed_ctx internals shared by the host-side translation units: the context's buffers, key
+// sets and scratch.  The frame the entry points run in over them (lock, staging, the one exit that
+// waits for the stream) is call_frame.h; the exception guard of every extern "C" function is api_guard.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -53,6 +55,22 @@ struct HostBuf {
     p = nullptr;
     cap = 0;
   }
+};
+
+// A pinned buffer and a device buffer that one call fills, copies and reads back.
+struct Staged {
+  HostBuf h;
+  DevBuf d;
+  hipError_t ensure(size_t host_bytes, size_t dev_bytes) {
+    const hipError_t e = h.ensure(host_bytes);
+    return e == hipSuccess ? d.ensure(dev_bytes) : e;
+  }
+  void release() {
+    h.release();
+    d.release();
+  }
+  uint8_t *host() const { return (uint8_t *)h.p; }
+  uint8_t *dev() const { return (uint8_t *)d.p; }
 };
 
 inline int map_err(hipError_t e) {
@@ -301,24 +319,14 @@ struct tmed_ctx {
   // Merkle proofs: the leaves' aunt offsets and the call's outputs (verify: its root indexes,
   // totals / indexes and codes)
   tmed::DevBuf d_proof_off, d_proof_out, d_proof_in;
-  // tmed_commit_hashes (merkle.hip): the commits' arrays packed per kind (pinned) and their device
-  // copy, plus the roots.  Its own buffers: no batch of a submitted blocksync window ever holds them.
-  tmed::HostBuf h_csig;
-  tmed::DevBuf d_csig;
-  // header_hash_kernel (merkle.hip): the packed header records (pinned) and their device copy, plus
-  // the hashes.  Its own buffers, as h_csig / d_csig.
-  tmed::HostBuf h_hdr;
-  tmed::DevBuf d_hdr;
-  // tmed_median_times (median.hip): the pair table, the commits' and the sets' arrays packed per
-  // kind (pinned) and their device copy, plus the outcomes.  Its own buffers, as h_csig / d_csig.
-  tmed::HostBuf h_med;
-  tmed::DevBuf d_med;
-  // tmed_verify_votes (votes.hip): the votes' records, the requests' steps and set addresses, keys and
-  // signatures (pinned) and their device copy, plus the slots, lengths, codes and validity bits.  Its
-  // own buffers, as h_csig / d_csig.  vote_ev: the end of vote_prepare_kernel (last_vote_prep_ms).
-  tmed::HostBuf h_vfree;
-  tmed::DevBuf d_vfree;
-  hipEvent_t vote_ev = nullptr;
+  // The staging arena of commit_hashes_locked, header_hashes_fused (merkle.hip), median_times_locked
+  // (median.hip) and run_group_device (votes.hip), each laid out by its own layout struct.  One pair
+  // serves all four: each packs, copies in, launches, copies out, waits (finish_call) and reads its
+  // results before it returns, all inside one hold of ctx->mu, so no two are ever live at once (a
+  // light-client call takes its header hashes, set hashes and commit checks under separate holds, one
+  // after the other).  No batch of a submitted blocksync window touches it: those hold the vote slots.
+  tmed::Staged stage;
+  hipEvent_t vote_ev = nullptr;  // the end of vote_prepare_kernel (last_vote_prep_ms)
   float last_vote_prep_ms = 0.f;
   tmed::DevBuf d_korder;  // key-grouped order of a key-cached batch: counts / cursors + permutation
   tmed::DevBuf d_zip;     // ZIP-215 batch mode scratch (zip215.hip zip_bufs: points, digits, sort, buckets)

@@ -13,7 +13,7 @@
 #include <algorithm>
 #include <chrono>
 
-#include "ctx.h"
+#include "call_frame.h"
 
 using namespace tmed;
 
@@ -24,9 +24,9 @@ int build_comb(tmed_ctx *c, const uint8_t *d_pubs, size_t n, int negate, uint8_t
   hipError_t e = hipMalloc((void **)&d_bases, n * kCombWindows * 40 * sizeof(int32_t));
   if (e == hipSuccess) e = launch_comb_bases(d_pubs, (uint32_t)n, negate, d_ok, d_bases, c->stream);
   if (e == hipSuccess) e = launch_comb_fill(d_bases, (uint32_t)n, d_comb, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  const int rc = finish_call(c, c->stream, e);
   if (d_bases) (void)hipFree(d_bases);
-  return map_err(e);
+  return rc;
 }
 
 // Every key-set device allocation goes through here (TMED_TEST_FAIL_KS_ALLOC: the failure paths
@@ -54,8 +54,6 @@ void free_keyset(Keyset &k) {
   if (k.h_tab) (void)hipHostFree(k.h_tab);
   k = Keyset();
 }
-
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // Key-grouped visiting order for the throughput kernels (launch_key_order): the comb rows a
 // signature reads are random 128-B lines of its key's 528-KB comb; with the signatures of a
@@ -587,7 +585,7 @@ int tmed_keyset_load(tmed_ctx *c, const uint8_t *pubkeys, size_t n, uint64_t *ha
   // room for one key at least: an index past an empty set still reads key 0's rows (and rejects)
   int rc = keyset_reserve(c, k, n ? n : 1, n ? n : 1, c->stream);
   if (rc == TMED_OK) rc = keyset_append(c, k, pubkeys, n, c->stream, n);
-  if (rc == TMED_OK) rc = map_err(hipStreamSynchronize(c->stream));
+  rc = finish_call(c, c->stream, rc);
   if (rc == TMED_OK) (void)ctx_bcomb24(c);  // the shared radix-2^24 B comb (null: radix 2^16)
   if (rc != TMED_OK) {
     free_keyset(k);
@@ -607,9 +605,7 @@ int tmed_keyset_extend(tmed_ctx *c, uint64_t handle, const uint8_t *pubkeys, siz
   if (first_index) *first_index = (uint32_t)k->n;
   if (n == 0) return TMED_OK;
   (void)hipSetDevice(c->device);
-  int rc = keyset_append(c, *k, pubkeys, n, c->stream, 0xffffffu);
-  if (rc == TMED_OK) rc = map_err(hipStreamSynchronize(c->stream));
-  return rc;
+  return finish_call(c, c->stream, keyset_append(c, *k, pubkeys, n, c->stream, 0xffffffu));
 }
 
 int tmed_keyset_free(tmed_ctx *c, uint64_t handle) {
@@ -649,13 +645,9 @@ int tmed_verify_batch_keyset_device(tmed_ctx *c, uint64_t handle, const uint32_t
 int tmed_verify_batch_keyset(tmed_ctx *c, uint64_t handle, const uint32_t *val_idx, const uint8_t *sigs,
                              const uint32_t *sig_lens, const uint8_t *msgs, const uint32_t *off, size_t n,
                              uint8_t *out) {
-  if (!c || !out) return TMED_EINVAL;
-  if (n == 0) return TMED_OK;
-  if (!val_idx || !sigs || !off || n > 0xffffffffu) return TMED_EINVAL;
-  for (size_t i = 0; i < n; i++)
-    if (off[i + 1] < off[i]) return TMED_EINVAL;
+  int rc = check_raw_batch(c, val_idx, sigs, msgs, off, n, out);
+  if (rc != TMED_OK || n == 0) return rc;
   const size_t mbytes = off[n];
-  if (mbytes && !msgs) return TMED_EINVAL;
   std::lock_guard<std::mutex> lk(c->mu);
   Keyset *kp = find_keyset(c, handle);
   if (!kp) return TMED_ENOKEYSET;
@@ -663,42 +655,21 @@ int tmed_verify_batch_keyset(tmed_ctx *c, uint64_t handle, const uint32_t *val_i
   for (size_t i = 0; i < n; i++)
     if (val_idx[i] >= k.n) return TMED_EINVAL;
   (void)hipSetDevice(c->device);
-  hipError_t e = hipSuccess;
-  const size_t moff = (n + 1) * 4;
-  for (auto &pr : {std::make_pair(&c->d_a, n * 4), std::make_pair(&c->d_b, n * 64),
-                   std::make_pair(&c->d_msg, mbytes + 16), std::make_pair(&c->d_off, moff),
-                   std::make_pair(&c->d_out, n)})
-    if (e == hipSuccess) e = pr.first->ensure(pr.second);
-  for (auto &pr : {std::make_pair(&c->h_a, n * 4), std::make_pair(&c->h_b, n * 64),
-                   std::make_pair(&c->h_msg, mbytes + 16), std::make_pair(&c->h_off, moff),
-                   std::make_pair(&c->h_out, n)})
-    if (e == hipSuccess) e = pr.first->ensure(pr.second);
-  if (e != hipSuccess) return map_err(e);
-  memcpy(c->h_a.p, val_idx, n * 4);
-  memcpy(c->h_b.p, sigs, n * 64);
-  if (mbytes) memcpy(c->h_msg.p, msgs, mbytes);
-  memcpy(c->h_off.p, off, moff);
-  hipStream_t s = c->stream;
-  e = hipMemcpyAsync(c->d_a.p, c->h_a.p, n * 4, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(c->d_b.p, c->h_b.p, n * 64, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && mbytes) e = hipMemcpyAsync(c->d_msg.p, c->h_msg.p, mbytes, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(c->d_off.p, c->h_off.p, moff, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = scratch_acquire(c, s);
-  if (e == hipSuccess) e = hipEventRecord(c->ev0, s);
-  if (e == hipSuccess)
-    e = keyset_verify(c, k, (const uint32_t *)c->d_a.p, (const uint8_t *)c->d_b.p, (const uint8_t *)c->d_msg.p,
-                      (const uint32_t *)c->d_off.p, (uint32_t)n, (uint8_t *)c->d_out.p, s, false);
-  if (e == hipSuccess) e = hipEventRecord(c->ev1, s);
-  if (e == hipSuccess) e = scratch_release(c, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(c->h_out.p, c->d_out.p, n, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return map_err(e);
-  (void)hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1);
-  memcpy(out, c->h_out.p, n);
-  if (sig_lens)
-    for (size_t i = 0; i < n; i++)
-      if (sig_lens[i] != 64) out[i] = 0;  // crypto/ed25519/ed25519.go:150-152
-  return TMED_OK;
+  RawStage st;
+  rc = raw_stage(c, 4, n, mbytes, st);
+  if (rc != TMED_OK) return rc;
+  memcpy(st.keys, val_idx, n * 4);
+  memcpy(st.sigs, sigs, n * 64);
+  if (mbytes) memcpy(st.msgs, msgs, mbytes);
+  memcpy(st.off, off, (n + 1) * 4);
+  rc = raw_run(c, st, /*timed=*/true,
+               [&](const uint8_t *d_idx, const uint8_t *d_sig, const uint8_t *d_msg, const uint32_t *d_off, uint32_t m,
+                   uint8_t *d_out, hipStream_t s) {
+                 return map_err(keyset_verify(c, k, (const uint32_t *)d_idx, d_sig, d_msg, d_off, m, d_out, s, false));
+               },
+               out, sig_lens);
+  if (rc == TMED_OK) c->last_ms = st.ms;
+  return rc;
 }
 
 }  // extern "C"

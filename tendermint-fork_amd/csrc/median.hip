@@ -33,7 +33,7 @@
 #include <vector>
 
 #include "../../include/tmed25519.h"
-#include "ctx.h"
+#include "call_frame.h"
 #include "host_for.h"
 #include "median_host.h"
 
@@ -223,20 +223,18 @@ __global__ __launch_bounds__(kWaves == 1 ? 64 * kMedWaveGroups : 64 * kWaves) vo
 }
 
 // ---- staging ---------------------------------------------------------------------------------------
-static size_t med_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // The call's regions for P pairs, Nc commit elements and Ns set elements; [0, out) is copied in.
 struct MedLayout {
   size_t pairs, sec, power, nanos, caddr, saddr, flags, out, total;
   MedLayout(size_t P, size_t Nc, size_t Ns) {
     pairs = 0;
-    sec = med_align(pairs + sizeof(MedPair) * P);
-    power = med_align(sec + 8 * Nc);
-    nanos = med_align(power + 8 * Ns);
-    caddr = med_align(nanos + 4 * Nc);
-    saddr = med_align(caddr + 20 * Nc);
-    flags = med_align(saddr + 20 * Ns);
-    out = med_align(flags + Nc);
+    sec = align256(pairs + sizeof(MedPair) * P);
+    power = align256(sec + 8 * Nc);
+    nanos = align256(power + 8 * Ns);
+    caddr = align256(nanos + 4 * Nc);
+    saddr = align256(caddr + 20 * Nc);
+    flags = align256(saddr + 20 * Ns);
+    out = align256(flags + Nc);
     total = out + sizeof(MedOut) * P;
   }
 };
@@ -286,10 +284,9 @@ int median_times_locked(tmed_ctx *c, const tmed_median_request *reqs, size_t n, 
     const MedLayout lay(P, Nc, Ns);
     (void)hipSetDevice(c->device);
     hipStream_t s = c->stream;
-    hipError_t e = c->h_med.ensure(lay.total);
-    if (e == hipSuccess) e = c->d_med.ensure(lay.total);
+    hipError_t e = c->stage.ensure(lay.total, lay.total);
     if (e != hipSuccess) return map_err(e);
-    uint8_t *h = (uint8_t *)c->h_med.p, *d = (uint8_t *)c->d_med.p;
+    uint8_t *h = c->stage.host(), *d = c->stage.dev();
     MedPair *hp = reinterpret_cast<MedPair *>(h + lay.pairs);
     for (size_t j = 0; j < P; j++)
       hp[j] = MedPair{cbase[reqs[dev[j]].commit], sbase[reqs[dev[j]].vals], (uint32_t)reqs[dev[j]].commit->n_sigs, 0};
@@ -335,10 +332,8 @@ int median_times_locked(tmed_ctx *c, const tmed_median_request *reqs, size_t n, 
         e = hipErrorOutOfMemory;
       }
     }
-    const hipError_t es = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return map_err(e);
-    (void)hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1);
+    const int rc = finish_call(c, s, e, &c->last_ms);
+    if (rc != TMED_OK) return rc;
     const MedOut *ho = reinterpret_cast<const MedOut *>(h + lay.out);
     for (size_t j = 0; j < P; j++) {
       if (ho[j].status == kMedMisaligned || !sets.get(*reqs[dev[j]].vals).unique) {

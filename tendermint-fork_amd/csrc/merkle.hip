@@ -23,7 +23,8 @@
 // Host shape, the same for every root and proof call: the level plan (merkle_levels.h) from the
 // trees' leaf counts, a leaf stage that writes level 0 into the node buffer, build_levels (the plan
 // uploaded once, then every level launch back to back into the one buffer that keeps every level),
-// emit_roots on the last level, and one wait before the call returns.
+// emit_roots on the last level, and one wait before the call returns (finish_call).  The call frame
+// (guard, lock, that exit) is call_frame.h; Commit.Hash and the fused Header.Hash stage in tmed_ctx::stage.
 //
 // Proofs (crypto/merkle/proof.go:35-68, 151-181, 216-237; types/part_set.go:166-194 keeps every
 // part's proof, types/tx.go:80-93 builds one per transaction): after the levels are built,
@@ -34,13 +35,12 @@
 #include <string.h>
 
 #include <algorithm>
-#include <new>
 #include <thread>
 #include <vector>
 
 #include "../../include/tmed25519.h"
+#include "call_frame.h"
 #include "commitsig_leaf.h"
-#include "ctx.h"
 #include "header_leaf.h"
 #include "host_for.h"
 #include "merkle_levels.h"
@@ -339,8 +339,6 @@ __global__ __launch_bounds__(256) void header_hash_kernel(const uint8_t *__restr
   }
 }
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // One step of a call's chain of stream operations: after a failure (e) or for no lanes nothing is
 // launched; else kernel k over `lanes` lanes in blocks of 256.
 template <class K, class... A>
@@ -391,50 +389,16 @@ static hipError_t emit_roots(tmed_ctx *c, const MerkleLevels &p, uint8_t *d_root
                 dev_tab(c, p) + last * (p.T + 1), (uint32_t)p.T, d_roots);
 }
 
-// The one exit of every device call of this file, taken on a failure (e) as on success: the call
-// has queued copies whose sources are host vectors of its own (the plan, offsets) or the caller's
-// pageable arrays, so it waits for the stream before any of them goes away.  timed: ev0 / ev1 were
-// recorded around the call's kernel of record (tmed_last_kernel_ms).
-static int finish_call(tmed_ctx *c, hipError_t e, bool timed) {
-  const hipError_t es = hipStreamSynchronize(c->stream);
-  if (e == hipSuccess) e = es;
-  if (e == hipSuccess && timed) (void)hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1);
-  return map_err(e);
-}
-
 }  // namespace tmed
 
 using namespace tmed;
 
 namespace {
 
-// ---- the call frame of every extern "C" function of this file -----------------------------------
-// guarded(body): body checks the arguments and builds the call's host vectors; no exception
-// crosses the C boundary.  Inside it, locked(c, collect, run) is the device part under ctx->mu;
-// collect: the call follows the seam's rule (ctx.h bs_collect_submitted) and first collects the
-// submitted blocksync windows, then releases the completed ones once the lock is dropped.
-template <class F>
-int guarded(F &&body) {
-  try {
-    return body();
-  } catch (const std::bad_alloc &) {
-    return TMED_ENOMEM;
-  } catch (...) {
-    return TMED_EINTERNAL;
-  }
-}
-
-template <class F>
-int locked(tmed_ctx *c, bool collect, F &&run) {
-  int rc;
-  {
-    std::lock_guard<std::mutex> lk(c->mu);
-    rc = collect ? bs_collect_submitted(c) : TMED_OK;
-    if (rc == TMED_OK) rc = run();
-  }
-  if (collect) bs_release_collected(c);
-  return rc;
-}
+// Every extern "C" function of this file runs in the shared call frame: guarded(body) (api_guard.h),
+// in which body checks the arguments and builds the call's host vectors, then locked(c, collect, run)
+// for the device part, which leaves through finish_call (call_frame.h; timed calls pass &c->last_ms
+// for the kernel of record between ev0 and ev1, tmed_last_kernel_ms).
 
 // ---- argument checks ------------------------------------------------------------------------
 // The forest of a byte-slice call (n_trees >= 1): tree t holds leaves [tree_off[t], tree_off[t+1]),
@@ -557,7 +521,7 @@ int roots_from_host_leaves_locked(tmed_ctx *c, const uint8_t *leaves, const uint
   if (e == hipSuccess) e = build_levels(c, plan, s);
   if (e == hipSuccess) e = emit_roots(c, plan, (uint8_t *)c->d_out.p, s);
   if (e == hipSuccess) e = hipMemcpyAsync(roots, c->d_out.p, T * 32, hipMemcpyDeviceToHost, s);
-  return finish_call(c, e, /*timed=*/txs);
+  return finish_call(c, s, e, txs ? &c->last_ms : nullptr);
 }
 
 // ---- Commit.Hash (types/block.go:894-912) ---------------------------------------------------
@@ -623,17 +587,16 @@ int header_hashes_fused(tmed_ctx *c, const tmed_header *headers, const std::vect
   const size_t o_roots = m * (size_t)kHdrRecBytes;  // a multiple of 256
   (void)hipSetDevice(c->device);
   hipStream_t s = c->stream;
-  hipError_t e = c->h_hdr.ensure(o_roots + 32 * m);
-  if (e == hipSuccess) e = c->d_hdr.ensure(o_roots + 32 * m);
+  hipError_t e = c->stage.ensure(o_roots + 32 * m, o_roots + 32 * m);
   if (e != hipSuccess) return map_err(e);
-  uint8_t *h = (uint8_t *)c->h_hdr.p, *d = (uint8_t *)c->d_hdr.p;
+  uint8_t *h = c->stage.host(), *d = c->stage.dev();
   host_for(m, pack_threads(m * 32), [&](size_t j) { header_pack(headers[idx[j]], h + j * kHdrRecBytes); });
   e = hipMemcpyAsync(d, h, o_roots, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipEventRecord(c->ev0, s);
   e = launch(e, header_hash_kernel, 16 * m, s, (const uint8_t *)d, (uint32_t)m, d + o_roots);
   if (e == hipSuccess) e = hipEventRecord(c->ev1, s);
   if (e == hipSuccess) e = hipMemcpyAsync(h + o_roots, d + o_roots, 32 * m, hipMemcpyDeviceToHost, s);
-  const int rc = finish_call(c, e, /*timed=*/true);
+  const int rc = finish_call(c, s, e, &c->last_ms);
   if (rc != TMED_OK) return rc;
   for (size_t j = 0; j < m; j++) memcpy(out + 32 * idx[j], h + o_roots + 32 * j, 32);
   return TMED_OK;
@@ -647,10 +610,9 @@ int commit_hashes_locked(tmed_ctx *c, const tmed_commit *commits, size_t n, cons
   const CsigLayout lay(N, n);
   int rc = ensure_nodes(c, plan);
   if (rc != TMED_OK) return rc;
-  hipError_t e = c->h_csig.ensure(lay.total);
-  if (e == hipSuccess) e = c->d_csig.ensure(lay.total);
+  hipError_t e = c->stage.ensure(lay.total, lay.total);
   if (e != hipSuccess) return map_err(e);
-  uint8_t *h = (uint8_t *)c->h_csig.p, *d = (uint8_t *)c->d_csig.p;
+  uint8_t *h = c->stage.host(), *d = c->stage.dev();
   host_for(n, pack_threads(N), [&](size_t i) {
     if (counts[i]) commit_pack(commits[i], h, lay, base[i]);
   });
@@ -668,7 +630,7 @@ int commit_hashes_locked(tmed_ctx *c, const tmed_commit *commits, size_t n, cons
   if (e == hipSuccess) e = build_levels(c, plan, s);
   if (e == hipSuccess) e = emit_roots(c, plan, d + lay.roots, s);
   if (e == hipSuccess) e = hipMemcpyAsync(h + lay.roots, d + lay.roots, n * 32, hipMemcpyDeviceToHost, s);
-  rc = finish_call(c, e, /*timed=*/true);
+  rc = finish_call(c, s, e, &c->last_ms);
   if (rc != TMED_OK) return rc;
   memcpy(out, h + lay.roots, n * 32);
   return TMED_OK;
@@ -712,7 +674,7 @@ int proofs_locked(tmed_ctx *c, const uint8_t *leaves, const uint64_t *leaf_off, 
   if (e == hipSuccess && need) e = hipMemcpyAsync(o.aunts, d_res, need, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess && L) e = hipMemcpyAsync(o.leaf_hashes, d_res + o_leaf, 32 * L, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipMemcpyAsync(o.roots, d_res + o_root, 32 * T, hipMemcpyDeviceToHost, s);
-  return finish_call(c, e, /*timed=*/true);
+  return finish_call(c, s, e, &c->last_ms);
 }
 
 // The common tail of the three generators: size the aunts on the host (merkle_path.h), answer a
@@ -785,7 +747,7 @@ int verify_proofs_locked(tmed_ctx *c, const ProofIn &in, const std::vector<uint6
              in.root_of ? (const uint32_t *)(d_in + o_rof) : nullptr, (uint32_t)n, (uint8_t *)c->d_proof_out.p);
   if (e == hipSuccess) e = hipEventRecord(c->ev1, s);
   if (e == hipSuccess) e = hipMemcpyAsync(out_code, c->d_proof_out.p, n, hipMemcpyDeviceToHost, s);
-  return finish_call(c, e, /*timed=*/true);
+  return finish_call(c, s, e, &c->last_ms);
 }
 
 // tmed_merkle_roots, and tmed_txs_hashes (txs) over blocks of transactions
@@ -851,7 +813,7 @@ int valset_hashes_locked(tmed_ctx *c, const uint8_t *pubkeys, const int64_t *pow
   if (e == hipSuccess) e = build_levels(c, plan, s);
   if (e == hipSuccess) e = emit_roots(c, plan, (uint8_t *)c->d_out.p, s);
   if (e == hipSuccess) e = hipMemcpyAsync(out, c->d_out.p, n_sets * 32, hipMemcpyDeviceToHost, s);
-  return finish_call(c, e, /*timed=*/false);
+  return finish_call(c, s, e);
 }
 
 // ValidatorSet.Hash of n_sets validator sets given as structs: their keys and powers are packed

@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "../../include/tmed25519.h"
+#include "api_guard.h"
 #include "host_pool.h"
 #include "keycache.h"
 #include "light_host.h"
@@ -970,7 +971,7 @@ extern "C" int tmed_seam_phase_us(double out_us[3]) {
 extern "C" int tmed_verify_commits_with(const tmed_commit_request *reqs, size_t n, tmed_commit_result *out,
                                         tmed_batch_verify_fn verify, void *user) {
   if (!verify) return TMED_EINVAL;
-  try {  // no C++ exception crosses the C ABI (c_guard below does the same for the device seams)
+  return guarded([&] {  // (c_guard.h does the same for the device seams)
     return run_seam(reqs, n, out,
                     [&](const tmed_commit_request *rq, size_t nr, const Cands &cands, uint8_t *valid) {
                       CandBatch cb;
@@ -979,9 +980,7 @@ extern "C" int tmed_verify_commits_with(const tmed_commit_request *reqs, size_t 
                       return verify(user, cb.pubs.data(), cb.sigs.data(), cb.lens.data(), cb.msgs.data(),
                                     cb.offs.data(), cb.m, valid);
                     });
-  } catch (const std::bad_alloc &) {
-    return TMED_ENOMEM;
-  }
+  });
 }
 
 // light.Verify over hashes and a batch verifier supplied by the caller (light_host.h is the replay).
@@ -990,7 +989,7 @@ extern "C" int tmed_light_verify_with(const tmed_light_request *reqs, size_t n, 
                                       const uint8_t *vals_hashes, tmed_light_result *out, tmed_batch_verify_fn verify,
                                       void *user) {
   if (!verify || (n && (!header_hashes || !header_ok || !vals_hashes))) return TMED_EINVAL;
-  try {
+  return guarded([&] {
     return tmed_light::light_run(
         reqs, n, flags, out,
         [&](const std::vector<size_t> &need_hdr, const std::vector<size_t> &need_vals, uint8_t *hh, uint8_t *hok,
@@ -1005,11 +1004,7 @@ extern "C" int tmed_light_verify_with(const tmed_light_request *reqs, size_t n, 
         [&](const tmed_commit_request *rq, size_t m, tmed_commit_result *res) {
           return tmed_verify_commits_with(rq, m, res, verify, user);
         });
-  } catch (const std::bad_alloc &) {
-    return TMED_ENOMEM;
-  } catch (...) {
-    return TMED_EINTERNAL;
-  }
+  });
 }
 
 // The group of every run without its aliased candidates: run ranges built in parallel (a

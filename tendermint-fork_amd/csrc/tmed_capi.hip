@@ -19,7 +19,7 @@
 #include "../../include/tmed25519.h"
 #include "kernels.h"
 
-#include "ctx.h"
+#include "call_frame.h"
 #include "median_host.h"
 
 using namespace tmed;
@@ -229,12 +229,9 @@ void tmed_destroy(tmed_ctx *c) {
   for (DevBuf *b : {&c->d_a, &c->d_b, &c->d_msg, &c->d_off, &c->d_out, &c->d_c}) b->release();
   for (HostBuf *b : {&c->h_a, &c->h_b, &c->h_msg, &c->h_off, &c->h_out, &c->h_c}) b->release();
   for (DevBuf *b : {&c->d_merkle_lv, &c->d_merkle_tab, &c->d_proof_off, &c->d_proof_out, &c->d_proof_in, &c->d_korder,
-                    &c->d_zip, &c->d_kbases, &c->d_csig, &c->d_hdr, &c->d_med, &c->d_vfree})
+                    &c->d_zip, &c->d_kbases})
     b->release();
-  c->h_csig.release();
-  c->h_hdr.release();
-  c->h_med.release();
-  c->h_vfree.release();
+  c->stage.release();
   if (c->vote_ev) hipEventDestroy(c->vote_ev);
   c->h_kup.release();
   if (c->kup_ev) hipEventDestroy(c->kup_ev);
@@ -276,13 +273,7 @@ float tmed_last_kernel_ms(tmed_ctx *c) { return c ? c->last_ms : 0.f; }
 // ---- state.MedianTime (median_host.h: the rule on the host; median.hip: the kernels and their staging)
 
 int tmed_median_times_host(const tmed_median_request *reqs, size_t n, tmed_median_result *out) {
-  try {
-    return tmed_median::median_times_host(reqs, n, out);
-  } catch (const std::bad_alloc &) {
-    return TMED_ENOMEM;
-  } catch (...) {
-    return TMED_EINTERNAL;
-  }
+  return guarded([&] { return tmed_median::median_times_host(reqs, n, out); });
 }
 
 int tmed_median_times(tmed_ctx *c, const tmed_median_request *reqs, size_t n, tmed_median_result *out) {
@@ -290,20 +281,9 @@ int tmed_median_times(tmed_ctx *c, const tmed_median_request *reqs, size_t n, tm
   if (n == 0) return TMED_OK;
   for (size_t i = 0; i < n; i++)
     if (tmed_median::check_request(reqs[i]) != TMED_OK) return TMED_EINVAL;
-  try {
-    int rc;
-    {
-      std::lock_guard<std::mutex> lk(c->mu);
-      rc = bs_collect_submitted(c);  // the seam's rule: submitted blocksync windows first
-      if (rc == TMED_OK) rc = median_times_locked(c, reqs, n, out);
-    }
-    bs_release_collected(c);
-    return rc;
-  } catch (const std::bad_alloc &) {
-    return TMED_ENOMEM;
-  } catch (...) {
-    return TMED_EINTERNAL;
-  }
+  return guarded([&] {
+    return locked(c, /*collect=*/true, [&] { return median_times_locked(c, reqs, n, out); });
+  });
 }
 
 int tmed_set_kernel_timing(tmed_ctx *c, int on) {
@@ -431,14 +411,19 @@ int tmed_window_stats(tmed_ctx *c, uint32_t lane_hist[65], uint32_t wave_hist[65
   (void)hipSetDevice(c->device);
   uint32_t *d = nullptr;
   hipError_t e = hipMalloc((void **)&d, 2 * 65 * sizeof(uint32_t));
-  if (e == hipSuccess) e = scratch_acquire(c, c->stream);
+  if (e != hipSuccess) return map_err(e);
+  e = scratch_acquire(c, c->stream);
+  const bool acquired = e == hipSuccess;
   if (e == hipSuccess) e = launch_window_stats(c->d_prep, c->slab_slots, c->last_hs_count, d, c->stream);
-  if (e == hipSuccess) e = scratch_release(c, c->stream);
+  if (acquired) {
+    const hipError_t er = scratch_release(c, c->stream);
+    if (e == hipSuccess) e = er;
+  }
   uint32_t h[130];
   if (e == hipSuccess) e = hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (d) (void)hipFree(d);
-  if (e != hipSuccess) return map_err(e);
+  const int rc = finish_call(c, c->stream, e);
+  (void)hipFree(d);
+  if (rc != TMED_OK) return rc;
   for (int w = 0; w < 65; w++) { lane_hist[w] = h[w]; wave_hist[w] = h[65 + w]; }
   return TMED_OK;
 }
@@ -458,11 +443,10 @@ int tmed_test_joint_rows(tmed_ctx *c, const uint8_t *a, const uint8_t *r, const 
   if (e == hipSuccess) e = hipMemcpyAsync(d_in + 64 * n, dneg, n, hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = launch_test_joint_rows(d_in, d_in + 32 * n, d_in + 64 * n, (uint32_t)n, d_rows, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(rows, d_rows, row_bytes, hipMemcpyDeviceToHost, c->stream);
-  const hipError_t es = hipStreamSynchronize(c->stream);
-  if (e == hipSuccess) e = es;
+  const int rc = finish_call(c, c->stream, e);
   if (d_in) (void)hipFree(d_in);
   if (d_rows) (void)hipFree(d_rows);
-  return e == hipSuccess ? TMED_OK : map_err(e);
+  return rc;
 }
 
 // The B tables by the index tmed_test_b_table_entry / tmed_test_table_chain take; false: no
@@ -549,11 +533,10 @@ int tmed_test_table_chain(tmed_ctx *c, int table, uint64_t handle, int radix_bit
   }
   if (e == hipSuccess) e = launch_table_chain(p, d_out, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(h, d_out, sizeof h, hipMemcpyDeviceToHost, c->stream);
-  const hipError_t es = hipStreamSynchronize(c->stream);
-  if (e == hipSuccess) e = es;
+  const int rc = finish_call(c, c->stream, e);
   if (d_out) (void)hipFree(d_out);
   if (copy) (void)hipFree(copy);
-  if (e != hipSuccess) return map_err(e);
+  if (rc != TMED_OK) return rc;
   *rows = h[0];
   *n_bad = h[1];
   for (int i = 0; i < 16; i++) first_bad[i] = h[2 + i];
@@ -570,63 +553,30 @@ int tmed_sign_batch_device(tmed_ctx *c, const uint8_t *d_seeds, const uint8_t *d
   return map_err(launch_sign(d_seeds, d_msgs, d_off, (uint32_t)n, d_sig_out, d_pub_out, c->d_bcomb, s));
 }
 
-static int check_offsets(const uint32_t *off, size_t n) {
-  for (size_t i = 0; i < n; i++)
-    if (off[i + 1] < off[i]) return TMED_EINVAL;
-  return TMED_OK;
-}
-
 int tmed_verify_batch(tmed_ctx *c, const uint8_t *pub, const uint8_t *sig, const uint32_t *sig_lens,
                       const uint8_t *msgs, const uint32_t *off, size_t n, uint8_t *out) {
-  if (!c || !out) return TMED_EINVAL;
-  if (n == 0) return TMED_OK;
-  if (!pub || !sig || !off || n > 0xffffffffu) return TMED_EINVAL;
-  if (check_offsets(off, n) != TMED_OK) return TMED_EINVAL;
+  int rc = check_raw_batch(c, pub, sig, msgs, off, n, out);
+  if (rc != TMED_OK || n == 0) return rc;
   const size_t mbytes = off[n];
-  if (mbytes && !msgs) return TMED_EINVAL;
   std::lock_guard<std::mutex> lk(c->mu);
   hipSetDevice(c->device);
-  hipError_t e = hipSuccess;
-  const size_t moff_bytes = (n + 1) * 4;
-  for (auto &pr : {std::make_pair(&c->d_a, n * 32), std::make_pair(&c->d_b, n * 64),
-                   std::make_pair(&c->d_msg, mbytes + 16), std::make_pair(&c->d_off, moff_bytes),
-                   std::make_pair(&c->d_out, n)})
-    if (e == hipSuccess) e = pr.first->ensure(pr.second);
-  for (auto &pr : {std::make_pair(&c->h_a, n * 32), std::make_pair(&c->h_b, n * 64),
-                   std::make_pair(&c->h_msg, mbytes + 16), std::make_pair(&c->h_off, moff_bytes),
-                   std::make_pair(&c->h_out, n)})
-    if (e == hipSuccess) e = pr.first->ensure(pr.second);
-  if (e != hipSuccess) return map_err(e);
-  // Stage into pinned memory (the caller's buffers may be GC-managed Go memory).
-  memcpy(c->h_a.p, pub, n * 32);
-  memcpy(c->h_b.p, sig, n * 64);
-  if (mbytes) memcpy(c->h_msg.p, msgs, mbytes);
-  memcpy(c->h_off.p, off, moff_bytes);
-  hipStream_t s = c->stream;
-  e = hipMemcpyAsync(c->d_a.p, c->h_a.p, n * 32, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(c->d_b.p, c->h_b.p, n * 64, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && mbytes) e = hipMemcpyAsync(c->d_msg.p, c->h_msg.p, mbytes, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(c->d_off.p, c->h_off.p, moff_bytes, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = scratch_acquire(c, s);
-  // a small (latency-mode) batch skips the kernel-time events unless timing is on: they add
-  // ~8 us to the call (see votes_enqueue)
+  RawStage st;
+  rc = raw_stage(c, 32, n, mbytes, st);
+  if (rc != TMED_OK) return rc;
+  memcpy(st.keys, pub, n * 32);
+  memcpy(st.sigs, sig, n * 64);
+  if (mbytes) memcpy(st.msgs, msgs, mbytes);
+  memcpy(st.off, off, (n + 1) * 4);
+  // a small (latency-mode) batch skips the kernel-time events unless timing is on (last_ms = 0 then)
   const bool timed = c->timing || n > kLatencyUntimedMax;
-  if (e == hipSuccess && timed) e = hipEventRecord(c->ev0, s);
-  if (e == hipSuccess)
-    e = generic_verify(c, (const uint8_t *)c->d_a.p, (const uint8_t *)c->d_b.p, (const uint8_t *)c->d_msg.p,
-                       (const uint32_t *)c->d_off.p, (uint32_t)n, (uint8_t *)c->d_out.p, s, false, nullptr);
-  if (e == hipSuccess && timed) e = hipEventRecord(c->ev1, s);
-  if (e == hipSuccess) e = scratch_release(c, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(c->h_out.p, c->d_out.p, n, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return map_err(e);
-  c->last_ms = 0.f;
-  if (timed) hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1);
-  memcpy(out, c->h_out.p, n);
-  if (sig_lens)
-    for (size_t i = 0; i < n; i++)
-      if (sig_lens[i] != 64) out[i] = 0;  // crypto/ed25519/ed25519.go:150-152
-  return TMED_OK;
+  rc = raw_run(c, st, timed,
+               [&](const uint8_t *d_pub, const uint8_t *d_sig, const uint8_t *d_msg, const uint32_t *d_off, uint32_t m,
+                   uint8_t *d_out, hipStream_t s) {
+                 return map_err(generic_verify(c, d_pub, d_sig, d_msg, d_off, m, d_out, s, false, nullptr));
+               },
+               out, sig_lens);
+  if (rc == TMED_OK) c->last_ms = st.ms;
+  return rc;
 }
 
 int tmed_sign_batch(tmed_ctx *c, const uint8_t *seeds, const uint8_t *msgs, const uint32_t *off, size_t n,
@@ -634,9 +584,8 @@ int tmed_sign_batch(tmed_ctx *c, const uint8_t *seeds, const uint8_t *msgs, cons
   if (!c || !sigs_out || !pubs_out) return TMED_EINVAL;
   if (n == 0) return TMED_OK;
   if (!seeds || !off || n > 0xffffffffu) return TMED_EINVAL;
-  if (check_offsets(off, n) != TMED_OK) return TMED_EINVAL;
+  if (check_offsets(off, n, msgs) != TMED_OK) return TMED_EINVAL;
   const size_t mbytes = off[n];
-  if (mbytes && !msgs) return TMED_EINVAL;
   std::lock_guard<std::mutex> lk(c->mu);
   hipSetDevice(c->device);
   hipError_t e = hipSuccess;
@@ -657,10 +606,7 @@ int tmed_sign_batch(tmed_ctx *c, const uint8_t *seeds, const uint8_t *msgs, cons
   if (e == hipSuccess) e = hipEventRecord(c->ev1, s);
   if (e == hipSuccess) e = hipMemcpyAsync(sigs_out, c->d_b.p, n * 64, hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipMemcpyAsync(pubs_out, c->d_c.p, n * 32, hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return map_err(e);
-  hipEventElapsedTime(&c->last_ms, c->ev0, c->ev1);
-  return TMED_OK;
+  return finish_call(c, s, e, &c->last_ms);
 }
 
 }  // extern "C"

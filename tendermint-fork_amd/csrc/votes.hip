@@ -24,7 +24,7 @@
 #include <vector>
 
 #include "../../include/tmed25519.h"
-#include "ctx.h"
+#include "call_frame.h"
 #include "host_for.h"
 #include "votes_host.h"
 
@@ -84,8 +84,6 @@ namespace {
 
 namespace VH = tmed_votes_host;
 
-size_t valign(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // One group of the call: the requests that share a route and a key set.
 struct VoteGroup {
   bool device;
@@ -129,15 +127,14 @@ int run_group_device(tmed_ctx *c, const tmed_vote_request *reqs, const size_t *b
       n_addr += reqs[q].vals->n;
     }
   }
-  const size_t o_rec = 0, o_step = valign(o_rec + m * kVoteRecBytes), o_addr = valign(o_step + G * sizeof(VoteStep)),
-               o_key = valign(o_addr + 20 * n_addr), o_sig = valign(o_key + m * (ks ? 4 : 32)),
-               o_code = valign(o_sig + m * 64), o_valid = valign(o_code + m), o_slot = valign(o_valid + m),
-               o_len = valign(o_slot + m * kVoteSlot), total = valign(o_len + m * 4);
-  hipError_t e = c->h_vfree.ensure(o_slot);
-  if (e == hipSuccess) e = c->d_vfree.ensure(total);
+  const size_t o_rec = 0, o_step = align256(o_rec + m * kVoteRecBytes), o_addr = align256(o_step + G * sizeof(VoteStep)),
+               o_key = align256(o_addr + 20 * n_addr), o_sig = align256(o_key + m * (ks ? 4 : 32)),
+               o_code = align256(o_sig + m * 64), o_valid = align256(o_code + m), o_slot = align256(o_valid + m),
+               o_len = align256(o_slot + m * kVoteSlot), total = align256(o_len + m * 4);
+  hipError_t e = c->stage.ensure(o_slot, total);  // the slots and lengths stay on the device
   if (e == hipSuccess && !c->vote_ev) e = hipEventCreate(&c->vote_ev);
   if (e != hipSuccess) return map_err(e);
-  uint8_t *h = (uint8_t *)c->h_vfree.p, *d = (uint8_t *)c->d_vfree.p;
+  uint8_t *h = c->stage.host(), *d = c->stage.dev();
   VoteStep *steps = reinterpret_cast<VoteStep *>(h + o_step);
   bool keys_ok = true;
   size_t at = 0;
@@ -173,6 +170,7 @@ int run_group_device(tmed_ctx *c, const tmed_vote_request *reqs, const size_t *b
   hipStream_t s = c->stream;
   e = hipMemcpyAsync(d, h, o_code, hipMemcpyHostToDevice, s);  // one copy in
   if (e == hipSuccess) e = scratch_acquire(c, s);
+  const bool acquired = e == hipSuccess;
   if (e == hipSuccess) e = hipEventRecord(c->ev0, s);
   if (e == hipSuccess)
     e = launch_vote_prepare(VotePrep{reinterpret_cast<const int4 *>(d + o_rec), reinterpret_cast<const VoteStep *>(d + o_step),
@@ -188,13 +186,14 @@ int run_group_device(tmed_ctx *c, const tmed_vote_request *reqs, const size_t *b
                             nullptr);
   }
   if (e == hipSuccess) e = hipEventRecord(c->ev1, s);
-  if (e == hipSuccess) e = scratch_release(c, s);
+  if (acquired) {
+    const hipError_t er = scratch_release(c, s);
+    if (e == hipSuccess) e = er;
+  }
   if (e == hipSuccess) e = hipMemcpyAsync(h + o_code, d + o_code, o_slot - o_code, hipMemcpyDeviceToHost, s);
-  const hipError_t es = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) return map_err(e);
   float ms = 0.f, pms = 0.f;
-  (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
+  const int rc = finish_call(c, s, e, &ms);
+  if (rc != TMED_OK) return rc;
   (void)hipEventElapsedTime(&pms, c->ev0, c->vote_ev);
   c->last_ms += ms;
   c->last_vote_prep_ms += pms;
@@ -216,7 +215,7 @@ int run_group_device(tmed_ctx *c, const tmed_vote_request *reqs, const size_t *b
 int run_group_host(tmed_ctx *c, const tmed_vote_request *reqs, const size_t *base, const VoteGroup &g, Keyset *ks,
                    uint8_t *codes) {
   const size_t m = g.m;
-  std::vector<uint8_t> pre(m), msgs;
+  std::vector<uint8_t> pre(m), valid(m), msgs;
   std::vector<uint32_t> off(m + 1);
   size_t k = 0, pos = 0;
   for (const size_t q : g.reqs) {
@@ -235,51 +234,33 @@ int run_group_host(tmed_ctx *c, const tmed_vote_request *reqs, const size_t *bas
     }
   }
   off[m] = (uint32_t)pos;
-  const size_t kb = m * (ks ? 4 : 32), moff = (m + 1) * 4;
-  hipError_t e = hipSuccess;
-  for (auto &pr : {std::make_pair(&c->d_a, kb), std::make_pair(&c->d_b, m * 64), std::make_pair(&c->d_msg, pos + 16),
-                   std::make_pair(&c->d_off, moff), std::make_pair(&c->d_out, m)})
-    if (e == hipSuccess) e = pr.first->ensure(pr.second);
-  for (auto &pr : {std::make_pair(&c->h_a, kb), std::make_pair(&c->h_b, m * 64), std::make_pair(&c->h_msg, pos + 16),
-                   std::make_pair(&c->h_off, moff), std::make_pair(&c->h_out, m)})
-    if (e == hipSuccess) e = pr.first->ensure(pr.second);
-  if (e != hipSuccess) return map_err(e);
+  RawStage st;
+  int rc = raw_stage(c, ks ? 4 : 32, m, pos, st);
+  if (rc != TMED_OK) return rc;
   k = 0;
   for (const size_t q : g.reqs) {
     const tmed_votes &v = *reqs[q].votes;
     for (size_t i = 0; i < v.n; i++, k++) {
       if (ks) {
-        if (!vote_key_index(*reqs[q].vals, v.validator_indexes[i], ks->n, (uint32_t *)c->h_a.p + k)) return TMED_EINVAL;
+        if (!vote_key_index(*reqs[q].vals, v.validator_indexes[i], ks->n, (uint32_t *)st.keys + k)) return TMED_EINVAL;
       } else {
-        vote_key_bytes(*reqs[q].vals, v.validator_indexes[i], (uint8_t *)c->h_a.p + 32 * k);
+        vote_key_bytes(*reqs[q].vals, v.validator_indexes[i], st.keys + 32 * k);
       }
-      vote_sig(v, i, (uint8_t *)c->h_b.p + 64 * k);
+      vote_sig(v, i, st.sigs + 64 * k);
     }
   }
-  if (pos) memcpy(c->h_msg.p, msgs.data(), pos);
-  memcpy(c->h_off.p, off.data(), moff);
-  hipStream_t s = c->stream;
-  e = hipMemcpyAsync(c->d_a.p, c->h_a.p, kb, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(c->d_b.p, c->h_b.p, m * 64, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess && pos) e = hipMemcpyAsync(c->d_msg.p, c->h_msg.p, pos, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(c->d_off.p, c->h_off.p, moff, hipMemcpyHostToDevice, s);
-  if (e == hipSuccess) e = scratch_acquire(c, s);
-  if (e == hipSuccess) e = hipEventRecord(c->ev0, s);
-  if (e == hipSuccess)
-    e = ks ? keyset_verify_batch(c, *ks, (const uint32_t *)c->d_a.p, (const uint8_t *)c->d_b.p, (const uint8_t *)c->d_msg.p,
-                                 (const uint32_t *)c->d_off.p, (uint32_t)m, (uint8_t *)c->d_out.p, s, /*msg_slots=*/false)
-           : generic_verify(c, (const uint8_t *)c->d_a.p, (const uint8_t *)c->d_b.p, (const uint8_t *)c->d_msg.p,
-                            (const uint32_t *)c->d_off.p, (uint32_t)m, (uint8_t *)c->d_out.p, s, /*msg_slots=*/false, nullptr);
-  if (e == hipSuccess) e = hipEventRecord(c->ev1, s);
-  if (e == hipSuccess) e = scratch_release(c, s);
-  if (e == hipSuccess) e = hipMemcpyAsync(c->h_out.p, c->d_out.p, m, hipMemcpyDeviceToHost, s);
-  const hipError_t es = hipStreamSynchronize(s);
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) return map_err(e);
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
-  c->last_ms += ms;
-  const uint8_t *valid = (const uint8_t *)c->h_out.p;
+  if (pos) memcpy(st.msgs, msgs.data(), pos);
+  memcpy(st.off, off.data(), (m + 1) * 4);
+  rc = raw_run(c, st, /*timed=*/true,
+               [&](const uint8_t *d_key, const uint8_t *d_sig, const uint8_t *d_msg, const uint32_t *d_off, uint32_t n,
+                   uint8_t *d_out, hipStream_t s) {
+                 return map_err(ks ? keyset_verify_batch(c, *ks, (const uint32_t *)d_key, d_sig, d_msg, d_off, n, d_out, s,
+                                                         /*msg_slots=*/false)
+                                   : generic_verify(c, d_key, d_sig, d_msg, d_off, n, d_out, s, /*msg_slots=*/false, nullptr));
+               },
+               valid.data(), nullptr);
+  if (rc != TMED_OK) return rc;
+  c->last_ms += st.ms;
   k = 0;
   for (const size_t q : g.reqs) {
     const tmed_votes &v = *reqs[q].votes;
