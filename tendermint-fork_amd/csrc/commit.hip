@@ -11,7 +11,7 @@
 //      loops, the ForBlock prefix up to the crossing computed as if every signature were
 //      valid (if one in that prefix is invalid the loop stops there anyway; if none is,
 //      it stops at the crossing), and for Trusting also up to the first double vote
-//   3. CanonicalVote sign-bytes (signbytes.hip), ONE device batch (tmed_verify_batch)
+//   3. CanonicalVote sign-bytes (signbytes.hip over vote_wire.h), ONE device batch (tmed_verify_batch)
 //   4. replay of the reference loop over the validity bits — first-error index, early
 //      exit, Got/Needed and error kinds come out identical by construction.
 #include <atomic>

@@ -167,8 +167,8 @@ __global__ __launch_bounds__(kHsBlock, kPrepWaves) void verify_prep_kernel(
 }
 
 // ---- f1: CanonicalVote sign-bytes assembled on the device ----------
-// (votes_dev.h assemble_vote_into; this kernel serves the throughput and key-cached paths, the
-// latency kernels assemble in their hash lanes.)  One wave per block: every lane assembles its
+// (votes_dev.h assemble_vote_into: vote_wire.h's vote_splice on the staged template; this kernel
+// serves the throughput and key-cached paths, the latency kernels assemble in their hash lanes.)  One wave per block: every lane assembles its
 // vote in LDS (byte stores to LDS, beside its staged template), then the wave writes its 64
 // consecutive 256-B slots as sixteen coalesced 1-KB rows.  Assembled straight into the global
 // slots, each lane's ~114 byte stores went to 64 different lines per instruction: 0.29 ms per

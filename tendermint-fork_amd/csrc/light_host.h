@@ -21,13 +21,14 @@
 #include <vector>
 
 #include "../../include/tmed25519.h"
+#include "vote_wire.h"
 
 namespace tmed_light {
 
-// gogoproto StdTime's range (validateTimestamp): the range in which Time.Add of an int64-nanosecond
-// duration cannot overflow and outside which the reference's own marshalling fails.
-constexpr int64_t kMinSeconds = -62135596800ll;  // 0001-01-01T00:00:00Z, Go's zero time
-constexpr int64_t kMaxSeconds = 253402300800ll;  // 10000-01-01T00:00:00Z (exclusive)
+// gogoproto StdTime's range (vote_wire.h timestamp_encodable): the range in which Time.Add of an
+// int64-nanosecond duration cannot overflow and outside which the reference's own marshalling fails.
+using tmed::kMaxSeconds;
+using tmed::kMinSeconds;
 constexpr int64_t kNanos = 1000000000ll;
 
 // Go's time.Time as (Unix seconds, nanoseconds in [0, 1e9)): wall-clock comparisons only.
@@ -35,7 +36,7 @@ struct GoTime {
   int64_t sec;
   int32_t nsec;
 };
-inline bool time_ok(GoTime t) { return t.sec >= kMinSeconds && t.sec < kMaxSeconds && t.nsec >= 0 && t.nsec < kNanos; }
+inline bool time_ok(GoTime t) { return tmed::timestamp_encodable(t.sec, t.nsec); }
 // Time.Add (time/time.go): d / 1e9 and d % 1e9 truncate toward zero in Go as in C++.
 inline GoTime time_add(GoTime t, int64_t d) {
   int64_t sec = t.sec + d / kNanos;

@@ -18,19 +18,12 @@
 #include "../../include/tmed25519.h"
 #include "keycache.h"  // AddrIndex: GetByAddress as a hash lookup, first match in set order
 
-#ifndef TMED_HD
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define TMED_HD __host__ __device__ __forceinline__
-#else
-#define TMED_HD static inline
-#endif
-#endif
+#include "vote_wire.h"  // TMED_HD; the zero time
 
 namespace tmed_median {
 
 constexpr int64_t kNanos = 1000000000ll;
-constexpr int64_t kZeroTimeSeconds = -62135596800ll;  // time.Time{}.Unix(): 0001-01-01T00:00:00Z
+constexpr int64_t kZeroTimeSeconds = tmed::kMinSeconds;  // time.Time{}.Unix(): 0001-01-01T00:00:00Z
 
 // Time.UnixNano() = seconds * 1e9 + nanos (the sort key, time.go:46) when that is an int64 and nanos
 // is a Time's nanosecond field; false otherwise (Go's UnixNano is then undefined: GO_PATH).

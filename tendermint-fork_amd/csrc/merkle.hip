@@ -46,6 +46,7 @@
 #include "merkle_levels.h"
 #include "merkle_path.h"
 #include "sha256.h"
+#include "vote_wire.h"
 
 namespace tmed {
 
@@ -441,8 +442,8 @@ int split_parts(const uint8_t *data, const uint64_t *data_off, size_t n_blocks, 
 
 // gogoproto varint / field helpers for the header leaves (types/block.go:440-475)
 void put_varint(std::vector<uint8_t> &o, uint64_t v) {
-  while (v >= 0x80) { o.push_back((uint8_t)(v | 0x80)); v >>= 7; }
-  o.push_back((uint8_t)v);
+  uint8_t b[10];
+  o.insert(o.end(), b, b + put_uvarint(b, 0, v));
 }
 void put_bytes_field(std::vector<uint8_t> &o, uint8_t tag, const uint8_t *p, size_t n) {
   o.push_back(tag);
@@ -525,11 +526,6 @@ int roots_from_host_leaves_locked(tmed_ctx *c, const uint8_t *leaves, const uint
 }
 
 // ---- Commit.Hash (types/block.go:894-912) ---------------------------------------------------
-// StdTimeMarshal's range (gogoproto timestamp.go validateTimestamp): outside it the reference's
-// Marshal fails and Commit.Hash panics.
-constexpr int64_t kMinTimeSeconds = -62135596800ll;  // 0001-01-01T00:00:00Z, Go's zero time
-constexpr int64_t kMaxTimeSeconds = 253402300800ll;  // 10000-01-01T00:00:00Z (exclusive)
-
 // The commits' arrays of one call, packed per kind: region offsets for N signatures.
 struct CsigLayout {
   size_t sig, sec, meta, nanos, addr, roots, total;
@@ -556,9 +552,8 @@ int commit_scan(const tmed_commit &cm) {
     any_sig |= sl != 0;
     any_addr |= al == 20;
     ok &= sl <= 64 && (al == 0 || al == 20);
-    const int64_t s = cm.ts_seconds[j];
-    const int32_t ns = cm.ts_nanos[j];
-    ok &= s >= kMinTimeSeconds && s < kMaxTimeSeconds && ns >= 0 && ns < 1000000000;
+    // outside StdTimeMarshal's range the reference's Marshal fails and Commit.Hash panics
+    ok &= timestamp_encodable(cm.ts_seconds[j], cm.ts_nanos[j]);
   }
   if ((any_addr && !cm.addresses) || (ok && any_sig && !cm.sigs)) return TMED_EINVAL;
   return ok ? 1 : 0;

@@ -321,6 +321,22 @@ struct CandBatch {
 using BatchVerifier =
     std::function<int(const tmed_commit_request *reqs, size_t n, const Cands &cands, uint8_t *valid)>;
 
+// What Commit.GetVote (types/block.go:784-796) copies from the request's commit into each of its votes.
+static tmed_vote_template vote_template_of(const tmed_commit_request &rq) {
+  const tmed_commit &c = *rq.commit;
+  tmed_vote_template t;
+  t.chain_id = rq.chain_id;
+  t.chain_id_len = rq.chain_id_len;
+  t.height = c.height;
+  t.round = c.round;
+  t.block_hash = c.block_id.hash;
+  t.block_hash_len = c.block_id.hash_len;
+  t.psh_total = c.block_id.psh_total;
+  t.psh_hash = c.block_id.psh_hash;
+  t.psh_hash_len = c.block_id.psh_hash_len;
+  return t;
+}
+
 // Per-request CanonicalVote encoders for the requests that have candidates; then(q, enc)
 // runs right after request q's encoder is built (false = failure).  Candidates are in request
 // order, so the first candidate of each request marks it used (one writer per request).
@@ -335,17 +351,7 @@ static int init_encoders(const tmed_commit_request *reqs, size_t n, const Cands 
   parallel_ranges(n, n >= 64 ? host_threads(m) : 1, [&](size_t lo, size_t hi, unsigned) {
   for (size_t q = lo; q < hi; q++) {
     if (!used[q]) continue;
-    const tmed_commit &c = *reqs[q].commit;
-    tmed_vote_template t;
-    t.chain_id = reqs[q].chain_id;
-    t.chain_id_len = reqs[q].chain_id_len;
-    t.height = c.height;
-    t.round = c.round;
-    t.block_hash = c.block_id.hash;
-    t.block_hash_len = c.block_id.hash_len;
-    t.psh_total = c.block_id.psh_total;
-    t.psh_hash = c.block_id.psh_hash;
-    t.psh_hash_len = c.block_id.psh_hash_len;
+    const tmed_vote_template t = vote_template_of(reqs[q]);
     if (enc[q].init(&t) != TMED_OK || !then(q, enc[q])) bad = 1;
   }
   });
@@ -1073,17 +1079,7 @@ static void for_segments(const Cands &c, const Group &g, size_t lo, size_t hi, F
 // Request q's template row (kVoteTmplBytes at row); false: the encoder rejected the request
 // (bad), or *fit = false when its template does not fit the device assembler.
 static bool template_row(const tmed_commit_request &rq, uint8_t *row, bool *fit) {
-  const tmed_commit &c = *rq.commit;
-  tmed_vote_template t;
-  t.chain_id = rq.chain_id;
-  t.chain_id_len = rq.chain_id_len;
-  t.height = c.height;
-  t.round = c.round;
-  t.block_hash = c.block_id.hash;
-  t.block_hash_len = c.block_id.hash_len;
-  t.psh_total = c.block_id.psh_total;
-  t.psh_hash = c.block_id.psh_hash;
-  t.psh_hash_len = c.block_id.psh_hash_len;
+  const tmed_vote_template t = vote_template_of(rq);
   tmed::VoteEncoder e;
   if (e.init(&t) != TMED_OK) return false;
   memset(row, 0, tmed::kVoteTmplBytes);

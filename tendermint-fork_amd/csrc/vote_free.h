@@ -5,27 +5,17 @@
 // vote, tmed_votes_sign_bytes / tmed_verify_votes_host (votes_host.h) and tests/native/votes_host.cpp
 // run it lane by lane on the CPU.
 //
-// The bytes, field for field (types/vote.go:93-101 = protoio.MarshalDelimited(CanonicalizeVote)):
-//   uvarint(len(body))                      libs/protoio/writer.go:93-100
-//   08 uvarint(uint64(int64(type)))         only if type != 0 (canonical.pb.go:517-579; an int32: a
-//                                           negative type is ten bytes)
-//   11 le64(height)                         sfixed64, only if height != 0
-//   19 le64(int64(round))                   sfixed64, only if round != 0 (canonical.go:56-65)
-//   22 len {[0a 20 hash] 12 len {[08 uvarint(total)] [12 20 psh_hash]}}
-//                                           only if the BlockID is not zero: hash, total and part-set
-//                                           hash not all empty / 0 (canonical.go:18-34; :370-428).  The
-//                                           inner PartSetHeader field is always there (non-nullable);
-//                                           an incomplete BlockID encodes as Go encodes it
-//   2a len {[08 uvarint(seconds)] [10 uvarint(int64(nanos))]}   ALWAYS (gogoproto StdTime)
-//   32 len chain_id                         only if len(chain_id) > 0
-// A hash or part-set hash whose length is neither 0 nor 32 makes CanonicalizeBlockID panic
-// (BlockIDFromProto -> ValidateBasic -> ValidateHash): vote_bid_malformed, nothing is encoded.
+// The bytes are vote_wire.h's, field for field: the head from the vote's type, height and round, the
+// BlockID field from its hash, total and part-set hash, the timestamp, the chain ID.  A hash or
+// part-set hash whose length is neither 0 nor 32 makes CanonicalizeBlockID panic (BlockIDFromProto ->
+// ValidateBasic -> ValidateHash): vote_bid_malformed, nothing is encoded.
 #pragma once
 #include <stdint.h>
 #include <string.h>
 
 #include "sha256.h"
 #include "signbytes.h"
+#include "vote_wire.h"
 
 namespace tmed {
 
@@ -36,13 +26,12 @@ constexpr uint8_t kVoteOk = 0, kVoteIndexNegative = 1, kVoteAddressEmpty = 2, kV
 constexpr uint32_t kVoteFlagAddVote = 1;  // TMED_VOTES_ADDVOTE
 
 // The longest message of a vote whose chain ID has at most kVoteChainMax bytes (MaxChainIDLen,
-// types/genesis.go): type 1 + 10, height 1 + 8, round 1 + 8, BlockID 2 + {hash 2 + 32, part-set
-// header 2 + {total 1 + 5 (a uint32), hash 2 + 32}} = 78, timestamp 2 + {1 + 10, 1 + 10} = 24,
+// types/genesis.go): every field at vote_wire.h's longest (head 29, BlockID 78, timestamp 24) and
 // chain ID 2 + 50: a body of 183 bytes behind a two-byte length.  Such votes are assembled on the
 // device, each into its kVoteSlot-byte slot; a request with a longer chain ID is assembled on the
 // host by the same source (votes.hip), as VoteEncoder::device_template rules for commits.
 constexpr uint32_t kVoteChainMax = 50;
-constexpr uint32_t kVoteFreeFixedMax = 11 + 9 + 9 + 78 + 24;
+constexpr uint32_t kVoteFreeFixedMax = kVoteHeadMax + kBlockIdFieldMax + kTimestampFieldMax;
 constexpr uint32_t kVoteFreeBodyMax = kVoteFreeFixedMax + 2 + kVoteChainMax;
 constexpr uint32_t kVoteFreeMsgMax = 2 + kVoteFreeBodyMax;
 static_assert(kVoteChainMax < 128 && kVoteFreeBodyMax >= 128 && kVoteFreeBodyMax < (1u << 14),
@@ -86,79 +75,26 @@ struct VoteStep {
 };
 static_assert(sizeof(VoteStep) == 96, "VoteStep layout");
 
-TMED_HD uint32_t vf_uvarint_len(uint64_t v) {
-  uint32_t n = 1;
-  while (v >= 0x80) { v >>= 7; n++; }
-  return n;
-}
-TMED_HD uint32_t vf_put_uvarint(uint8_t *p, uint32_t pos, uint64_t v) {
-  while (v >= 0x80) { p[pos++] = (uint8_t)(v | 0x80); v >>= 7; }
-  p[pos++] = (uint8_t)v;
-  return pos;
-}
-TMED_HD uint32_t vf_put_le64(uint8_t *p, uint32_t pos, uint64_t v) {
-  for (int i = 0; i < 8; i++) p[pos++] = (uint8_t)(v >> (8 * i));
-  return pos;
-}
-
 TMED_HD bool vote_bid_malformed(const VoteRec &r) {
   return (r.hash_len != 0 && r.hash_len != 32) || (r.psh_len != 0 && r.psh_len != 32);
 }
 
-// Field sizes of a vote whose BlockID is not malformed.
-struct VoteSizes {
-  uint32_t psh_body, bid_body, ts_body, body;
-};
-TMED_HD VoteSizes vote_free_sizes(const VoteRec &r, uint32_t cid_len) {
-  VoteSizes z;
-  const uint64_t s = (uint64_t)r.sec, ns = (uint64_t)(int64_t)r.nanos;
-  z.psh_body = (r.psh_total ? 1 + vf_uvarint_len(r.psh_total) : 0) + (r.psh_len ? 2 + 32 : 0);
-  const bool zero = r.hash_len == 0 && r.psh_total == 0 && r.psh_len == 0;
-  z.bid_body = zero ? 0 : (r.hash_len ? 2 + 32 : 0) + 1 + vf_uvarint_len(z.psh_body) + z.psh_body;
-  z.ts_body = (s ? 1 + vf_uvarint_len(s) : 0) + (ns ? 1 + vf_uvarint_len(ns) : 0);
-  z.body = (r.type ? 1 + vf_uvarint_len((uint64_t)(int64_t)r.type) : 0) + (r.height ? 9 : 0) + (r.round ? 9 : 0) +
-           (zero ? 0 : 1 + vf_uvarint_len(z.bid_body) + z.bid_body) + 1 + vf_uvarint_len(z.ts_body) + z.ts_body +
-           (cid_len ? 1 + vf_uvarint_len(cid_len) + cid_len : 0);
-  return z;
+// The body and the length of the sign-bytes of a vote whose BlockID is not malformed.
+TMED_HD uint32_t vote_free_body(const VoteRec &r, uint32_t cid_len) {
+  return vote_body_len(vote_head_len(r.type, r.height, r.round), block_id_field_len(r.hash_len, r.psh_total, r.psh_len),
+                       timestamp_field_len(r.sec, r.nanos), chain_id_field_len(cid_len));
 }
-TMED_HD uint32_t vote_free_size(const VoteRec &r, uint32_t cid_len) {
-  const uint32_t body = vote_free_sizes(r, cid_len).body;
-  return vf_uvarint_len(body) + body;
-}
+TMED_HD uint32_t vote_free_size(const VoteRec &r, uint32_t cid_len) { return vote_msg_len(vote_free_body(r, cid_len)); }
 
 // The vote's sign-bytes into o (vote_free_size bytes; the BlockID is not malformed); returns the length.
+// vote_splice's message with the three ranges written in place instead of copied: a lane of
+// vote_prepare_kernel has nowhere to stage them.
 TMED_HD uint32_t vote_free_write(const VoteRec &r, const uint8_t *chain, uint32_t cid_len, uint8_t *o) {
-  const VoteSizes z = vote_free_sizes(r, cid_len);
-  const uint64_t s = (uint64_t)r.sec, ns = (uint64_t)(int64_t)r.nanos;
-  uint32_t p = vf_put_uvarint(o, 0, z.body);
-  if (r.type) { o[p++] = 0x08; p = vf_put_uvarint(o, p, (uint64_t)(int64_t)r.type); }
-  if (r.height) { o[p++] = 0x11; p = vf_put_le64(o, p, (uint64_t)r.height); }
-  if (r.round) { o[p++] = 0x19; p = vf_put_le64(o, p, (uint64_t)(int64_t)r.round); }
-  if (z.bid_body) {  // never 0 for a non-zero BlockID: the PartSetHeader field alone is two bytes
-    o[p++] = 0x22;
-    p = vf_put_uvarint(o, p, z.bid_body);
-    if (r.hash_len) {
-      o[p++] = 0x0a; o[p++] = 32;
-      for (int j = 0; j < 32; j++) o[p++] = r.hash[j];
-    }
-    o[p++] = 0x12;
-    p = vf_put_uvarint(o, p, z.psh_body);
-    if (r.psh_total) { o[p++] = 0x08; p = vf_put_uvarint(o, p, r.psh_total); }
-    if (r.psh_len) {
-      o[p++] = 0x12; o[p++] = 32;
-      for (int j = 0; j < 32; j++) o[p++] = r.psh[j];
-    }
-  }
-  o[p++] = 0x2a;
-  p = vf_put_uvarint(o, p, z.ts_body);
-  if (s) { o[p++] = 0x08; p = vf_put_uvarint(o, p, s); }
-  if (ns) { o[p++] = 0x10; p = vf_put_uvarint(o, p, ns); }
-  if (cid_len) {
-    o[p++] = 0x32;
-    p = vf_put_uvarint(o, p, cid_len);
-    for (uint32_t j = 0; j < cid_len; j++) o[p++] = chain[j];
-  }
-  return p;
+  uint32_t p = put_uvarint(o, 0, vote_free_body(r, cid_len));
+  p = put_vote_head(o, p, r.type, r.height, r.round);
+  p = put_block_id_field(o, p, r.hash_len ? r.hash : nullptr, r.psh_total, r.psh_len ? r.psh : nullptr);
+  p = put_timestamp_field(o, p, r.sec, r.nanos);
+  return put_chain_id_field(o, p, chain, cid_len);
 }
 
 // PubKey.Address() = SHA-256(key)[:20] (crypto/ed25519/ed25519.go:136-141, crypto/tmhash
@@ -183,13 +119,6 @@ TMED_HD bool vote_address_of_key(const VoteRec &r, const uint32_t pubw[8]) {
   return diff == 0;
 }
 
-// google.protobuf.Timestamp's range (gogoproto validateTimestamp, which StdTimeMarshal runs): outside
-// it MarshalDelimited fails and VoteSignBytes panics (types/vote.go:95-98); a Go time.Time holds no
-// nanos outside [0, 1e9), so such a struct is no vote the reference could have seen.
-TMED_HD bool vote_time_encodable(const VoteRec &r) {
-  return r.sec >= -62135596800ll && r.sec < 253402300800ll && r.nanos >= 0 && r.nanos < 1000000000;
-}
-
 // The checks in front of the signature, in the reference's order; 0 = the signature decides.
 //   1 valIndex < 0                                             types/vote_set.go:165
 //   2 len(valAddr) == 0                          (ADDVOTE)     :167
@@ -200,7 +129,8 @@ TMED_HD bool vote_time_encodable(const VoteRec &r) {
 //     stays in Go)
 //   6 !bytes.Equal(pubKey.Address(), vote.ValidatorAddress)    types/vote.go:148
 //   7 CanonicalizeBlockID panics on a malformed hash           types/canonical.go:19-22
-//   then the Timestamp's range (vote_time_encodable): kVoteGoPath
+//   then the Timestamp's range (vote_wire.h timestamp_encodable: VoteSignBytes panics outside it,
+//   types/vote.go:95-98, and a Go time.Time holds no such nanos): kVoteGoPath
 // set_addr: the request's set addresses (n_vals x 20; read only under ADDVOTE); key(w): loads the
 // eight words of the key at val_index (called only when checks 1-5 passed).
 template <class KeyFn>
@@ -221,7 +151,7 @@ TMED_HD uint8_t vote_prechecks(const VoteRec &r, const VoteStep &s, const uint8_
   key(pubw);
   if (!vote_address_of_key(r, pubw)) return kVoteAddressNotOfKey;
   if (vote_bid_malformed(r)) return kVotePanic;
-  if (!vote_time_encodable(r)) return kVoteGoPath;
+  if (!timestamp_encodable(r.sec, r.nanos)) return kVoteGoPath;
   return 0;
 }
 

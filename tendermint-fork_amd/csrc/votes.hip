@@ -1,6 +1,6 @@
 // votes.hip — free-standing votes on gfx950: vote_prepare_kernel and the device batch of
-// tmed_verify_votes (include/tmed25519.h states the call; vote_free.h is the encoder and the checks,
-// shared with the host; votes_host.h the host entries).
+// tmed_verify_votes (include/tmed25519.h states the call; vote_free.h is the encoder, over the field
+// writers of vote_wire.h, and the checks, shared with the host; votes_host.h the host entries).
 //
 // vote_prepare_kernel: one lane per vote, one wavefront per workgroup of 64 votes, laid out like
 // assemble_votes_kernel (kernels.hip).  A lane stages its 144-byte record (VoteRec, nine 16-byte

@@ -1,5 +1,5 @@
 // votes_host.h — free-standing votes on the host: the request checks of tmed_verify_votes, the
-// staging of a vote into the record vote_free.h reads, and the host entries tmed_votes_sign_bytes /
+// staging of a vote into the record vote_free.h reads (its bytes: vote_wire.h), and the host entries tmed_votes_sign_bytes /
 // tmed_verify_votes_host, which run the shared source lane by lane with no device (votes.hip holds
 // the kernel and the device batch; tests/native/votes_host.cpp compiles this header on its own).
 #pragma once

@@ -2,7 +2,7 @@
 
 Product-side counterpart of ``Commit.VoteSignBytes`` (reference
 ``types/block.go:807-810`` -> ``types/vote.go:93-101``); see
-``csrc/signbytes.hip`` for the byte layout and citations.
+``csrc/vote_wire.h`` for the byte layout and citations.
 """
 from __future__ import annotations
 

@@ -17,8 +17,10 @@ year 9999, psh_total >= 2^28 (a 5-byte varint), heights >= 2^56, round 2^31 - 1,
 round 0 (fields omitted), an empty and a 50-byte chain ID (the genesis maximum,
 types/genesis.go:21), Nil and Absent flags; a 120-byte chain ID still takes the device template
 and a 140-byte one the host-assembled path (its longest message would overflow the 256-byte
-device vote slot).  A generic tmed_verify_batch case with 1-4 KB messages covers the SHA-512
-block loop past the vote sizes."""
+device vote slot); with every per-commit field at its longest, a 129-byte chain ID is the last the
+device template takes (its longest vote fills the slot) and a 130-byte one the first it refuses.
+A generic tmed_verify_batch case with 1-4 KB messages covers the SHA-512 block loop past the vote
+sizes."""
 import numpy as np
 import pytest
 
@@ -41,6 +43,9 @@ COMMITS = [  # chain, height, round, psh_total, flags
     ("x" * 120, (1 << 62) + 1, 3, (1 << 32) - 1, None),
     ("y" * 140, 77, 1, 123, None),
     ("test_chain_id", 9, 0, 123, [C.FLAG_NIL] * 3 + [C.FLAG_COMMIT] * 9),
+    # the template-fit boundary, every per-commit field at its longest (tests/native/vote_wire_host.cpp)
+    ("f" * 129, (1 << 63) - 1, (1 << 31) - 1, (1 << 32) - 1, None),
+    ("g" * 130, (1 << 63) - 1, (1 << 31) - 1, (1 << 32) - 1, None),
 ]
 
 

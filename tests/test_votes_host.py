@@ -3,7 +3,9 @@ vote_prepare_kernel compiles) byte for byte against oracle.signbytes over the re
 full product of field values and the length boundaries; agreement with tmed_vote_sign_bytes on
 precommits; tmed_verify_votes_host's codes against the restatement of tests/vote_cases.py; the same
 code as a stand-alone program under AddressSanitizer and UndefinedBehaviorSanitizer
-(tests/native/votes_host.cpp); the static check of the Go binding.  The device run of the same corpus
+(tests/native/votes_host.cpp); the device splice of the commit seam on the CPU against the commit
+encoder, the free-standing encoder and the oracle (tests/native/vote_wire_host.cpp); the static check
+of the Go binding.  The device run of the same corpus
 is tests/test_gpu_votes.py."""
 import itertools
 import json
@@ -301,6 +303,43 @@ def test_checks_under_sanitizers(votes_host, requests, tmp_path):
         code, mlen = [int(x) for x in line.split()]
         assert code == _pre(e)
         assert mlen == (len(VC.sign_bytes(r.chain_id, v)) if code == 0 else 0)
+
+
+@pytest.fixture(scope="module")
+def wire_cases():
+    """The cases of tests/native/vote_wire_host.cpp in its order, with the oracle's bytes: flags 1-3 over the
+    product of BlockIDs, heights, rounds, chain-ID lengths, seconds and nanos (any int32 crosses the ABI),
+    bodies of 127 and 128 bytes, and the longest chain ID the device template takes (129) and one more."""
+    bids = [(b"", 0, b""), (H32, 0, b""), (b"", 0, P32), (H32, 123, P32), (b"", 1, b""), (H32, 2**32 - 1, P32)]
+    cases = [(cl, h, r, bid, flag, (s, ns)) for bid, h, r, cl, s, ns, flag in itertools.product(
+        bids, [0, 1, 2**63 - 1], [0, 1, 2**31 - 1], [0, 13, 50, 127, 128], [0, 1, -62135596800, 253402300799],
+        [0, 1, 999999999, -1], [1, 2, 3])]
+    cases += [(cl, 0, 0, bids[0], 1, (0, 0)) for cl in (121, 122)]
+    cases += [(cl, 2**63 - 1, 2**31 - 1, bids[5], flag, (-1, -1)) for flag in (1, 2, 3) for cl in (129, 130)]
+    want = [vote_sign_bytes("c" * cl, 2, h, r, bid if flag == 2 else None, ts) for cl, h, r, bid, flag, ts in cases]
+    return cases, want
+
+
+@pytest.mark.parametrize("san", [[], ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]],
+                         ids=["plain", "sanitizers"])
+def test_device_splice_on_the_host(san, wire_cases, tmp_path):
+    """vote_splice on the device_template record (what assemble_vote_into runs once the record is staged)
+    == VoteEncoder::write == vote_free_write inside the program; its messages == the oracle's here."""
+    cases, want = wire_cases
+    exe = str(tmp_path / "vote_wire_host")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", *san, "-Wno-unknown-pragmas", "-I", CSRC,
+                           os.path.join(ROOT, "tests", "native", "vote_wire_host.cpp"),
+                           "-x", "c++", os.path.join(CSRC, "signbytes.hip"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = out.stdout.split()
+    assert lines[-3:] == ["wire-ok", str(len(cases)), "257"] and len(lines) == len(cases) + 3
+    for k, (line, w) in enumerate(zip(lines, want)):
+        assert line == w.hex(), cases[k]
+    lens = {(cl, flag): len(w) for (cl, _, _, _, flag, _), w in zip(cases, want)}
+    assert lens[129, 2] == 256 and lens[130, 2] == 257  # a slot is 256 bytes
+    bodies = {cl: len(w) for (cl, *_), w in zip(cases, want) if cl in (121, 122)}
+    assert bodies == {121: 1 + 127, 122: 2 + 128}
 
 
 def test_go_binding_static_check():
