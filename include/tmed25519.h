@@ -323,6 +323,35 @@ int tmed_test_zip_msm(tmed_ctx *ctx, uint32_t n, const uint8_t *points, const in
                       uint32_t lo, uint32_t cnt, int32_t windows[640], uint32_t ctot[8], uint32_t *flag);
 
 /*
+ * Tests only (tests/test_gpu_keyed_stages.py): two stages of the key-cached throughput route, run by
+ * the product's own launchers on the context's own scratch buffers.
+ *
+ * tmed_test_key_order: the key-grouped visiting order (csrc/kernels.hip launch_key_order: the
+ * counting sort of one chunk's key indexes) of val_idx[0..n), 1 <= n <= 2^20, over a key set of
+ * nkeys keys (no key set is needed: only the number counts).  The context's order scratch is sized
+ * as a key-cached batch sizes it, its permutation region filled with 0xFFFFFFFF, and the launcher
+ * run with index_base.  perm_out: n entries, index_base + i for every i of [0, n), grouped by bin
+ * (v >> *shift_out; every v >= nkeys in the last bin).  cursor_out: room for 4096 words; the first
+ * *nbins_out hold the scratch words after the scatter, bin b's being the end of bin b in perm_out.
+ * TMED_EINVAL: n = 0 or n > 2^20, nkeys = 0 or nkeys > 2^24 (the launcher refuses those),
+ * index_base + n past 32 bits.
+ *
+ * tmed_test_finish: the batched finish (launch_finish, verify_finish_kernel, verify_core.h
+ * finish_group) of m <= 2^20 projective points a caller gives.  xyz: m x 30 int32, the limbs of X, Y,
+ * Z (10 each, radix 2^25.5) of position p, written into fin slot p in the layout the main kernels
+ * write.  r: m x 32 bytes, position p's R, written as the R half of signature row fin_base + p, or
+ * perm[fin_base + p] when perm (fin_base + m entries, each below fin_base + m) is not NULL.
+ * bits_in: m bytes, the bit `out` holds for position p before the finish.  bits_out: fin_base + m
+ * bytes, `out` after the finish: position p's byte is bits_in && Z != 0 && enc(X/Z, Y/Z) == r at
+ * that same index; a byte no position owns is 0xAA.
+ * TMED_EINVAL: m = 0, m > 2^20, fin_base + m > 2^21, a perm entry out of range.
+ */
+int tmed_test_key_order(tmed_ctx *ctx, const uint32_t *val_idx, uint32_t n, uint32_t nkeys, uint32_t index_base,
+                        uint32_t *perm_out, uint32_t *cursor_out, uint32_t *nbins_out, uint32_t *shift_out);
+int tmed_test_finish(tmed_ctx *ctx, uint32_t m, const int32_t *xyz, const uint8_t *r, const uint32_t *perm,
+                     uint32_t fin_base, const uint8_t *bits_in, uint8_t *bits_out);
+
+/*
  * With TMED_DEBUG_ZERO set at the first pipelined generic batch: every staged candidate whose
  * device bit is 0 is recorded (request, signature, staging position, the staged and the device
  * copies of its key and signature, the assembled sign-bytes).  Copies up to cap records into out

@@ -45,6 +45,15 @@ constexpr uint32_t kFinGroupMax = 16;
 constexpr uint32_t kFinPreStride = kFinCap + 64;
 constexpr size_t kFinBytes = (size_t)kFinCap * kFinInt4 * 16;
 constexpr size_t kFinPreBytes = (size_t)kFinPreStride * 3 * 16;
+// The finish of the m <= kFinCap signatures whose R' are in fin slots [0, m): slot p belongs to
+// signature fin_base + p, or perm[fin_base + p] (the key-grouped order); out[i] &= enc(R') == R.
+hipError_t launch_finish(const int4 *fin, int4 *pre, const uint8_t *sig, uint8_t *out, uint32_t fin_base, uint32_t m,
+                         hipStream_t stream, const uint32_t *perm = nullptr);
+// Tests (tmed_test_finish): m rows of 30 int32 limbs (X, Y, Z) into fin slots [0, m) in fin_store's
+// layout, each row's 32-byte R into the R half of its signature row and its bit into out.
+hipError_t launch_test_fin_fill(const int32_t *xyz, const uint8_t *r, const uint8_t *bits, const uint32_t *perm,
+                                uint32_t fin_base, uint32_t m, int4 *fin, uint8_t *sig, uint8_t *out,
+                                hipStream_t stream);
 
 // The shared B tables of the generic main kernels: the radix-2^16 table of j*B (full-length
 // fallback, variant 5) and the radix-2^16 comb of B (windows 0 and 8: the half-size default).
@@ -162,6 +171,8 @@ hipError_t launch_verify_keyset(const uint32_t *val_idx, uint32_t nkeys, const u
 // come from few keys (TLB / L2 locality across a multi-GB key set).
 constexpr uint32_t kKeyOrderMaxKeys = 1u << 24;
 uint32_t key_order_scratch_words(uint32_t n, uint32_t nkeys);
+// keys per bin = 2^key_order_shift(nkeys): the smallest shift that leaves at most 4096 bins
+uint32_t key_order_shift(uint32_t nkeys);
 // perm[j] = index_base + i for the signatures i of val_idx[0..n) in key-grouped order.
 hipError_t launch_key_order(const uint32_t *val_idx, uint32_t n, uint32_t nkeys, uint32_t *scratch, uint32_t *perm,
                             uint32_t index_base, hipStream_t stream);

@@ -533,7 +533,7 @@ __global__ __launch_bounds__(kThreadsPerBlock) void verify_finish_kernel(
 // a latency-bound chain, and a SIMD holding two such waves runs them ~twice as long (a C4 batch of
 // ~853k votes took 13 per group = 1,025 waves with the floor: C4 585 -> 591 M/s, profiles/r05/s17/).
 hipError_t launch_finish(const int4 *fin, int4 *pre, const uint8_t *sig, uint8_t *out, uint32_t fin_base, uint32_t m,
-                         hipStream_t stream, const uint32_t *perm = nullptr) {
+                         hipStream_t stream, const uint32_t *perm) {
   if (m == 0) return hipSuccess;
   constexpr uint32_t kLanes = 65536;  // one inversion per lane and group; 65,536 lanes fill every SIMD
   uint32_t G = (m + kLanes - 1) / kLanes;
@@ -542,6 +542,40 @@ hipError_t launch_finish(const int4 *fin, int4 *pre, const uint8_t *sig, uint8_t
   const uint32_t L = (m + G - 1) / G;
   hipLaunchKernelGGL(verify_finish_kernel, dim3((L + kThreadsPerBlock - 1) / kThreadsPerBlock),
                      dim3(kThreadsPerBlock), 0, stream, fin, pre, sig, out, fin_base, L, m, perm);
+  return hipGetLastError();
+}
+
+// Tests (tmed_test_finish): position p's X, Y, Z (30 limbs) into fin slot p as fin_store writes
+// them, its R into the first half of signature row fin_base + p (perm[fin_base + p] with perm), and
+// its bit into out at the same index.
+__global__ __launch_bounds__(kThreadsPerBlock) void test_fin_fill_kernel(
+    const int32_t *__restrict__ xyz, const uint8_t *__restrict__ r, const uint8_t *__restrict__ bits,
+    const uint32_t *__restrict__ perm, uint32_t fin_base, uint32_t m, int4 *__restrict__ fin, uint8_t *__restrict__ sig,
+    uint8_t *__restrict__ out) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= m) return;
+  fe X, Y, Z;
+#pragma unroll
+  for (int i = 0; i < 10; i++) {
+    X.v[i] = xyz[30 * (size_t)p + i];
+    Y.v[i] = xyz[30 * (size_t)p + 10 + i];
+    Z.v[i] = xyz[30 * (size_t)p + 20 + i];
+  }
+  fin_store(fin, kFinCap, p, X, Y, Z);
+  const uint32_t i = perm ? perm[fin_base + p] : fin_base + p;
+  const uint4 *src = reinterpret_cast<const uint4 *>(r + 32 * (size_t)p);
+  uint4 *dst = reinterpret_cast<uint4 *>(sig + 64 * (size_t)i);
+  dst[0] = src[0];
+  dst[1] = src[1];
+  out[i] = bits[p];
+}
+
+hipError_t launch_test_fin_fill(const int32_t *xyz, const uint8_t *r, const uint8_t *bits, const uint32_t *perm,
+                                uint32_t fin_base, uint32_t m, int4 *fin, uint8_t *sig, uint8_t *out,
+                                hipStream_t stream) {
+  if (m == 0 || m > kFinCap) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(test_fin_fill_kernel, dim3((m + kThreadsPerBlock - 1) / kThreadsPerBlock), dim3(kThreadsPerBlock),
+                     0, stream, xyz, r, bits, perm, fin_base, m, fin, sig, out);
   return hipGetLastError();
 }
 
@@ -964,7 +998,7 @@ __global__ __launch_bounds__(256) void key_scatter_kernel(const uint32_t *__rest
   }
 }
 
-static uint32_t key_shift(uint32_t nkeys) {
+uint32_t key_order_shift(uint32_t nkeys) {
   uint32_t shift = 0;
   while (((nkeys - 1) >> shift) + 2 > kKeyBins) shift++;
   return shift;
@@ -972,14 +1006,14 @@ static uint32_t key_shift(uint32_t nkeys) {
 
 uint32_t key_order_scratch_words(uint32_t n, uint32_t nkeys) {
   (void)n;
-  return ((nkeys - 1) >> key_shift(nkeys)) + 2;
+  return ((nkeys - 1) >> key_order_shift(nkeys)) + 2;
 }
 
 hipError_t launch_key_order(const uint32_t *val_idx, uint32_t n, uint32_t nkeys, uint32_t *scratch, uint32_t *perm,
                             uint32_t index_base, hipStream_t stream) {
   if (nkeys == 0 || nkeys > kKeyOrderMaxKeys) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
-  const uint32_t shift = key_shift(nkeys), nbins = ((nkeys - 1) >> shift) + 2;
+  const uint32_t shift = key_order_shift(nkeys), nbins = ((nkeys - 1) >> shift) + 2;
   const uint32_t ntiles = (n + kKeyTile - 1) / kKeyTile;
   hipError_t e = hipMemsetAsync(scratch, 0, (size_t)nbins * 4, stream);
   if (e != hipSuccess) return e;

@@ -543,6 +543,87 @@ int tmed_test_table_chain(tmed_ctx *c, int table, uint64_t handle, int radix_bit
   return TMED_OK;
 }
 
+int tmed_test_key_order(tmed_ctx *c, const uint32_t *val_idx, uint32_t n, uint32_t nkeys, uint32_t index_base,
+                        uint32_t *perm_out, uint32_t *cursor_out, uint32_t *nbins_out, uint32_t *shift_out) {
+  if (!c || !val_idx || !perm_out || !cursor_out || !nbins_out || !shift_out) return TMED_EINVAL;
+  if (n == 0 || n > kFinCap || nkeys == 0 || nkeys > kKeyOrderMaxKeys || index_base > 0xffffffffu - n) return TMED_EINVAL;
+  return guarded([&] {
+    return locked(c, /*collect=*/false, [&] {
+      (void)hipSetDevice(c->device);
+      hipStream_t s = c->stream;
+      // sized as keyset_verify sizes it: the counters / cursors, then the permutation
+      const size_t sw = key_order_scratch_words(n, nkeys);
+      uint32_t *d_idx = nullptr;
+      hipError_t e = c->d_korder.ensure((sw + (size_t)n) * 4);
+      if (e == hipSuccess) e = hipMalloc((void **)&d_idx, (size_t)n * 4);
+      if (e != hipSuccess) return map_err(e);
+      uint32_t *scratch = (uint32_t *)c->d_korder.p, *perm = scratch + sw;
+      e = hipMemcpyAsync(d_idx, val_idx, (size_t)n * 4, hipMemcpyHostToDevice, s);
+      if (e == hipSuccess) e = scratch_acquire(c, s);
+      const bool acquired = e == hipSuccess;
+      if (e == hipSuccess) e = hipMemsetAsync(perm, 0xff, (size_t)n * 4, s);
+      if (e == hipSuccess) e = launch_key_order(d_idx, n, nkeys, scratch, perm, index_base, s);
+      if (e == hipSuccess) e = hipMemcpyAsync(perm_out, perm, (size_t)n * 4, hipMemcpyDeviceToHost, s);
+      if (e == hipSuccess) e = hipMemcpyAsync(cursor_out, scratch, sw * 4, hipMemcpyDeviceToHost, s);
+      if (acquired) {
+        const hipError_t er = scratch_release(c, s);
+        if (e == hipSuccess) e = er;
+      }
+      const int rc = finish_call(c, s, e);
+      (void)hipFree(d_idx);
+      if (rc != TMED_OK) return rc;
+      *nbins_out = (uint32_t)sw;
+      *shift_out = key_order_shift(nkeys);
+      return (int)TMED_OK;
+    });
+  });
+}
+
+int tmed_test_finish(tmed_ctx *c, uint32_t m, const int32_t *xyz, const uint8_t *r, const uint32_t *perm,
+                     uint32_t fin_base, const uint8_t *bits_in, uint8_t *bits_out) {
+  if (!c || !xyz || !r || !bits_in || !bits_out) return TMED_EINVAL;
+  if (m == 0 || m > kFinCap || fin_base > 2 * kFinCap - m) return TMED_EINVAL;
+  const size_t rows = (size_t)fin_base + m;  // signature rows and out bytes the call allocates
+  if (perm)
+    for (uint32_t p = 0; p < m; p++)
+      if (perm[fin_base + p] >= rows) return TMED_EINVAL;
+  return guarded([&] {
+    return locked(c, /*collect=*/false, [&] {
+      if (!c->d_fin || !c->d_fin_pre) return (int)TMED_EINVAL;
+      (void)hipSetDevice(c->device);
+      hipStream_t s = c->stream;
+      // one staging allocation: xyz, r, perm, the bits in; then the signature rows and out
+      const size_t b_xyz = align256((size_t)m * 120), b_r = align256((size_t)m * 32), b_perm = align256(rows * 4),
+                   b_bits = align256(m), b_sig = align256(rows * 64), b_out = align256(rows);
+      uint8_t *d = nullptr;
+      hipError_t e = hipMalloc((void **)&d, b_xyz + b_r + b_perm + b_bits + b_sig + b_out);
+      if (e != hipSuccess) return map_err(e);
+      uint8_t *d_r = d + b_xyz, *d_perm = d_r + b_r, *d_bits = d_perm + b_perm, *d_sig = d_bits + b_bits,
+              *d_out = d_sig + b_sig;
+      e = hipMemcpyAsync(d, xyz, (size_t)m * 120, hipMemcpyHostToDevice, s);
+      if (e == hipSuccess) e = hipMemcpyAsync(d_r, r, (size_t)m * 32, hipMemcpyHostToDevice, s);
+      if (e == hipSuccess && perm) e = hipMemcpyAsync(d_perm, perm, rows * 4, hipMemcpyHostToDevice, s);
+      if (e == hipSuccess) e = hipMemcpyAsync(d_bits, bits_in, m, hipMemcpyHostToDevice, s);
+      if (e == hipSuccess) e = hipMemsetAsync(d_sig, 0, rows * 64, s);
+      if (e == hipSuccess) e = hipMemsetAsync(d_out, 0xaa, rows, s);  // a byte no position owns keeps this
+      if (e == hipSuccess) e = scratch_acquire(c, s);
+      const bool acquired = e == hipSuccess;
+      const uint32_t *dp = perm ? (const uint32_t *)d_perm : nullptr;
+      if (e == hipSuccess)
+        e = launch_test_fin_fill((const int32_t *)d, d_r, d_bits, dp, fin_base, m, c->d_fin, d_sig, d_out, s);
+      if (e == hipSuccess) e = launch_finish(c->d_fin, c->d_fin_pre, d_sig, d_out, fin_base, m, s, dp);
+      if (acquired) {
+        const hipError_t er = scratch_release(c, s);
+        if (e == hipSuccess) e = er;
+      }
+      if (e == hipSuccess) e = hipMemcpyAsync(bits_out, d_out, rows, hipMemcpyDeviceToHost, s);
+      const int rc = finish_call(c, s, e);
+      (void)hipFree(d);
+      return rc;
+    });
+  });
+}
+
 int tmed_sign_batch_device(tmed_ctx *c, const uint8_t *d_seeds, const uint8_t *d_msgs, const uint32_t *d_off,
                            size_t n, uint8_t *d_sig_out, uint8_t *d_pub_out, void *stream) {
   if (!c) return TMED_EINVAL;

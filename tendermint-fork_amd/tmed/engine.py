@@ -352,5 +352,39 @@ class Engine:
             raise TmedError(rc, "tmed_test_zip_msm")
         return win, ctot, int(flag.value)
 
+    def key_order(self, val_idx: np.ndarray, nkeys: int, index_base: int = 0):
+        """Tests: the key-grouped visiting order of one chunk's key indexes, by the product's own
+        launcher on the context's order scratch (tmed_test_key_order).
+        -> (perm (n,) uint32, cursor (nbins,) uint32: every bin's end, nbins, shift)."""
+        vi = np.ascontiguousarray(val_idx, dtype=np.uint32)
+        n = vi.shape[0]
+        perm, cursor = np.zeros(n, np.uint32), np.zeros(4096, np.uint32)
+        nbins, shift = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        rc = lib().tmed_test_key_order(self._h, _p(vi), n, nkeys, index_base, _p(perm), _p(cursor),
+                                       ctypes.byref(nbins), ctypes.byref(shift))
+        if rc != 0:
+            raise TmedError(rc, "tmed_test_key_order")
+        return perm, cursor[:nbins.value].copy(), int(nbins.value), int(shift.value)
+
+    def finish(self, xyz: np.ndarray, r: np.ndarray, bits_in: np.ndarray, fin_base: int = 0, perm=None) -> np.ndarray:
+        """Tests: the batched finish of m projective points a caller gives, by the product's own
+        launcher on the context's finish buffers (tmed_test_finish).  xyz (m, 30) int32: X, Y, Z limbs;
+        r (m, 32) uint8; bits_in (m,) uint8; perm: fin_base + m uint32 entries or None.
+        -> `out` (fin_base + m,) uint8 after the finish (0xAA where no position's decision lands)."""
+        m = bits_in.shape[0]
+        xyz = np.ascontiguousarray(xyz, dtype=np.int32).reshape(m, 30)
+        r = np.ascontiguousarray(r, dtype=np.uint8).reshape(m, 32)
+        bits_in = np.ascontiguousarray(bits_in, dtype=np.uint8)
+        if perm is not None:
+            perm = np.ascontiguousarray(perm, dtype=np.uint32)
+            if perm.shape[0] != fin_base + m:
+                raise ValueError("perm must hold fin_base + m entries")
+        out = np.zeros(fin_base + m, np.uint8)
+        rc = lib().tmed_test_finish(self._h, m, _p(xyz), _p(r), None if perm is None else _p(perm), fin_base,
+                                    _p(bits_in), _p(out))
+        if rc != 0:
+            raise TmedError(rc, "tmed_test_finish")
+        return out
+
     def last_kernel_ms(self) -> float:
         return float(lib().tmed_last_kernel_ms(self._h))

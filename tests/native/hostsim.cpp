@@ -68,25 +68,33 @@ struct HostFin {
   const uint8_t *sig;
   uint8_t *out;
   uint32_t lane, L, m;
+  // as FinDev (kernels.hip): slot p is signature fin_base + p, or perm[fin_base + p] in the key-grouped order
+  uint32_t fin_base = 0;
+  const uint32_t *perm = nullptr;
   int count() const { return lane < m ? (int)((m - lane + L - 1) / L) : 0; }
   uint32_t slot(int j) const { return lane + (uint32_t)j * L; }
+  uint32_t sig_index(int j) const {
+    const uint32_t p = fin_base + slot(j);
+    return perm ? perm[p] : p;
+  }
   void load_z(int j, fe &z) const { z = (*pts)[slot(j)].Z; }
   void load_xy(int j, fe &X, fe &Y) const { X = (*pts)[slot(j)].X; Y = (*pts)[slot(j)].Y; }
   void store_pre(int j, const fe &p) const { (*pre)[(size_t)j * L + lane] = p; }
   void load_pre(int j, fe &p) const { p = (*pre)[(size_t)j * L + lane]; }
-  void load_r(int j, uint32_t Rw[8]) const { load_words8(Rw, sig + 64 * (size_t)slot(j)); }
-  void result(int j, bool ok) const { uint8_t &o = out[slot(j)]; o = (o && ok) ? 1 : 0; }
+  void load_r(int j, uint32_t Rw[8]) const { load_words8(Rw, sig + 64 * (size_t)sig_index(j)); }
+  void result(int j, bool ok) const { uint8_t &o = out[sig_index(j)]; o = (o && ok) ? 1 : 0; }
 };
 
 // Host twin of launch_finish: same group-size rule, but G is a parameter so tests can
 // cover partial groups.
-void host_finish(const std::vector<ge_p2> &pts, const uint8_t *sig, uint8_t *out, uint32_t m, uint32_t G) {
+void host_finish(const std::vector<ge_p2> &pts, const uint8_t *sig, uint8_t *out, uint32_t m, uint32_t G,
+                 uint32_t fin_base = 0, const uint32_t *perm = nullptr) {
   if (m == 0) return;
   const uint32_t L = (m + G - 1) / G;
   std::vector<fe> pre((size_t)G * L);
 #pragma omp parallel for schedule(dynamic, 8)
   for (long l = 0; l < (long)L; l++) {
-    HostFin a{&pts, &pre, sig, out, (uint32_t)l, L, m};
+    HostFin a{&pts, &pre, sig, out, (uint32_t)l, L, m, fin_base, perm};
     finish_group(a);
   }
 }
@@ -127,6 +135,32 @@ static void verify_batch_impl(const uint8_t *pub, const uint8_t *sig, const uint
 void hostsim_verify_batch_g(const uint8_t *pub, const uint8_t *sig, const uint8_t *msgs, const uint32_t *off,
                             size_t n, uint8_t *out, int group) {
   verify_batch_impl(pub, sig, msgs, off, n, out, group, 8);
+}
+
+// The finish alone, on points a caller gives (the host twin of tmed_test_finish, same arrays, plus
+// the group size G in 1..16): xyz m x 30 limbs; r m x 32 bytes, position p's R at signature row
+// fin_base + p, or perm[fin_base + p] (perm: fin_base + m entries below fin_base + m, or null);
+// bits_in m bytes; bits_out fin_base + m bytes, 0xAA where no position's decision lands.
+int hostsim_finish_raw(uint32_t m, const int32_t *xyz, const uint8_t *r, const uint32_t *perm, uint32_t fin_base,
+                       const uint8_t *bits_in, uint8_t *bits_out, uint32_t G) {
+  if (m == 0 || G == 0 || G > 16 || !xyz || !r || !bits_in || !bits_out) return -1;
+  const size_t rows = (size_t)fin_base + m;
+  std::vector<ge_p2> pts(m);
+  std::vector<uint8_t> sig(64 * rows, 0);
+  memset(bits_out, 0xaa, rows);
+  for (uint32_t p = 0; p < m; p++) {
+    for (int i = 0; i < 10; i++) {
+      pts[p].X.v[i] = xyz[30 * (size_t)p + i];
+      pts[p].Y.v[i] = xyz[30 * (size_t)p + 10 + i];
+      pts[p].Z.v[i] = xyz[30 * (size_t)p + 20 + i];
+    }
+    const uint32_t i = perm ? perm[fin_base + p] : fin_base + p;
+    if (i >= rows) return -1;
+    memcpy(&sig[64 * (size_t)i], r + 32 * (size_t)p, 32);
+    bits_out[i] = bits_in[p];
+  }
+  host_finish(pts, sig.data(), bits_out, m, G, fin_base, perm);
+  return 0;
 }
 
 // Main-kernel variant 5: radix-2^16 B windows (16 B additions) + the batched finish.

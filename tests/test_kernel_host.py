@@ -131,6 +131,34 @@ def test_golden_vectors_hostsim(hostsim, golden, group):
     assert not bad, bad
 
 
+def test_finish_raw_cases_hostsim(hostsim):
+    """The batched finish alone (hostsim_finish_raw: HostFin / host_finish with FinDev's perm indexing)
+    on every case of tests/finish_cases.py at m <= 4,099, with G in {1, 2, 3, 16}, with and without a
+    shuffled perm: every bit equals the Python-integer expectation, the Z = 0 rows are rejected
+    without touching their lane's group, no byte outside the m decisions is written.  Every row's
+    expectation is first recomputed from its limbs alone."""
+    import finish_cases as FC
+    fin_base = 64
+    for m in (1, 17, 255, 256, 257, 4095, 4099):
+        for G in (1, 2, 3, 16):
+            if G > m or (m == 4099 and G == 16):  # L = 257 would repeat a pool's Z inside a group
+                continue
+            c = FC.case(m, 4099, G)
+            if G == 1:  # (the bulk rows are the same for every G; the planted ones are expected this way anyhow)
+                direct = [FC.direct_expected(row[:10], row[10:20], row[20:], bytes(rb), bit)
+                          for row, rb, bit in zip(c["xyz"].tolist(), c["r"], c["bits_in"])]
+                assert (np.array(direct, np.uint8) == c["exp"]).all()
+            for base, perm in ((0, None), (fin_base, None), (0, FC.shuffled_perm(m, 0, m + G)),
+                               (fin_base, FC.shuffled_perm(m, fin_base, m - G))):
+                out = np.zeros(base + m, np.uint8)
+                rc = hostsim.hostsim_finish_raw(ctypes.c_uint32(m), _p(c["xyz"]), _p(c["r"]),
+                                                None if perm is None else _p(perm), ctypes.c_uint32(base),
+                                                _p(c["bits_in"]), _p(out), ctypes.c_uint32(G))
+                assert rc == 0
+                FC.check(c, out, base, perm)
+                FC.check_guards(c, out, base, perm)
+
+
 def test_sign_matches_oracle(hostsim):
     rng = np.random.default_rng(2)
     n = 96
