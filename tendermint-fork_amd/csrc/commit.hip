@@ -130,7 +130,7 @@ static int stage_group(tmed_ctx *ctx, const tmed_commit_request *reqs, size_t n,
   // signatures stay per vote
   auto fill = [&](size_t lo, size_t hi, unsigned tid) {
     bool ok = true, staged_sig = false;
-    std::vector<tmed::VoteStage::Dma> mine;  // (a header of its own: see seam_plan)
+    std::vector<tmed::VoteStage::Dma> mine;  // (a header of its own: see PlanPart, seam_host.h)
     for_segments(cands, grp, lo, hi, [&](size_t j, uint32_t u0, uint32_t u1, size_t p) {
       const Run &run = cands.runs[grp.run(cands, j)];
       const tmed_commit_request &r = reqs[run.req];

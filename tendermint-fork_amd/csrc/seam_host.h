@@ -7,13 +7,23 @@
 // region writes is a reported race on the CPU suite, not a rare wrong bit on the GPU box.
 //
 // Parallel regions (parallel_ranges) and what each part reads from outside its own range — every
-// such read is of data a PRIOR region (or the serial code before the region) wrote:
-//   seam_plan plan_range   reqs (caller, read-only); writes part[t], plans[lo, hi), out[lo, hi)
-//   seam_plan merge_part   part[t], pc / rbase / cbase (plan region + serial prefix sums);
-//                          writes runs/off of its own run range, plans/tmpl_of/row_of of its
-//                          own requests; pair_request and Group::add_run read only those
-//   seam_plan join         ps.aparts / gparts / trows (merge region), abase / sbase / pbase /
-//                          tbase (serial prefix sums)
+// such read is of data a PRIOR region (or the serial code before the region) wrote.
+//
+// seam_plan's three passes run over the planning workers' parts (PlanPart p, one per worker); a
+// pass writes the fields of its own part listed first, and what it reads of OTHER parts or of the
+// joined arrays is listed second:
+//   plan_part    writes p.lo / hi / runs / ncand / rc / trusting / vof, plans[lo, hi), out[lo, hi)
+//                reads  nothing of another part (reqs: the caller's, read-only)
+//   (serial)     writes every p.run0 / cand0; sizes cands.runs / off / tmpl_of, tp->row_of
+//   merge_part   writes p.alias / grp / rows / rows_fit / rows_bad; its own slices of the joined arrays:
+//                cands.runs / off [run0, run0 + runs.size()), plans / tmpl_of / row_of [lo, hi)
+//                reads  nothing of another part, and of the joined arrays only those slices
+//                (pair_request pairs inside [lo, hi); add_run ends a run at off[r] + len)
+//   (serial)     writes every p.alias0 / seg0 / pos0 / row0; sizes cands.alias, *grp, tp->rows
+//   join_part    writes its own slices of cands.alias, grp->rix / ub / pos and tp->rows; row_of [lo, hi)
+//                reads  nothing of another part (p.alias / grp / rows and the bases: finished above)
+//   (serial)     cands.preq / pal / pseg from every p.lo / alias0 / seg0
+// The regions after planning:
 //   build_group            c.off / c.runs / c.alias: complete before the call (seam_plan)
 //   finish_parts           grp / cands / plans (planning, finished before the batch was staged);
 //                          part t scatters, aliases and replays only its own requests' candidates
@@ -183,7 +193,7 @@ struct Group {
     pos.assign(1, 0);
   }
   // run r without its aliased candidates (al[ap..] ascending; ap advances past run r's).  The end
-  // is off[r] + len, not off[r + 1]: seam_plan's merge calls this for a part's runs while the next
+  // is off[r] + len, not off[r + 1]: merge_part calls this for a part's runs while the next
   // part's worker is still writing its offsets, and off[r + 1] of a part's last run is the next
   // part's first (read before it was written, it held the slot's previous batch's offset).
   void add_run(const Cands &c, uint32_t r, const std::vector<std::pair<uint32_t, uint32_t>> &al, size_t &ap) {
@@ -201,6 +211,18 @@ struct Group {
     }
     seg(k, c1);
   }
+  // Groups built part by part, joined: room for ns segments, then part p's at segment s0, position p0.
+  void resize(size_t ns) {
+    rix.resize(ns);
+    ub.resize(ns);
+    pos.resize(ns + 1);
+    pos[0] = 0;
+  }
+  void join(const Group &p, size_t s0, size_t p0) {
+    std::copy(p.rix.begin(), p.rix.end(), rix.begin() + s0);
+    std::copy(p.ub.begin(), p.ub.end(), ub.begin() + s0);
+    for (size_t j = 0; j < p.rix.size(); j++) pos[s0 + j + 1] = p0 + p.pos[j + 1];
+  }
 };
 
 // Device templates, one row per request whose candidates use its own (Cands::tmpl_row), rows
@@ -214,8 +236,6 @@ struct Templates {
   uint32_t row(const Cands &c, uint32_t q) const { return row_of[c.tmpl_row(q)]; }
 };
 
-// The plans of one seam call and the planning workers' parts, kept between calls (blocksync
-// plans batch after batch), so their pages are touched once.
 // A planning worker's vof arrays: taken from chunks kept between calls (pointers stay valid
 // until the next reset).
 struct VofArena {
@@ -235,15 +255,34 @@ struct VofArena {
   }
 };
 
-struct Plans {
-  std::vector<Plan> v;
-  std::vector<VofArena> tbits;  // per planning worker: its Trusting requests' vof arrays
-  std::vector<std::vector<Run>> parts;
-  std::vector<std::vector<std::pair<uint32_t, uint32_t>>> aparts;  // per worker: its aliases
-  std::vector<Group> gparts;                                       // per worker: its group segments
-  std::vector<std::vector<uint8_t>> trows;                         // per worker: its template rows
+// One planning worker's part of a seam call (seam_plan): everything the three passes keep per worker.
+// A pass writes only its own part, under its heading below; the serial code between the passes
+// writes the prefix sums.  Aligned to a cache line: a worker's push_backs write its vectors'
+// headers, and a neighbour's headers in the same line would make every one of them a miss.
+struct alignas(64) PlanPart {
+  // plan pass
+  size_t lo = 0, hi = 0;  // its requests; a part that did not run: [n, n)
+  std::vector<Run> runs;  // their candidates, offsets and Plan::run_lo / run_hi counted from the part's first
+  size_t ncand = 0;
+  int rc = TMED_OK;       // of the first request that failed its check
+  bool trusting = false;  // it planned a Trusting request
+  VofArena vof;           // its Trusting requests' vof arrays
+  // merge pass
+  std::vector<std::pair<uint32_t, uint32_t>> alias;  // its aliases (global candidates)
+  Group grp;                                         // its staging segments (global runs, positions from 0)
+  std::vector<uint8_t> rows;                         // its template rows
+  bool rows_fit = true, rows_bad = false;            // all within the device assembler; the encoder rejected one
+  // where the part's share of each joined array starts (serial prefix sums: run0 / cand0 after the
+  // plan pass, the rest after the merge pass)
+  size_t run0 = 0, cand0 = 0, alias0 = 0, seg0 = 0, pos0 = 0, row0 = 0;
 };
 
+// The plans of one seam call and the planning workers' parts, kept between calls (blocksync
+// plans batch after batch), so their pages are touched once.
+struct Plans {
+  std::vector<Plan> v;
+  std::vector<PlanPart> part;
+};
 
 // Per-thread "seen" marks of the Trusting loops (first index of each validator), reset in
 // O(1) per request by an epoch stamp instead of a fresh n-sized vector.
@@ -335,6 +374,17 @@ static tmed_vote_template vote_template_of(const tmed_commit_request &rq) {
   t.psh_hash = c.block_id.psh_hash;
   t.psh_hash_len = c.block_id.psh_hash_len;
   return t;
+}
+
+// Request q's template row (kVoteTmplBytes at row); false: the encoder rejected the request
+// (bad), or *fit = false when its template does not fit the device assembler.
+static bool template_row(const tmed_commit_request &rq, uint8_t *row, bool *fit) {
+  const tmed_vote_template t = vote_template_of(rq);
+  tmed::VoteEncoder e;
+  if (e.init(&t) != TMED_OK) return false;
+  memset(row, 0, tmed::kVoteTmplBytes);
+  if (!e.device_template(row, tmed::kVoteTmplBytes, tmed::kVoteSlot)) *fit = false;
+  return true;
 }
 
 // Per-request CanonicalVote encoders for the requests that have candidates; then(q, enc)
@@ -520,267 +570,6 @@ static size_t total_sigs(const tmed_commit_request *reqs, size_t n) {
   return s;
 }
 
-static void pair_request(const tmed_commit_request *reqs, const std::vector<Plan> &plans, Cands &cands, size_t q,
-                         size_t lo, size_t hi, std::vector<std::pair<uint32_t, uint32_t>> &mine);
-
-// Candidates of requests [0, n) in request order (identical to a serial plan).
-static bool template_row(const tmed_commit_request &rq, uint8_t *row, bool *fit);
-
-static int seam_plan(const tmed_commit_request *reqs, size_t n, tmed_commit_result *out, Plans &ps, Cands &cands,
-                     const KcCall *kc = nullptr, Group *grp = nullptr, Templates *tp = nullptr) {
-  PhaseClock clk;
-  std::vector<Plan> &plans = ps.v;
-  plans.assign(n, Plan());
-  cands.clear();
-  // worker count: calls of 1,024+ requests fan out at once; smaller ones by their signature count
-  // (a blocksync batch: 128 requests of 10k signatures).  Each worker checks its requests as it
-  // plans them (plan_request) and keeps the vof arrays of its Trusting requests in a buffer of its
-  // own, so no separate pass over the (cold) requests runs first.
-  size_t sigs_est = 0;
-  if (n < 1024)
-    for (size_t q = 0; q < n; q++) sigs_est += reqs[q].commit ? reqs[q].commit->n_sigs : 0;
-  const unsigned nt = n >= 1024 ? host_threads(~(size_t)0) : host_threads(sigs_est);
-  const unsigned np = std::max(1u, nt);
-  if (ps.parts.size() < np) ps.parts.resize(np);
-  if (ps.tbits.size() < np) ps.tbits.resize(np);
-  std::vector<std::vector<Run>> &part = ps.parts;
-  // (parts that never run — parallel_ranges uses at most n of them — keep the empty range [n, n))
-  std::vector<size_t> lo_of(np, n), hi_of(np, n), pc(np, 0);
-  std::vector<int> rcs(np, TMED_OK);
-  std::vector<uint8_t> trusting(np, 0);
-  auto plan_range = [&](size_t lo, size_t hi, unsigned t) {
-    lo_of[t] = lo; hi_of[t] = hi;
-    AddrScratch addr;
-    addr.kc = kc;
-    size_t c = 0;
-    VofArena &va = ps.tbits[t];
-    va.reset();
-    bool tr = false;
-    std::vector<Run> mine;
-    mine.swap(part[t]);
-    int rc = TMED_OK;
-    // the next request's arrays are cold (a light-client batch touches ~5 KB of flags, powers and
-    // addresses per request, each request in arrays of its own): their first lines are fetched
-    // while this request is planned
-    auto prefetch_req = [&](size_t q) {
-      if (q >= hi) return;
-      const tmed_commit_request &r = reqs[q];
-      if (!r.commit || !r.vals) return;
-      const tmed_commit &cm = *r.commit;
-      const size_t ns = std::min<size_t>(cm.n_sigs, 128);
-      for (size_t o = 0; o < ns; o += 64) __builtin_prefetch(cm.flags + o, 0, 0);
-      if (r.vals->powers)
-        for (size_t o = 0; o < 8 * ns; o += 64) __builtin_prefetch((const uint8_t *)r.vals->powers + o, 0, 0);
-      if (r.mode == TMED_MODE_LIGHT_TRUSTING && cm.addresses)
-        for (size_t o = 0; o < 20 * ns; o += 64) __builtin_prefetch(cm.addresses + o, 0, 0);
-    };
-    for (size_t q = lo; q < lo + 4 && q < hi; q++) {  // the structs behind the requests are cold
-      __builtin_prefetch(reqs[q].commit, 0, 0);
-      __builtin_prefetch(reqs[q].vals, 0, 0);
-    }
-    prefetch_req(lo);
-    for (size_t q = lo; q < hi && rc == TMED_OK; q++) {
-      if (q + 4 < hi) {
-        __builtin_prefetch(reqs[q + 4].commit, 0, 0);
-        __builtin_prefetch(reqs[q + 4].vals, 0, 0);
-      }
-      prefetch_req(q + 1);
-      if (reqs[q].mode == TMED_MODE_LIGHT_TRUSTING && reqs[q].commit) {
-        plans[q].vof = va.take(std::max<size_t>(reqs[q].commit->n_sigs, 1));
-        tr = true;
-      }
-      rc = plan_request(reqs, q, out[q], plans[q], mine, c, addr);
-    }
-    trusting[t] = tr;
-    mine.swap(part[t]);
-    rcs[t] = rc;
-    pc[t] = c;
-  };
-  for (unsigned t = 0; t < np; t++) part[t].clear();
-  if (nt <= 1) plan_range(0, n, 0);
-  else parallel_ranges(n, nt, plan_range);
-  for (int rc : rcs)
-    if (rc != TMED_OK) return rc;
-  clk.lap("plan_requests");
-  // merge: the parts' runs in thread order (= request order), candidate offsets made global; in the
-  // same pass each worker pairs its Trusting requests with their Light partners (pair_request)
-  // and, for a device batch (grp), lays out its runs' staging segments without the aliased
-  // candidates; one more pass joins the workers' aliases and segments
-  std::vector<size_t> rbase(np + 1, 0), cbase(np + 1, 0);
-  for (unsigned t = 0; t < np; t++) {
-    rbase[t + 1] = rbase[t] + part[t].size();
-    cbase[t + 1] = cbase[t] + pc[t];
-  }
-  const size_t nr = rbase[np], cb = cbase[np];
-  cands.runs.resize(nr);
-  cands.off.resize(nr + 1);
-  cands.off[nr] = cb;
-  bool any_trusting = false;
-  for (unsigned t = 0; t < np; t++) any_trusting = any_trusting || trusting[t];
-  const bool pair = any_trusting && cb <= 0xffffffffu;
-  if (pair) {
-    cands.tmpl_of.resize(n);
-    if (ps.aparts.size() < np) ps.aparts.resize(np);
-    if (grp && ps.gparts.size() < np) ps.gparts.resize(np);
-  }
-  // a device batch planned by several workers also gets its template rows here, each worker
-  // encoding the requests of its part that own a row (row_of holds part-local rows until the join)
-  const bool rows_here = tp && nt > 1;
-  std::vector<uint8_t> tfit(np, 1), tbad(np, 0);
-  if (tp) tp->ready = false;
-  if (rows_here) {
-    tp->row_of.resize(n);
-    if (ps.trows.size() < np) ps.trows.resize(np);
-  }
-  // TMED_TEST_MERGE_SKEW=1 (tests): odd parts start their merge 2 ms late, so a part that read what
-  // the next part's worker writes (add_run's end of a part's last run, before the fix) reads it
-  // unwritten every time instead of rarely
-  const bool skew = nt > 1 && getenv("TMED_TEST_MERGE_SKEW") != nullptr;
-  auto merge_part = [&](size_t t) {
-    if (skew && (t & 1)) std::this_thread::sleep_for(std::chrono::milliseconds(2));
-    // reads from outside part t: part[t], pc, lo_of / hi_of (the planning region, finished), rbase /
-    // cbase (the serial prefix sums above); everything else read below is part t's own output of
-    // this same body (its runs, offsets and plans, written before pair_request / add_run read them)
-    size_t c = cbase[t];
-    Run *dst = cands.runs.data() + rbase[t];
-    size_t *off = cands.off.data() + rbase[t];
-    for (size_t r = 0; r < part[t].size(); r++) {
-      dst[r] = part[t][r];
-      off[r] = c;
-      c += part[t][r].len;
-    }
-    for (size_t q = lo_of[t]; q < hi_of[t]; q++) {
-      plans[q].cand_off += cbase[t];
-      plans[q].run_lo += rbase[t];
-      plans[q].run_hi += rbase[t];
-    }
-    auto rows_of_part = [&] {
-      std::vector<uint8_t> rows;  // (a header of its own: see seam_plan)
-      rows.swap(ps.trows[t]);
-      rows.clear();
-      uint32_t k = 0;
-      bool fit = true;
-      for (size_t q = lo_of[t]; q < hi_of[t]; q++) {
-        const Plan &pl = plans[q];
-        if (pl.run_lo == pl.run_hi || cands.tmpl_row((uint32_t)q) != q) {
-          tp->row_of[q] = kNoRow;
-          continue;
-        }
-        rows.resize((size_t)(k + 1) * tmed::kVoteTmplBytes);
-        if (!template_row(reqs[q], rows.data() + (size_t)k * tmed::kVoteTmplBytes, &fit)) tbad[t] = 1;
-        tp->row_of[q] = k++;
-      }
-      tfit[t] = fit;
-      rows.swap(ps.trows[t]);
-    };
-    if (!pair) {
-      if (rows_here) rows_of_part();
-      return;
-    }
-    for (size_t q = lo_of[t]; q < hi_of[t]; q++) cands.tmpl_of[q] = (uint32_t)q;
-    std::vector<std::pair<uint32_t, uint32_t>> mine;  // (a header of its own: see seam_plan)
-    mine.swap(ps.aparts[t]);
-    mine.clear();
-    for (size_t q = lo_of[t]; q < hi_of[t]; q++) pair_request(reqs, plans, cands, q, lo_of[t], hi_of[t], mine);
-    if (grp) {
-      Group g;
-      g.rix.swap(ps.gparts[t].rix);
-      g.ub.swap(ps.gparts[t].ub);
-      g.pos.swap(ps.gparts[t].pos);
-      g.start();
-      size_t ap = 0;
-      for (size_t r = rbase[t]; r < rbase[t + 1]; r++) g.add_run(cands, (uint32_t)r, mine, ap);
-      g.rix.swap(ps.gparts[t].rix);
-      g.ub.swap(ps.gparts[t].ub);
-      g.pos.swap(ps.gparts[t].pos);
-    }
-    mine.swap(ps.aparts[t]);
-    if (rows_here) rows_of_part();  // after the pairing: tmpl_of of the part is final
-  };
-  if (nt <= 1) {
-    for (unsigned t = 0; t < np; t++) merge_part(t);
-  } else {
-    parallel_ranges(np, np, [&](size_t lo, size_t hi, unsigned) {
-      for (size_t t = lo; t < hi; t++) merge_part(t);
-    });
-  }
-  clk.lap("merge");
-  cands.alias.clear();
-  if (grp) *grp = Group();  // no aliases: every run whole, in order
-  std::vector<size_t> abase(np + 1, 0), sbase(np + 1, 0), pbase(np + 1, 0), tbase(np + 1, 0);
-  bool rows_bad = false, rows_fit = true;
-  for (unsigned t = 0; t < np; t++) {
-    if (pair) {
-      abase[t + 1] = abase[t] + ps.aparts[t].size();
-      if (grp) {
-        const Group &g = ps.gparts[t];
-        sbase[t + 1] = sbase[t] + g.rix.size();
-        pbase[t + 1] = pbase[t] + (g.rix.empty() ? 0 : g.pos.back());
-      }
-    }
-    if (rows_here) {
-      tbase[t + 1] = tbase[t] + ps.trows[t].size() / tmed::kVoteTmplBytes;
-      rows_bad = rows_bad || tbad[t];
-      rows_fit = rows_fit && tfit[t];
-    }
-  }
-  if (rows_bad) return TMED_EINVAL;  // the encoder rejected a request (as device_templates does)
-  const bool aliases = pair && abase[np] != 0;
-  if (aliases) {
-    cands.alias.resize(abase[np]);
-    if (grp) {
-      grp->rix.resize(sbase[np]);
-      grp->ub.resize(sbase[np]);
-      grp->pos.resize(sbase[np] + 1);
-      grp->pos[0] = 0;
-    }
-  }
-  if (rows_here) {
-    tp->nrows = tbase[np];
-    tp->rows.resize(std::max<size_t>(tp->nrows, 1) * tmed::kVoteTmplBytes);
-  }
-  if (aliases || rows_here) {
-    auto join = [&](size_t t) {
-      // reads ps.aparts / gparts / trows (the merge region, finished) and the prefix sums above;
-      // writes only part t's slices of the joined arrays
-      if (rows_here) {
-        std::copy(ps.trows[t].begin(), ps.trows[t].end(), tp->rows.begin() + tbase[t] * tmed::kVoteTmplBytes);
-        for (size_t q = lo_of[t]; q < hi_of[t]; q++)
-          if (tp->row_of[q] != kNoRow) tp->row_of[q] += (uint32_t)tbase[t];
-      }
-      if (!aliases) return;
-      std::copy(ps.aparts[t].begin(), ps.aparts[t].end(), cands.alias.begin() + abase[t]);
-      if (!grp) return;
-      const Group &g = ps.gparts[t];
-      const size_t k = g.rix.size(), s0 = sbase[t], p0 = pbase[t];
-      std::copy(g.rix.begin(), g.rix.end(), grp->rix.begin() + s0);
-      std::copy(g.ub.begin(), g.ub.end(), grp->ub.begin() + s0);
-      for (size_t j = 0; j < k; j++) grp->pos[s0 + j + 1] = p0 + g.pos[j + 1];
-    };
-    if (nt <= 1) {
-      for (unsigned t = 0; t < np; t++) join(t);
-    } else {
-      parallel_ranges(np, np, [&](size_t lo, size_t hi, unsigned) {
-        for (size_t t = lo; t < hi; t++) join(t);
-      });
-    }
-    if (aliases && grp && nt > 1) {
-      cands.preq.resize(np + 1);
-      for (unsigned t = 0; t < np; t++) cands.preq[t] = lo_of[t];
-      cands.preq[np] = n;
-      cands.pal = abase;
-      cands.pseg = sbase;
-    }
-  }
-  if (rows_here) {
-    tp->fits = rows_fit;
-    tp->ready = true;
-  }
-  clk.lap("aliases");
-  clk.emit("plan", n, cb);
-  return TMED_OK;
-}
-
 // ---- candidates verified once for two requests ----------------------------------------
 // The light client checks one commit twice, LightTrusting against the trusted set and Light
 // against the untrusted one (light/verifier.go:58,73-76), and most validators sign for both
@@ -850,6 +639,225 @@ static void pair_request(const tmed_commit_request *reqs, const std::vector<Plan
     }
     return;
   }
+}
+
+// ---- the planner: three passes over the planning workers' parts (PlanPart) -------------
+
+// f(t) for the parts [0, np): one region of the pool with a worker per part (one part: a plain call).
+template <class F>
+static void for_parts(unsigned np, F &&f) {
+  parallel_ranges(np, np, [&](size_t lo, size_t hi, unsigned) {
+    for (size_t t = lo; t < hi; t++) f((unsigned)t);
+  });
+}
+
+// Plan pass: requests [lo, hi) planned into p.runs in request order, each checked as it is planned
+// (plan_request), the vof arrays of the Trusting ones taken from p.vof; stops at the first request
+// that fails its check (p.rc).
+static void plan_part(PlanPart &p, size_t lo, size_t hi, const tmed_commit_request *reqs, tmed_commit_result *out,
+                      std::vector<Plan> &plans, const KcCall *kc) {
+  p.lo = lo;
+  p.hi = hi;
+  p.vof.reset();
+  AddrScratch addr;
+  addr.kc = kc;
+  // the next request's arrays are cold (a light-client batch touches ~5 KB of flags, powers and
+  // addresses per request, each request in arrays of its own): their first lines are fetched
+  // while this request is planned
+  auto prefetch_req = [&](size_t q) {
+    if (q >= hi) return;
+    const tmed_commit_request &r = reqs[q];
+    if (!r.commit || !r.vals) return;
+    const tmed_commit &cm = *r.commit;
+    const size_t ns = std::min<size_t>(cm.n_sigs, 128);
+    for (size_t o = 0; o < ns; o += 64) __builtin_prefetch(cm.flags + o, 0, 0);
+    if (r.vals->powers)
+      for (size_t o = 0; o < 8 * ns; o += 64) __builtin_prefetch((const uint8_t *)r.vals->powers + o, 0, 0);
+    if (r.mode == TMED_MODE_LIGHT_TRUSTING && cm.addresses)
+      for (size_t o = 0; o < 20 * ns; o += 64) __builtin_prefetch(cm.addresses + o, 0, 0);
+  };
+  for (size_t q = lo; q < lo + 4 && q < hi; q++) {  // the structs behind the requests are cold
+    __builtin_prefetch(reqs[q].commit, 0, 0);
+    __builtin_prefetch(reqs[q].vals, 0, 0);
+  }
+  prefetch_req(lo);
+  for (size_t q = lo; q < hi && p.rc == TMED_OK; q++) {
+    if (q + 4 < hi) {
+      __builtin_prefetch(reqs[q + 4].commit, 0, 0);
+      __builtin_prefetch(reqs[q + 4].vals, 0, 0);
+    }
+    prefetch_req(q + 1);
+    if (reqs[q].mode == TMED_MODE_LIGHT_TRUSTING && reqs[q].commit) {
+      plans[q].vof = p.vof.take(std::max<size_t>(reqs[q].commit->n_sigs, 1));
+      p.trusting = true;
+    }
+    p.rc = plan_request(reqs, q, out[q], plans[q], p.runs, p.ncand, addr);
+  }
+}
+
+// The template rows of the part's requests that own one, packed in request order into p.rows
+// (row_of holds part-local rows until the join).  After the pairing: tmpl_of of the part is final.
+static void rows_of_part(PlanPart &p, const tmed_commit_request *reqs, const std::vector<Plan> &plans,
+                         const Cands &cands, Templates &tp) {
+  uint32_t k = 0;
+  for (size_t q = p.lo; q < p.hi; q++) {
+    const Plan &pl = plans[q];
+    if (pl.run_lo == pl.run_hi || cands.tmpl_row((uint32_t)q) != q) {
+      tp.row_of[q] = kNoRow;
+      continue;
+    }
+    p.rows.resize((size_t)(k + 1) * tmed::kVoteTmplBytes);
+    if (!template_row(reqs[q], p.rows.data() + (size_t)k * tmed::kVoteTmplBytes, &p.rows_fit)) p.rows_bad = true;
+    tp.row_of[q] = k++;
+  }
+}
+
+// Merge pass: the part's runs into the call's (thread order = request order), its candidate offsets
+// and plans made global; then (pair) its Trusting requests paired with their Light partners, (with_grp)
+// its runs' staging segments laid out without the aliased candidates, (rows: null unless rows_here)
+// its template rows.  pair_request and add_run read runs, offsets and plans of this part only, all
+// written above in this same body.
+static void merge_part(PlanPart &p, const tmed_commit_request *reqs, std::vector<Plan> &plans, Cands &cands,
+                       bool pair, bool with_grp, Templates *rows) {
+  p.alias.clear();
+  p.grp.start();
+  p.rows.clear();
+  p.rows_fit = true;
+  p.rows_bad = false;
+  size_t c = p.cand0;
+  Run *dst = cands.runs.data() + p.run0;
+  size_t *off = cands.off.data() + p.run0;
+  for (size_t r = 0; r < p.runs.size(); r++) {
+    dst[r] = p.runs[r];
+    off[r] = c;
+    c += p.runs[r].len;
+  }
+  for (size_t q = p.lo; q < p.hi; q++) {
+    plans[q].cand_off += p.cand0;
+    plans[q].run_lo += p.run0;
+    plans[q].run_hi += p.run0;
+  }
+  if (pair) {
+    for (size_t q = p.lo; q < p.hi; q++) cands.tmpl_of[q] = (uint32_t)q;
+    for (size_t q = p.lo; q < p.hi; q++) pair_request(reqs, plans, cands, q, p.lo, p.hi, p.alias);
+    if (with_grp) {
+      size_t ap = 0;
+      for (size_t r = p.run0; r < p.run0 + p.runs.size(); r++) p.grp.add_run(cands, (uint32_t)r, p.alias, ap);
+    }
+  }
+  if (rows) rows_of_part(p, reqs, plans, cands, *rows);
+}
+
+// Join pass: the part's rows, aliases and segments into its slices of the joined arrays, which the
+// driver sized from the prefix sums.
+static void join_part(const PlanPart &p, Cands &cands, bool aliases, Group *grp, Templates *rows) {
+  if (rows) {
+    std::copy(p.rows.begin(), p.rows.end(), rows->rows.begin() + p.row0 * tmed::kVoteTmplBytes);
+    for (size_t q = p.lo; q < p.hi; q++)
+      if (rows->row_of[q] != kNoRow) rows->row_of[q] += (uint32_t)p.row0;
+  }
+  if (!aliases) return;
+  std::copy(p.alias.begin(), p.alias.end(), cands.alias.begin() + p.alias0);
+  if (grp) grp->join(p.grp, p.seg0, p.pos0);
+}
+
+// Candidates of requests [0, n) in request order (identical to a serial plan).
+static int seam_plan(const tmed_commit_request *reqs, size_t n, tmed_commit_result *out, Plans &ps, Cands &cands,
+                     const KcCall *kc = nullptr, Group *grp = nullptr, Templates *tp = nullptr) {
+  PhaseClock clk;
+  std::vector<Plan> &plans = ps.v;
+  plans.assign(n, Plan());
+  cands.clear();
+  // worker count: calls of 1,024+ requests fan out at once; smaller ones by their signature count
+  // (a blocksync batch: 128 requests of 10k signatures)
+  const unsigned nt = host_threads(n >= 1024 ? ~(size_t)0 : total_sigs(reqs, n));
+  const unsigned np = std::max(1u, nt);
+  if (ps.part.size() < np) ps.part.resize(np);
+  PlanPart *const part = ps.part.data();
+  for (unsigned t = 0; t < np; t++) {  // (a part that never runs — parallel_ranges uses at most n — keeps [n, n))
+    PlanPart &p = part[t];
+    p.lo = p.hi = n;
+    p.runs.clear();
+    p.ncand = 0;
+    p.rc = TMED_OK;
+    p.trusting = false;
+  }
+  parallel_ranges(n, nt, [&](size_t lo, size_t hi, unsigned t) { plan_part(part[t], lo, hi, reqs, out, plans, kc); });
+  for (unsigned t = 0; t < np; t++)
+    if (part[t].rc != TMED_OK) return part[t].rc;
+  clk.lap("plan_requests");
+  size_t nr = 0, cb = 0;
+  bool any_trusting = false;
+  for (unsigned t = 0; t < np; t++) {
+    PlanPart &p = part[t];
+    p.run0 = nr;
+    p.cand0 = cb;
+    nr += p.runs.size();
+    cb += p.ncand;
+    any_trusting = any_trusting || p.trusting;
+  }
+  cands.runs.resize(nr);
+  cands.off.resize(nr + 1);
+  cands.off[nr] = cb;
+  const bool pair = any_trusting && cb <= 0xffffffffu;
+  if (pair) cands.tmpl_of.resize(n);
+  // a device batch planned by several workers also gets its template rows in the merge, each worker
+  // encoding the requests of its part that own a row
+  const bool rows_here = tp && nt > 1;
+  if (tp) tp->ready = false;
+  if (rows_here) tp->row_of.resize(n);
+  // TMED_TEST_MERGE_SKEW=1 (tests): odd parts start their merge 2 ms late, so a part that read what
+  // the next part's worker writes (add_run's end of a part's last run, before the fix) reads it
+  // unwritten every time instead of rarely
+  const bool skew = nt > 1 && getenv("TMED_TEST_MERGE_SKEW") != nullptr;
+  for_parts(np, [&](unsigned t) {
+    if (skew && (t & 1)) std::this_thread::sleep_for(std::chrono::milliseconds(2));
+    merge_part(part[t], reqs, plans, cands, pair, grp != nullptr, rows_here ? tp : nullptr);
+  });
+  clk.lap("merge");
+  if (grp) *grp = Group();  // no aliases: every run whole, in order
+  size_t na = 0, ns = 0, npos = 0, nrows = 0;
+  bool rows_bad = false, rows_fit = true;
+  for (unsigned t = 0; t < np; t++) {
+    PlanPart &p = part[t];
+    p.alias0 = na;
+    p.seg0 = ns;
+    p.pos0 = npos;
+    p.row0 = nrows;
+    na += p.alias.size();
+    ns += p.grp.rix.size();
+    npos += p.grp.pos.back();
+    nrows += p.rows.size() / tmed::kVoteTmplBytes;
+    rows_bad = rows_bad || p.rows_bad;
+    rows_fit = rows_fit && p.rows_fit;
+  }
+  if (rows_bad) return TMED_EINVAL;  // the encoder rejected a request (as device_templates does)
+  const bool aliases = na != 0;
+  cands.alias.resize(na);
+  if (grp && aliases) grp->resize(ns);
+  if (rows_here) {
+    tp->nrows = nrows;
+    tp->rows.resize(std::max<size_t>(nrows, 1) * tmed::kVoteTmplBytes);
+  }
+  if (aliases || rows_here)
+    for_parts(np, [&](unsigned t) { join_part(part[t], cands, aliases, grp, rows_here ? tp : nullptr); });
+  if (aliases && grp && nt > 1) {  // finish_batch works part by part
+    cands.preq.resize(np + 1, n);
+    cands.pal.resize(np + 1, na);
+    cands.pseg.resize(np + 1, ns);
+    for (unsigned t = 0; t < np; t++) {
+      cands.preq[t] = part[t].lo;
+      cands.pal[t] = part[t].alias0;
+      cands.pseg[t] = part[t].seg0;
+    }
+  }
+  if (rows_here) {
+    tp->fits = rows_fit;
+    tp->ready = true;
+  }
+  clk.lap("aliases");
+  clk.emit("plan", n, cb);
+  return TMED_OK;
 }
 
 // ---- replay of every reference loop over the validity bits (parallel over requests) ----
@@ -1020,36 +1028,22 @@ static void build_group(const Cands &c, Group &g) {
   const unsigned nt = c.alias.size() >= 8192 ? host_threads(c.size()) : 1u;
   std::vector<Group> part(std::max(1u, std::min<unsigned>(nt, (unsigned)std::max<size_t>(nr, 1))));
   parallel_ranges(nr, nt, [&](size_t lo, size_t hi, unsigned t) {
-    Group mine;  // (a header of its own: see seam_plan)
+    Group mine;  // (built in a header of its own, not next to the neighbours' in part: see PlanPart)
     mine.start();
     // c (runs, off, alias) is complete before this region (seam_plan returned): no part writes it
     const auto a0 = std::lower_bound(c.alias.begin(), c.alias.end(), std::make_pair((uint32_t)c.off[lo], 0u));
     size_t ap = (size_t)(a0 - c.alias.begin());
     for (size_t r = lo; r < hi; r++) mine.add_run(c, (uint32_t)r, c.alias, ap);
-    part[t].rix.swap(mine.rix);
-    part[t].ub.swap(mine.ub);
-    part[t].pos.swap(mine.pos);
+    part[t] = std::move(mine);
   });
-  size_t ns = 0;
   std::vector<size_t> sbase(part.size() + 1, 0), pbase(part.size() + 1, 0);
   for (size_t t = 0; t < part.size(); t++) {
-    const size_t k = part[t].rix.size();
-    sbase[t + 1] = sbase[t] + k;
-    pbase[t + 1] = pbase[t] + (k ? part[t].pos.back() : 0);
-    ns += k;
+    sbase[t + 1] = sbase[t] + part[t].rix.size();
+    pbase[t + 1] = pbase[t] + (part[t].pos.empty() ? 0 : part[t].pos.back());
   }
-  g.rix.resize(ns);
-  g.ub.resize(ns);
-  g.pos.resize(ns + 1);
-  g.pos[0] = 0;
+  g.resize(sbase[part.size()]);
   parallel_ranges(part.size(), (unsigned)part.size(), [&](size_t lo, size_t hi, unsigned) {
-    for (size_t t = lo; t < hi; t++) {
-      const Group &p = part[t];
-      const size_t k = p.rix.size(), s = sbase[t], pb = pbase[t];
-      std::copy(p.rix.begin(), p.rix.end(), g.rix.begin() + s);
-      std::copy(p.ub.begin(), p.ub.end(), g.ub.begin() + s);
-      for (size_t j = 0; j < k; j++) g.pos[s + j + 1] = pb + p.pos[j + 1];
-    }
+    for (size_t t = lo; t < hi; t++) g.join(part[t], sbase[t], pbase[t]);
   });
 }
 
@@ -1074,17 +1068,6 @@ static void for_segments(const Cands &c, const Group &g, size_t lo, size_t hi, F
     const uint32_t u = g.base(j);
     if (a < b) f(j, u + (uint32_t)(a - pos[j]), u + (uint32_t)(b - pos[j]), a);
   }
-}
-
-// Request q's template row (kVoteTmplBytes at row); false: the encoder rejected the request
-// (bad), or *fit = false when its template does not fit the device assembler.
-static bool template_row(const tmed_commit_request &rq, uint8_t *row, bool *fit) {
-  const tmed_vote_template t = vote_template_of(rq);
-  tmed::VoteEncoder e;
-  if (e.init(&t) != TMED_OK) return false;
-  memset(row, 0, tmed::kVoteTmplBytes);
-  if (!e.device_template(row, tmed::kVoteTmplBytes, tmed::kVoteSlot)) *fit = false;
-  return true;
 }
 
 static int device_templates(const tmed_commit_request *reqs, size_t n, const Cands &cands, Templates &tp,
