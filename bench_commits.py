@@ -1188,6 +1188,8 @@ def main():
                     help="C4: a tmed_blocksync_verify call per window only (no submit/wait stream pass)")
     ap.add_argument("--no-pinned", action="store_true",
                     help="C4: commits in ordinary (pageable) memory: signatures go through the seam's staging copy")
+    ap.add_argument("--rule", choices=["go", "zip215"], default="go",
+                    help="the context's signature rule for every leg (tmed_set_rule): go, the default, or zip215")
     args = ap.parse_args()
     import torch
     import torch.distributed as dist
@@ -1195,6 +1197,8 @@ def main():
     from tmed.launch import dist_setup, gpu_count_fields
     world, rank, local, dev, coll = dist_setup()
     eng = Engine(local)
+    if args.rule == "zip215":
+        eng.set_rule(Engine.RULE_ZIP215)
     for cfg in args.config.split(","):
         if cfg == "c1" and rank == 0:
             r = c1(eng, args.reps, not args.no_cpu)
@@ -1212,6 +1216,7 @@ def main():
         else:
             continue
         if rank == 0:
+            r["rule"] = args.rule
             print(json.dumps(r), flush=True)
     if world > 1:
         dist.destroy_process_group()

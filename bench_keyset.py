@@ -3,7 +3,10 @@
 validators with the per-validator-set key cache on (tmed_verify_batch_keyset_device: A decoded
 once per key, [k](-A) from the key's signed radix-256 comb, no doublings), the path the commit
 seam takes for blocksync (C4) and the light client (C3).  Inputs resident in HBM, one step =
-one verification pass; prints one JSON line like bench.py (rank 0; N ranks = N shards)."""
+one verification pass; prints one JSON line like bench.py (rank 0; N ranks = N shards).
+--rule zip215: the same leg through tmed_verify_batch_keyset_zip215_device (the key-cached kernels and
+the per-signature ZIP-215 finish); --rule msm: the same signatures and keys through
+tmed_verify_batch_zip215_device (the batch equation by MSM, keys by value), for comparison."""
 from __future__ import annotations
 
 import argparse
@@ -29,6 +32,9 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--sorted", action="store_true", help="signatures ordered by validator index (as in a commit)")
+    ap.add_argument("--rule", choices=["go", "zip215", "msm"], default="go",
+                    help="go: tmed_verify_batch_keyset_device; zip215: tmed_verify_batch_keyset_zip215_device; "
+                         "msm: tmed_verify_batch_zip215_device on the same tuples")
     args = ap.parse_args()
     import torch
     from tmed import Engine
@@ -66,7 +72,12 @@ def main():
     t_gen = time.time() - t_gen
 
     def step():
-        eng.verify_keyset_device(ks, d_vi, d_sig, d_msg, d_off, d_out, n, st.cuda_stream)
+        if args.rule == "zip215":
+            eng.verify_batch_keyset_zip215_device(ks, d_vi, d_sig, d_msg, d_off, d_out, n, st.cuda_stream)
+        elif args.rule == "msm":
+            eng.verify_zip215_device(d_pub, d_sig, d_msg, d_off, d_out, n, st.cuda_stream)
+        else:
+            eng.verify_keyset_device(ks, d_vi, d_sig, d_msg, d_off, d_out, n, st.cuda_stream)
 
     for _ in range(args.warmup):
         step()
@@ -79,11 +90,13 @@ def main():
     torch.cuda.synchronize(dev)
     dt = time.perf_counter() - t0
     valid = int(d_out.sum().item())
-    eng.set_kernel_timing(True)
-    step()
-    torch.cuda.synchronize(dev)
-    (prep_ms, main_ms, fin_ms), (pl, ml, fl) = eng.kernel_times()
-    eng.set_kernel_timing(False)
+    prep_ms = main_ms = fin_ms = 0.0
+    if args.rule != "msm":  # (the MSM entry records no per-kind kernel times)
+        eng.set_kernel_timing(True)
+        step()
+        torch.cuda.synchronize(dev)
+        (prep_ms, main_ms, fin_ms), (pl, ml, fl) = eng.kernel_times()
+        eng.set_kernel_timing(False)
     kbits = eng.keyset_b_window_bits()
     abits = eng.keyset_a_window_bits(ks)
     eng.keyset_free(ks)
@@ -96,7 +109,7 @@ def main():
             "all_valid": valid == n and ok_first == n, "keyset_build_s": round(t_ks, 3), "setup_s": round(t_gen, 2),
             "mads_per_verify_main": mads_keyset_main(kbits, abits), "b_window_bits": kbits, "a_window_bits": abits,
             "kernel_ms": {"prep": round(prep_ms, 4), "main": round(main_ms, 4), "finish": round(fin_ms, 4)},
-            "sorted": args.sorted,
+            "sorted": args.sorted, "rule": args.rule,
             "data": "synthetic (10k seeded keys, CanonicalVote sign-bytes, GPU RFC 8032 signer)",
             "config": {"workload": "C2 variant: %d signatures by %d validators, key cache on" % (n, nk)}}), flush=True)
 

@@ -205,6 +205,44 @@ int tmed_zip215_set_seed(const uint8_t *seed32);
  * signature, signatures decided singly. */
 int tmed_zip215_stats(uint32_t out[4]);
 
+/*
+ * The same rule by key index.  Same contract as tmed_verify_batch_keyset(_device): the host form
+ * returns TMED_EINVAL for a key index past the set, the device form rejects that signature; a key
+ * that does not decode rejects its signatures (keys decode identically under both rules: Point.SetBytes
+ * is ZIP-215's permissive decoding); sig_lens as in tmed_verify_batch.  out_valid[i] is the ZIP-215
+ * single-signature decision stated above.  The decision is exact and deterministic: the key-cached
+ * prep and main kernels leave P = [S]B + [k](-A), and one lane per signature decodes R permissively
+ * and checks [8](P - R) = O.  No random weights and no host read-back in the middle, which is why
+ * this form, and not the batch equation, is what the seam queues under TMED_RULE_ZIP215.
+ */
+int tmed_verify_batch_keyset_zip215(tmed_ctx *ctx, uint64_t handle, const uint32_t *val_idx, const uint8_t *sigs,
+                                    const uint32_t *sig_lens, const uint8_t *msgs, const uint32_t *msg_off, size_t n,
+                                    uint8_t *out_valid);
+int tmed_verify_batch_keyset_zip215_device(tmed_ctx *ctx, uint64_t handle, const uint32_t *d_val_idx,
+                                           const uint8_t *d_sigs, const uint8_t *d_msgs, const uint32_t *d_msg_off,
+                                           size_t n, uint8_t *d_out_valid, void *stream);
+
+/*
+ * The signature rule of a context's SEAM calls: tmed_verify_commits, tmed_blocksync_verify / _submit /
+ * _wait, tmed_light_verify, tmed_verify_votes and the _multi forms (TMED_EINVAL when their contexts'
+ * rules differ).  A new context has TMED_RULE_GO.  tmed_set_rule collects the submitted blocksync
+ * windows first, as every seam call does, so a window is decided under the rule it was submitted
+ * under, and a call reads the rule once: no call mixes rules.  TMED_EINVAL for an unknown rule.
+ * ONLY THE SIGNATURE DECISION CHANGES.  The loops, prechecks, early exits, candidate selection and
+ * error values stay v0.34.24's: a chain on a later release that verifies with ZIP-215 gets that
+ * release's signature decisions inside 0.34's VerifyCommit* / light.Verify / Vote.Verify loops (a
+ * shim for a later release's loops replays them over tmed_verify_batch_keyset_zip215's bits).
+ * The raw batch calls keep the rule their name states (tmed_verify_batch, tmed_verify_batch_keyset
+ * and their _device forms: always the Go rule), the *_with entries take the caller's verifier.
+ * The key-set cache is untouched by a rule change (keys decode identically under both rules).
+ * Under TMED_RULE_ZIP215 key-cached batches take tmed_verify_batch_keyset_zip215's kernels and
+ * generic batches the exact single check per signature (no batch equation in the seam).
+ */
+#define TMED_RULE_GO 0     /* Go 1.18 crypto/ed25519.Verify: the default, as today */
+#define TMED_RULE_ZIP215 1 /* the rule stated at tmed_verify_batch_zip215 */
+int tmed_set_rule(tmed_ctx *ctx, int rule);
+int tmed_rule(const tmed_ctx *ctx);
+
 /* ---------------------------------------------------------------- commits */
 
 /*
@@ -345,11 +383,17 @@ int tmed_test_zip_msm(tmed_ctx *ctx, uint32_t n, const uint8_t *points, const in
  * bytes, `out` after the finish: position p's byte is bits_in && Z != 0 && enc(X/Z, Y/Z) == r at
  * that same index; a byte no position owns is 0xAA.
  * TMED_EINVAL: m = 0, m > 2^20, fin_base + m > 2^21, a perm entry out of range.
+ *
+ * tmed_test_finish_zip215: the same arguments through the ZIP-215 finish (launch_finish_zip,
+ * keyset_finish_zip_kernel, zip_finish.h) on the context's own fin buffer: position p's byte is
+ * bits_in && Z != 0 && r decodes permissively && [8]((X : Y : Z) - r) is the identity.
  */
 int tmed_test_key_order(tmed_ctx *ctx, const uint32_t *val_idx, uint32_t n, uint32_t nkeys, uint32_t index_base,
                         uint32_t *perm_out, uint32_t *cursor_out, uint32_t *nbins_out, uint32_t *shift_out);
 int tmed_test_finish(tmed_ctx *ctx, uint32_t m, const int32_t *xyz, const uint8_t *r, const uint32_t *perm,
                      uint32_t fin_base, const uint8_t *bits_in, uint8_t *bits_out);
+int tmed_test_finish_zip215(tmed_ctx *ctx, uint32_t m, const int32_t *xyz, const uint8_t *r, const uint32_t *perm,
+                            uint32_t fin_base, const uint8_t *bits_in, uint8_t *bits_out);
 
 /*
  * With TMED_DEBUG_ZERO set at the first pipelined generic batch: every staged candidate whose

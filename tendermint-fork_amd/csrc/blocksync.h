@@ -25,9 +25,9 @@
 // one cycle between the two files): a batch is staged as a seam call's group is, and a batch whose
 // templates do not fit the device assembler takes the seam's host-message route.
 static int stage_group(tmed_ctx *ctx, const tmed_commit_request *reqs, size_t n, const Cands &cands, const Group &grp,
-                       uint64_t keyset, const Templates &tp, int slot, tmed::VoteStage &st);
+                       uint64_t keyset, const Templates &tp, int slot, tmed::VoteStage &st, int rule);
 static int ctx_verify_host_msgs(tmed_ctx *ctx, const tmed_commit_request *reqs, size_t n, const Cands &cands,
-                                uint8_t *valid);
+                                uint8_t *valid, int rule);
 
 namespace {
 struct BsWindow {
@@ -35,6 +35,7 @@ struct BsWindow {
   tmed_commit_result *out = nullptr;
   size_t n = 0, bsz = 0, next = 0;          // requests; per batch; the next one to batch
   uint64_t keyset = 0;
+  int rule = TMED_RULE_GO;  // the signature rule its call read at its entry: every batch of the window runs under it
   const KcCall *kc = nullptr;  // planning's cached address indexes (a call-scoped window only)
   // a submitted window owns its requests, its resolved set and its key-set cache pin (held until
   // its last batch is collected; released outside ctx->mu: ~KcCall takes it)
@@ -205,7 +206,7 @@ static int bs_pump(tmed_ctx *ctx, BsStream &S, BsWindow &w, double ph[3], std::u
     clk.lap("templates");
     if (rc == TMED_OK && m) {
       if (fits && m <= 0xffffffffu) {
-        rc = stage_group(ctx, rq, b.n, b.cands, b.grp, w.keyset, b.tmpl, (int)(idx % ns), b.st);
+        rc = stage_group(ctx, rq, b.n, b.cands, b.grp, w.keyset, b.tmpl, (int)(idx % ns), b.st, w.rule);
         // key-cached batches alternate between the two kernel lanes, so one batch's small kernels
         // (assembly, key order, prep, finish) run beside the other's main kernel
         b.st.lane = w.keyset && (idx & 1) && tmed::lanes_on() ? 1 : 0;
@@ -223,7 +224,7 @@ static int bs_pump(tmed_ctx *ctx, BsStream &S, BsWindow &w, double ph[3], std::u
         if (rc == TMED_OK && mid.n && &mid != &b) rc = bs_finish(ctx, mid, ph);
         lk.unlock();
         b.valid.assign(m, 0);
-        if (rc == TMED_OK) rc = ctx_verify_host_msgs(ctx, rq, b.n, b.cands, b.valid.data());
+        if (rc == TMED_OK) rc = ctx_verify_host_msgs(ctx, rq, b.n, b.cands, b.valid.data(), w.rule);
         lk.lock();
       }
     }
@@ -289,7 +290,7 @@ void bs_release_collected(tmed_ctx *c) { bs_reap(c); }
 
 // One window through the stream and back (every batch collected before returning).
 static int run_pipelined(tmed_ctx *ctx, const tmed_commit_request *reqs, size_t nb, size_t bsz, uint64_t keyset,
-                         tmed_commit_result *out, const KcCall *kc) {
+                         tmed_commit_result *out, const KcCall *kc, int rule) {
   std::vector<std::unique_ptr<BsWindow>> gone;
   int rc;
   {
@@ -305,6 +306,7 @@ static int run_pipelined(tmed_ctx *ctx, const tmed_commit_request *reqs, size_t 
     w->n = nb;
     w->bsz = std::max<size_t>(1, bsz);
     w->keyset = keyset;
+    w->rule = rule;
     w->kc = kc;
     BsWindow *wp = w.get();
     S.wins.push_back(std::move(w));
@@ -369,6 +371,7 @@ static int bs_window(tmed_ctx *ctx, const tmed_blocksync_window *w, uint32_t bat
   W.n = nb;
   W.bsz = batch_blocks ? batch_blocks : 128;
   W.keyset = nb ? W.own_reqs[0].vals->keyset : 0;
+  W.rule = tmed::seam_rule(ctx);
   return TMED_OK;
 }
 
@@ -421,7 +424,7 @@ extern "C" int tmed_blocksync_verify(tmed_ctx *ctx, const tmed_blocksync_window 
     std::unique_ptr<BsWindow> win;
     int rc = bs_window(ctx, w, batch_blocks, out, win);
     if (rc != TMED_OK || win->n == 0) return rc;
-    return run_pipelined(ctx, win->rq, win->n, win->bsz, win->keyset, out, nullptr);
+    return run_pipelined(ctx, win->rq, win->n, win->bsz, win->keyset, out, nullptr, win->rule);
   });
 }
 

@@ -50,7 +50,7 @@
 
 // Host fallback of the GPU verifier for templates the device assembler cannot hold.
 static int ctx_verify_host_msgs(tmed_ctx *ctx, const tmed_commit_request *reqs, size_t n, const Cands &cands,
-                                uint8_t *valid) {
+                                uint8_t *valid, int rule) {
   CandBatch cb;
   int rc = build_cand_batch(reqs, n, cands, cb);
   if (rc != TMED_OK) return rc;
@@ -77,10 +77,10 @@ static int ctx_verify_host_msgs(tmed_ctx *ctx, const tmed_commit_request *reqs, 
       total += len;
     }
     offs[m] = (uint32_t)total;
-    rc = g.first == 0 ? tmed_verify_batch(ctx, pubs.data(), sigs.data(), lens.data(), msgs.data(), offs.data(), m,
-                                          out.data())
-                      : tmed_verify_batch_keyset(ctx, g.first, vidx.data(), sigs.data(), lens.data(), msgs.data(),
-                                                 offs.data(), m, out.data());
+    rc = g.first == 0 ? tmed::verify_batch_rule(ctx, pubs.data(), sigs.data(), lens.data(), msgs.data(), offs.data(), m,
+                                                out.data(), rule)
+                      : tmed::verify_batch_keyset_rule(ctx, g.first, vidx.data(), sigs.data(), lens.data(), msgs.data(),
+                                                       offs.data(), m, out.data(), rule);
     if (rc != TMED_OK) return rc;
     for (size_t j = 0; j < m; j++) valid[ix[j]] = out[j];
   }
@@ -93,11 +93,12 @@ static int ctx_verify_host_msgs(tmed_ctx *ctx, const tmed_commit_request *reqs, 
 // pinned staging area, run by run (multi-threaded for large batches).  The caller holds ctx->mu.
 constexpr size_t kDmaMinRun = 256;  // signatures (16 KB)
 static int stage_group(tmed_ctx *ctx, const tmed_commit_request *reqs, size_t n, const Cands &cands, const Group &grp,
-                       uint64_t keyset, const Templates &tp, int slot, tmed::VoteStage &st) {
+                       uint64_t keyset, const Templates &tp, int slot, tmed::VoteStage &st, int rule) {
   const bool keyed = keyset != 0;
   const uint32_t m = (uint32_t)grp.size(cands);
   int rc = tmed::votes_stage(ctx, keyset, m, std::max<size_t>(tp.nrows, 1), st, slot);
   if (rc != TMED_OK) return rc;
+  st.rule = rule;
   memcpy(st.tmpl, tp.rows.data(), std::max<size_t>(tp.nrows, 1) * tmed::kVoteTmplBytes);
   std::atomic<bool> key_ok{true};
   const uint32_t nkeys = keyed ? (uint32_t)st.ks->n : 0u;
@@ -191,13 +192,13 @@ static int stage_group(tmed_ctx *ctx, const tmed_commit_request *reqs, size_t n,
 // GPU verifier of one seam call: candidates of validator sets with a key-set handle go
 // through the key-cached kernels, one launch sequence per distinct key set.
 static int ctx_verify(tmed_ctx *ctx, const tmed_commit_request *reqs, size_t n, const Cands &cands,
-                      uint8_t *valid) {
+                      uint8_t *valid, int rule) {
   PhaseClock clk;
   thread_local Templates tmpl;
   bool fits = true;
   int rc = device_templates(reqs, n, cands, tmpl, &fits);
   if (rc != TMED_OK) return rc;
-  if (!fits) return ctx_verify_host_msgs(ctx, reqs, n, cands, valid);
+  if (!fits) return ctx_verify_host_msgs(ctx, reqs, n, cands, valid, rule);
   clk.lap("templates");
   // the runs by key set (usually a single group: then it is every run, in order)
   std::vector<uint64_t> gkeys;
@@ -211,7 +212,7 @@ static int ctx_verify(tmed_ctx *ctx, const tmed_commit_request *reqs, size_t n, 
     const uint32_t m = (uint32_t)grp.size(cands);
     if (m == 0) continue;
     tmed::VoteStage st;
-    rc = stage_group(ctx, reqs, n, cands, grp, gkeys[g], tmpl, 0, st);
+    rc = stage_group(ctx, reqs, n, cands, grp, gkeys[g], tmpl, 0, st, rule);
     clk.lap("stage");
     std::vector<uint8_t> out(m);
     if (rc == TMED_OK) rc = tmed::votes_launch(ctx, st, out.data());
@@ -235,7 +236,9 @@ static size_t pipe_batch_sigs() {
   return e ? std::max<size_t>(1, strtoull(e, nullptr, 10)) : (size_t)1 << 19;
 }
 
-static int verify_commits_impl(tmed_ctx *ctx, const tmed_commit_request *reqs, size_t n, tmed_commit_result *out) {
+// rule: the context's rule as the entry point read it (tmed::seam_rule), once for the whole call.
+static int verify_commits_impl(tmed_ctx *ctx, const tmed_commit_request *reqs, size_t n, tmed_commit_result *out,
+                               int rule) {
   if (!ctx) return TMED_EINVAL;
   KcCall kc;
   reqs = keycache_resolve(ctx, reqs, n, kc);
@@ -261,7 +264,7 @@ static int verify_commits_impl(tmed_ctx *ctx, const tmed_commit_request *reqs, s
     if (ok && sigs >= 2 * kPipeBatchSigs) {
       const size_t bsz = std::max<size_t>(16, kPipeBatchSigs / std::max<size_t>(1, sigs / n));
       if (n > bsz) {
-        const int rc = run_pipelined(ctx, reqs, n, bsz, ks, out, &kc);
+        const int rc = run_pipelined(ctx, reqs, n, bsz, ks, out, &kc, rule);
         bs_reap(ctx);
         return rc;
       }
@@ -270,7 +273,7 @@ static int verify_commits_impl(tmed_ctx *ctx, const tmed_commit_request *reqs, s
   const int rc = run_seam(
       reqs, n, out,
       [&](const tmed_commit_request *rq, size_t nr, const Cands &cands, uint8_t *valid) {
-        return ctx_verify(ctx, rq, nr, cands, valid);
+        return ctx_verify(ctx, rq, nr, cands, valid, rule);
       },
       &kc);
   bs_reap(ctx);  // submitted windows this call collected (ctx_verify drained the stream) leave now
@@ -279,7 +282,8 @@ static int verify_commits_impl(tmed_ctx *ctx, const tmed_commit_request *reqs, s
 
 extern "C" int tmed_verify_commits(tmed_ctx *ctx, const tmed_commit_request *reqs, size_t n,
                                    tmed_commit_result *out) {
-  return c_guard(ctx, [&] { return verify_commits_impl(ctx, reqs, n, out); });
+  if (!ctx) return TMED_EINVAL;
+  return c_guard(ctx, [&] { return verify_commits_impl(ctx, reqs, n, out, tmed::seam_rule(ctx)); });
 }
 
 // ---- light.Verify (light/verifier.go:135-151; the replay is light_host.h) -------------------------
@@ -324,13 +328,14 @@ static int light_hashes_device(tmed_ctx *ctx, const tmed_light_request *reqs, co
 extern "C" int tmed_light_verify(tmed_ctx *ctx, const tmed_light_request *reqs, size_t n, uint32_t flags,
                                  tmed_light_result *out) {
   if (!ctx) return TMED_EINVAL;
+  const int rule = tmed::seam_rule(ctx);  // one rule for both of the call's commit batches
   return c_guard(ctx, [&] {
     return tmed_light::light_run(
         reqs, n, flags, out,
         [&](const std::vector<size_t> &need_hdr, const std::vector<size_t> &need_vals, uint8_t *hh, uint8_t *hok,
             uint8_t *vh) { return light_hashes_device(ctx, reqs, need_hdr, need_vals, hh, hok, vh); },
         [&](const tmed_commit_request *rq, size_t m, tmed_commit_result *res) {
-          return verify_commits_impl(ctx, rq, m, res);
+          return verify_commits_impl(ctx, rq, m, res, rule);
         });
   });
 }
@@ -394,10 +399,14 @@ static int run_shards(size_t n_ctx, const std::vector<size_t> &cut, F &&f) {
   return TMED_OK;
 }
 
+// Every context present and under one signature rule (a call sharded over contexts of different
+// rules would decide its shards differently: TMED_EINVAL).
 static bool ctxs_ok(tmed_ctx *const *ctxs, size_t n_ctx) {
   if (!ctxs || n_ctx == 0) return false;
   for (size_t t = 0; t < n_ctx; t++)
     if (!ctxs[t]) return false;
+  for (size_t t = 1; t < n_ctx; t++)
+    if (tmed::seam_rule(ctxs[t]) != tmed::seam_rule(ctxs[0])) return false;
   return true;
 }
 

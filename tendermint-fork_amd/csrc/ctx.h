@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <mutex>
 #include <unordered_map>
 #include <vector>
@@ -152,8 +153,17 @@ int median_times_locked(tmed_ctx *c, const tmed_median_request *reqs, size_t n, 
 int verify_votes_locked(tmed_ctx *c, const tmed_vote_request *reqs, size_t n, uint8_t *codes);
 // keyset.hip: a key-cached batch of device-resident tuples on stream s, as the commit seam runs it
 // (latency kernels up to lat_max, the throughput kernels above); inside a scratch_acquire/release pair.
+// rule: TMED_RULE_* of the call (the seam passes the rule it read once at its entry).
 hipError_t keyset_verify_batch(tmed_ctx *c, Keyset &k, const uint32_t *d_idx, const uint8_t *d_sig, const uint8_t *d_msgs,
-                               const uint32_t *d_off, uint32_t n, uint8_t *d_out, hipStream_t s, bool msg_slots);
+                               const uint32_t *d_off, uint32_t n, uint8_t *d_out, hipStream_t s, bool msg_slots, int rule);
+// The raw host batches by rule: tmed_verify_batch (tmed_capi.hip) and tmed_verify_batch_keyset
+// (keyset.hip) are these under TMED_RULE_GO; the seam's host-message route passes its call's rule.
+int verify_batch_rule(tmed_ctx *c, const uint8_t *pub, const uint8_t *sig, const uint32_t *sig_lens, const uint8_t *msgs,
+                      const uint32_t *off, size_t n, uint8_t *out, int rule);
+int verify_batch_keyset_rule(tmed_ctx *c, uint64_t handle, const uint32_t *val_idx, const uint8_t *sigs,
+                             const uint32_t *sig_lens, const uint8_t *msgs, const uint32_t *off, size_t n, uint8_t *out,
+                             int rule);
+static_assert(kRuleGo == TMED_RULE_GO && kRuleZip215 == TMED_RULE_ZIP215, "kernels.h rule values");
 struct Lane;
 void lane_release(Lane &L);    // keyset.hip: the second kernel lane's stream and scratch
 bool lanes_on();               // keyset.hip: TMED_LANES != 1
@@ -218,6 +228,9 @@ struct VoteStage {
   };
   std::vector<Dma> dma;
   bool sig_direct = false;
+  // The signature rule of the seam call this batch belongs to (TMED_RULE_*): set by whoever stages
+  // the batch from the rule its call read once, so a call's batches never mix rules.
+  int rule = TMED_RULE_GO;
   // Kernel lane: 0 = the context stream; 1 = the second kernel stream of the key-cached
   // throughput batches (its own scratch, ctx.h Lane), so consecutive batches of the pipelined seam
   // overlap on the device (one batch's small kernels beside the other's main kernel).
@@ -269,6 +282,10 @@ struct Lane {
 
 struct tmed_ctx {
   int device = 0;
+  // The signature rule of the seam calls (tmed_set_rule, written under mu after the submitted
+  // blocksync windows are collected).  A seam call reads it once at its entry (seam_rule) and hands
+  // that value down; the raw batch calls never read it.
+  std::atomic<int> rule{TMED_RULE_GO};
   hipStream_t stream = nullptr;
   hipStream_t copy_stream = nullptr;  // H2D of staged votes, so batch b's copy overlaps b-1's kernels
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -375,18 +392,24 @@ inline uint32_t last_chunk_count(uint32_t n, uint32_t chunk) {
 // c->glat_max signatures, the throughput pipeline above.  Inside a scratch_acquire/release pair.
 // va: assemble the vote sign-bytes inside the latency kernels (only when n <= glat_max, where
 // generic_uses_glat says they run; the caller then skips assemble_votes).
-inline bool generic_uses_glat(const tmed_ctx *c, uint32_t n) { return n <= c->glat_max; }
+// rule = TMED_RULE_ZIP215: the exact single check of the half-size path (launch_verify zip215) for
+// every batch size: the latency kernels have no ZIP-215 form and are not taken.
+inline int seam_rule(const tmed_ctx *c) { return c->rule.load(std::memory_order_relaxed); }
+inline bool generic_uses_glat(const tmed_ctx *c, uint32_t n, int rule = TMED_RULE_GO) {
+  return rule == TMED_RULE_GO && n <= c->glat_max;
+}
 inline hipError_t generic_verify(tmed_ctx *c, const uint8_t *pub, const uint8_t *sig, const uint8_t *msgs,
                                  const uint32_t *off, uint32_t n, uint8_t *out, hipStream_t s, bool msg_slots,
-                                 KernelTimer *timer, const VoteAsm *va = nullptr) {
-  if (generic_uses_glat(c, n)) {
+                                 KernelTimer *timer, const VoteAsm *va = nullptr, int rule = TMED_RULE_GO) {
+  if (generic_uses_glat(c, n, rule)) {
     c->last_hs_count = 0;  // no half-size hand-off in d_prep (tmed_window_stats)
     return launch_verify_glat(pub, sig, msgs, off, n, out, c->d_bcomb16, c->d_glat, s, msg_slots, timer, va);
   }
   if (va) return hipErrorInvalidValue;
   hipError_t e = launch_verify(pub, sig, msgs, off, n, out, c->d_slab, c->slab_slots, BTabs{c->d_b16, c->d_bcomb16, c->d_b26},
-                               c->d_prep, c->d_fin, c->d_fin_pre, s, c->chunk, c->main_waves, msg_slots, timer);
-  c->last_hs_count = (e != hipSuccess || c->main_waves == 5) ? 0 : last_chunk_count(n, c->chunk);
+                               c->d_prep, c->d_fin, c->d_fin_pre, s, c->chunk, c->main_waves, msg_slots, timer,
+                               rule == TMED_RULE_ZIP215);
+  c->last_hs_count = (e != hipSuccess || (c->main_waves == 5 && rule == TMED_RULE_GO)) ? 0 : last_chunk_count(n, c->chunk);
   return e;
 }
 inline hipError_t scratch_release(tmed_ctx *c, hipStream_t s) {

@@ -49,6 +49,18 @@ constexpr size_t kFinPreBytes = (size_t)kFinPreStride * 3 * 16;
 // signature fin_base + p, or perm[fin_base + p] (the key-grouped order); out[i] &= enc(R') == R.
 hipError_t launch_finish(const int4 *fin, int4 *pre, const uint8_t *sig, uint8_t *out, uint32_t fin_base, uint32_t m,
                          hipStream_t stream, const uint32_t *perm = nullptr);
+// The signature rule of a key-cached batch (include/tmed25519.h TMED_RULE_*; ctx.h checks the values).
+constexpr int kRuleGo = 0, kRuleZip215 = 1;
+// The same slots under the ZIP-215 rule (zip_finish.hip, zip_finish.h): one lane per signature,
+// out[i] &= Z != 0 && R decodes permissively && [8](R' - R) is the identity.  No prefix buffer.
+hipError_t launch_finish_zip(const int4 *fin, const uint8_t *sig, uint8_t *out, uint32_t fin_base, uint32_t m,
+                             hipStream_t stream, const uint32_t *perm = nullptr);
+// The latency route's form (zip_finish.hip): fin slots [0, m) of signatures [0, m) and the R blocks'
+// decode in dec ([q][i], kLatDecRows int4 a signature: x, y, strict flag): R comes from dec where the
+// flag is set, from the signature's bytes (permissive decode in the lane) where it is not.
+constexpr int kLatDecRows = 6;
+hipError_t launch_lat_finish_zip(const int4 *fin, const int4 *dec, const uint8_t *sig, uint8_t *out, uint32_t m,
+                                 hipStream_t stream);
 // Tests (tmed_test_finish): m rows of 30 int32 limbs (X, Y, Z) into fin slots [0, m) in fin_store's
 // layout, each row's 32-byte R into the R half of its signature row and its bit into out.
 hipError_t launch_test_fin_fill(const int32_t *xyz, const uint8_t *r, const uint8_t *bits, const uint32_t *perm,
@@ -158,13 +170,14 @@ hipError_t launch_build_comba(const uint8_t *pubs, uint32_t n, int32_t *bases, i
 // >= nkeys rejects that signature); acomb / acomba: the key set's chunk tables (kKeyChunk*).  perm (nullable, n entries of scratch) + order_scratch
 // (key_order_scratch_words): the main and finish kernels visit each chunk's signatures in
 // key-grouped order (launch_key_order per chunk); decisions still land at out[i].
+// rule = kRuleZip215: the same prep and main kernels, then launch_finish_zip instead of launch_finish.
 hipError_t launch_verify_keyset(const uint32_t *val_idx, uint32_t nkeys, const uint8_t *key_pub, const uint8_t *key_ok,
                                 const int4 *const *acomb, const int4 *bcomb, const uint8_t *sig, const uint8_t *msgs,
                                 const uint32_t *off, uint32_t n, uint8_t *out, int4 *prep, uint32_t stride,
                                 int4 *fin, int4 *fin_pre, hipStream_t stream, bool msg_slots = false,
                                 KernelTimer *timer = nullptr, uint32_t *perm = nullptr,
                                 uint32_t *order_scratch = nullptr, const int4 *bcomb24 = nullptr,
-                                const int4 *const *acomba = nullptr);
+                                const int4 *const *acomba = nullptr, int rule = kRuleGo);
 // Key-grouped visiting order of a key-cached batch (counting sort of val_idx by groups of
 // consecutive keys, indices >= nkeys last): perm[0..n) = signature indices grouped by key.
 // scratch: key_order_scratch_words(n, nkeys) u32.  The comb rows of the lanes in flight then
@@ -213,10 +226,13 @@ constexpr uint32_t kLatMax = 1u << 16;
 struct VoteAsm;
 // va (vote slots only): every lane of a signature's group assembles the vote's sign-bytes into
 // its slot first (identical bytes; no separate assemble_votes launch in front).
+// rule = kRuleZip215: the same launch (the R blocks decode beside the comb sum), then
+// launch_lat_finish_zip instead of verify_lat_finish_kernel.
 hipError_t launch_verify_keyset_lat(const uint32_t *val_idx, uint32_t nkeys, const uint8_t *key_pub, const uint8_t *key_ok,
                                     const int4 *const *acomb, const int4 *bcomb, const uint8_t *sig, const uint8_t *msgs,
                                     const uint32_t *off, uint32_t n, uint8_t *out, int4 *fin, int4 *dec,
-                                    hipStream_t stream, bool msg_slots = false, const VoteAsm *va = nullptr);
+                                    hipStream_t stream, bool msg_slots = false, const VoteAsm *va = nullptr,
+                                    int rule = kRuleGo);
 
 // Latency mode of the generic path (latency.hip; n <= kGLatMax): decode / hash roles, then
 // 8 lanes per signature (two quads, 4-way point formulas).  hand: kGLatHandBytes of scratch.

@@ -1157,14 +1157,19 @@ __global__ __launch_bounds__(kThreadsPerBlock) void verify_lat_finish_kernel(con
 hipError_t launch_verify_keyset_lat(const uint32_t *val_idx, uint32_t nkeys, const uint8_t *key_pub, const uint8_t *key_ok,
                                     const int4 *const *acomb, const int4 *bcomb, const uint8_t *sig, const uint8_t *msgs,
                                     const uint32_t *off, uint32_t n, uint8_t *out, int4 *fin, int4 *dec,
-                                    hipStream_t stream, bool msg_slots, const VoteAsm *va) {
+                                    hipStream_t stream, bool msg_slots, const VoteAsm *va, int rule) {
   if (n == 0) return hipSuccess;
   if (n > kLatMax) return hipErrorInvalidValue;  // fin / dec are sized for kLatMax signatures
   if (va && !msg_slots) return hipErrorInvalidValue;
   const MsgSrc ms{msgs, off, msg_slots};
+  static_assert(kLatDecInt4 == kLatDecRows, "dec layout shared with zip_finish.hip");
   const uint32_t nR = (n + 63) / 64, nC = (n + 64 / kLatLanes - 1) / (64 / kLatLanes);
   hipLaunchKernelGGL(verify_keyset_lat_kernel, dim3(nR + nC), dim3(64), 0, stream, val_idx, nkeys, key_pub, key_ok, acomb,
                      bcomb, sig, ms, n, nR, fin, dec, out, va ? *va : VoteAsm{}, va ? 1 : 0);
+  if (rule == kRuleZip215) {  // R from the R blocks' decode where it is canonical: zip_finish.hip
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : launch_lat_finish_zip(fin, dec, sig, out, n, stream);
+  }
   hipLaunchKernelGGL(verify_lat_finish_kernel, dim3((n + kThreadsPerBlock - 1) / kThreadsPerBlock),
                      dim3(kThreadsPerBlock), 0, stream, fin, dec, n, out);
   return hipGetLastError();
@@ -1175,7 +1180,7 @@ hipError_t launch_verify_keyset(const uint32_t *val_idx, uint32_t nkeys, const u
                                 const uint32_t *off, uint32_t n, uint8_t *out, int4 *prep, uint32_t stride,
                                 int4 *fin, int4 *fin_pre, hipStream_t stream, bool msg_slots, KernelTimer *timer,
                                 uint32_t *perm, uint32_t *order_scratch, const int4 *bcomb24,
-                                const int4 *const *acomba) {
+                                const int4 *const *acomba, int rule) {
   const MsgSrc ms{msgs, off, msg_slots};
   if (stride > kFinCap) stride = kFinCap;
   if (timer) timer->mark(stream, -1);
@@ -1204,7 +1209,8 @@ hipError_t launch_verify_keyset(const uint32_t *val_idx, uint32_t nkeys, const u
       hipError_t e = hipGetLastError();
       if (e != hipSuccess) return e;
     }
-    hipError_t e = launch_finish(fin, fin_pre, sig, out, fbase, m, stream, perm);
+    hipError_t e = rule == kRuleZip215 ? launch_finish_zip(fin, sig, out, fbase, m, stream, perm)
+                                       : launch_finish(fin, fin_pre, sig, out, fbase, m, stream, perm);
     if (timer) timer->mark(stream, 2);
     if (e != hipSuccess) return e;
   }

@@ -275,11 +275,12 @@ int keyset_append(tmed_ctx *c, Keyset &k, const uint8_t *pubkeys, size_t m, hipS
 // commit), the throughput kernels (prep / comb main / batched finish) above c->lat_max.
 static hipError_t keyset_verify(tmed_ctx *c, Keyset &k, const uint32_t *d_idx, const uint8_t *d_sig,
                                 const uint8_t *d_msgs, const uint32_t *d_off, uint32_t n, uint8_t *d_out,
-                                hipStream_t s, bool msg_slots, const VoteAsm *va = nullptr, Lane *lane = nullptr) {
+                                hipStream_t s, bool msg_slots, int rule, const VoteAsm *va = nullptr,
+                                Lane *lane = nullptr) {
   c->last_hs_count = 0;  // d_prep now holds another path's hand-off (tmed_window_stats)
   if (n <= c->lat_max)
     return launch_verify_keyset_lat(d_idx, (uint32_t)k.n, k.d_pub, k.d_ok, k.comb_tab(), c->d_bcomb, d_sig, d_msgs, d_off, n, d_out,
-                                    c->d_fin, c->d_fin_pre, s, msg_slots, va);
+                                    c->d_fin, c->d_fin_pre, s, msg_slots, va, rule);
   if (va) return hipErrorInvalidValue;
   if (c->d_b24) comba_extend(c, k, s);
   const int4 *const *comba = c->d_b24 && !k.comba.empty() && k.comba_n == k.n ? k.comba_tab() : nullptr;
@@ -297,12 +298,12 @@ static hipError_t keyset_verify(tmed_ctx *c, Keyset &k, const uint32_t *d_idx, c
   return launch_verify_keyset(d_idx, (uint32_t)k.n, k.d_pub, k.d_ok, k.comb_tab(), c->d_bcomb16, d_sig, d_msgs, d_off, n,
                               d_out, lane ? lane->d_prep : c->d_prep, c->slab_slots, lane ? lane->d_fin : c->d_fin,
                               lane ? lane->d_fin_pre : c->d_fin_pre, s, msg_slots, timer, perm, scratch, c->d_b24,
-                              comba);
+                              comba, rule);
 }
 
 hipError_t keyset_verify_batch(tmed_ctx *c, Keyset &k, const uint32_t *d_idx, const uint8_t *d_sig, const uint8_t *d_msgs,
-                               const uint32_t *d_off, uint32_t n, uint8_t *d_out, hipStream_t s, bool msg_slots) {
-  return keyset_verify(c, k, d_idx, d_sig, d_msgs, d_off, n, d_out, s, msg_slots);
+                               const uint32_t *d_off, uint32_t n, uint8_t *d_out, hipStream_t s, bool msg_slots, int rule) {
+  return keyset_verify(c, k, d_idx, d_sig, d_msgs, d_off, n, d_out, s, msg_slots, rule);
 }
 
 static std::atomic<uint32_t> g_test_stream_delay{0};
@@ -505,7 +506,7 @@ int votes_enqueue(tmed_ctx *c, VoteStage &st) {
   // launch in front)
   const VoteAsm va{d + st.o_tmpl, (const uint32_t *)(d + st.o_tidx), d + st.o_flag, (const int64_t *)(d + st.o_sec),
                    (const int32_t *)(d + st.o_nan)};
-  const bool fused = st.ks ? m <= c->lat_max : generic_uses_glat(c, m);
+  const bool fused = st.ks ? m <= c->lat_max : generic_uses_glat(c, m, st.rule);
   if (e == hipSuccess && !fused)
     e = launch_assemble_votes(va.tmpl, va.tmpl_idx, va.flags, va.ts_sec, va.ts_nanos, m, (uint8_t *)vs.d_vmsg.p,
                               (uint32_t *)vs.d_off.p, s);
@@ -513,10 +514,10 @@ int votes_enqueue(tmed_ctx *c, VoteStage &st) {
   if (e == hipSuccess) {
     if (st.ks)
       e = keyset_verify(c, *st.ks, (const uint32_t *)(d + st.o_key), d + st.o_sig, (const uint8_t *)vs.d_vmsg.p,
-                        (const uint32_t *)vs.d_off.p, m, out_dev, s, /*msg_slots=*/true, fused ? &va : nullptr, lane);
+                        (const uint32_t *)vs.d_off.p, m, out_dev, s, /*msg_slots=*/true, st.rule, fused ? &va : nullptr, lane);
     else
       e = generic_verify(c, d + st.o_key, d + st.o_sig, (const uint8_t *)vs.d_vmsg.p, (const uint32_t *)vs.d_off.p, m,
-                         out_dev, s, /*msg_slots=*/true, nullptr, fused ? &va : nullptr);
+                         out_dev, s, /*msg_slots=*/true, nullptr, fused ? &va : nullptr, st.rule);
   }
   slow.lap("verify launches");
   if (e == hipSuccess && st.timed) e = hipEventRecord(vs.ev1, s);
@@ -621,9 +622,12 @@ int tmed_keyset_free(tmed_ctx *c, uint64_t handle) {
   return TMED_OK;
 }
 
-int tmed_verify_batch_keyset_device(tmed_ctx *c, uint64_t handle, const uint32_t *d_val_idx, const uint8_t *d_sigs,
-                                    const uint8_t *d_msgs, const uint32_t *d_msg_off, size_t n, uint8_t *d_out,
-                                    void *stream) {
+}  // extern "C"
+
+namespace tmed {
+static int verify_batch_keyset_device_rule(tmed_ctx *c, uint64_t handle, const uint32_t *d_val_idx, const uint8_t *d_sigs,
+                                           const uint8_t *d_msgs, const uint32_t *d_msg_off, size_t n, uint8_t *d_out,
+                                           void *stream, int rule) {
   if (!c) return TMED_EINVAL;
   if (n == 0) return TMED_OK;
   if (!d_val_idx || !d_sigs || !d_msgs || !d_msg_off || !d_out || n > 0xffffffffu) return TMED_EINVAL;
@@ -637,14 +641,14 @@ int tmed_verify_batch_keyset_device(tmed_ctx *c, uint64_t handle, const uint32_t
   // (one lane: split over both kernel lanes in halves, a 2^20 batch ran 3 % slower — the halves'
   // key orders spread each kernel's comb reads — profiles/r04/s10/ab_keyed_lanes.jsonl)
   hipError_t e = scratch_acquire(c, s);
-  if (e == hipSuccess) e = keyset_verify(c, k, d_val_idx, d_sigs, d_msgs, d_msg_off, (uint32_t)n, d_out, s, false);
+  if (e == hipSuccess) e = keyset_verify(c, k, d_val_idx, d_sigs, d_msgs, d_msg_off, (uint32_t)n, d_out, s, false, rule);
   if (e == hipSuccess) e = scratch_release(c, s);
   return map_err(e);
 }
 
-int tmed_verify_batch_keyset(tmed_ctx *c, uint64_t handle, const uint32_t *val_idx, const uint8_t *sigs,
-                             const uint32_t *sig_lens, const uint8_t *msgs, const uint32_t *off, size_t n,
-                             uint8_t *out) {
+int verify_batch_keyset_rule(tmed_ctx *c, uint64_t handle, const uint32_t *val_idx, const uint8_t *sigs,
+                             const uint32_t *sig_lens, const uint8_t *msgs, const uint32_t *off, size_t n, uint8_t *out,
+                             int rule) {
   int rc = check_raw_batch(c, val_idx, sigs, msgs, off, n, out);
   if (rc != TMED_OK || n == 0) return rc;
   const size_t mbytes = off[n];
@@ -665,11 +669,41 @@ int tmed_verify_batch_keyset(tmed_ctx *c, uint64_t handle, const uint32_t *val_i
   rc = raw_run(c, st, /*timed=*/true,
                [&](const uint8_t *d_idx, const uint8_t *d_sig, const uint8_t *d_msg, const uint32_t *d_off, uint32_t m,
                    uint8_t *d_out, hipStream_t s) {
-                 return map_err(keyset_verify(c, k, (const uint32_t *)d_idx, d_sig, d_msg, d_off, m, d_out, s, false));
+                 return map_err(keyset_verify(c, k, (const uint32_t *)d_idx, d_sig, d_msg, d_off, m, d_out, s, false, rule));
                },
                out, sig_lens);
   if (rc == TMED_OK) c->last_ms = st.ms;
   return rc;
+}
+}  // namespace tmed
+
+extern "C" {
+
+// The raw keyed batches keep the rule their name states, whatever the context's seam rule is.
+int tmed_verify_batch_keyset_device(tmed_ctx *c, uint64_t handle, const uint32_t *d_val_idx, const uint8_t *d_sigs,
+                                    const uint8_t *d_msgs, const uint32_t *d_msg_off, size_t n, uint8_t *d_out,
+                                    void *stream) {
+  return tmed::verify_batch_keyset_device_rule(c, handle, d_val_idx, d_sigs, d_msgs, d_msg_off, n, d_out, stream,
+                                               TMED_RULE_GO);
+}
+
+int tmed_verify_batch_keyset_zip215_device(tmed_ctx *c, uint64_t handle, const uint32_t *d_val_idx,
+                                           const uint8_t *d_sigs, const uint8_t *d_msgs, const uint32_t *d_msg_off,
+                                           size_t n, uint8_t *d_out, void *stream) {
+  return tmed::verify_batch_keyset_device_rule(c, handle, d_val_idx, d_sigs, d_msgs, d_msg_off, n, d_out, stream,
+                                               TMED_RULE_ZIP215);
+}
+
+int tmed_verify_batch_keyset(tmed_ctx *c, uint64_t handle, const uint32_t *val_idx, const uint8_t *sigs,
+                             const uint32_t *sig_lens, const uint8_t *msgs, const uint32_t *off, size_t n,
+                             uint8_t *out) {
+  return tmed::verify_batch_keyset_rule(c, handle, val_idx, sigs, sig_lens, msgs, off, n, out, TMED_RULE_GO);
+}
+
+int tmed_verify_batch_keyset_zip215(tmed_ctx *c, uint64_t handle, const uint32_t *val_idx, const uint8_t *sigs,
+                                    const uint32_t *sig_lens, const uint8_t *msgs, const uint32_t *off, size_t n,
+                                    uint8_t *out) {
+  return tmed::verify_batch_keyset_rule(c, handle, val_idx, sigs, sig_lens, msgs, off, n, out, TMED_RULE_ZIP215);
 }
 
 }  // extern "C"

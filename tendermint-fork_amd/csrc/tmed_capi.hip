@@ -300,6 +300,19 @@ int tmed_set_kernel_timing(tmed_ctx *c, int on) {
   return TMED_OK;
 }
 
+int tmed_set_rule(tmed_ctx *c, int rule) {
+  if (!c || (rule != TMED_RULE_GO && rule != TMED_RULE_ZIP215)) return TMED_EINVAL;
+  // a seam call: the submitted blocksync windows are collected first, under the rule they were queued with
+  return guarded([&] {
+    return locked(c, /*collect=*/true, [&] {
+      c->rule.store(rule, std::memory_order_relaxed);
+      return (int)TMED_OK;
+    });
+  });
+}
+
+int tmed_rule(const tmed_ctx *c) { return c ? c->rule.load(std::memory_order_relaxed) : TMED_EINVAL; }
+
 int tmed_kernel_times(tmed_ctx *c, float ms[3], int launches[3]) {
   if (!c || !ms || !launches || !c->timing) return TMED_EINVAL;
   for (int k = 0; k < 3; k++) { ms[k] = 0.f; launches[k] = 0; }
@@ -579,8 +592,9 @@ int tmed_test_key_order(tmed_ctx *c, const uint32_t *val_idx, uint32_t n, uint32
   });
 }
 
-int tmed_test_finish(tmed_ctx *c, uint32_t m, const int32_t *xyz, const uint8_t *r, const uint32_t *perm,
-                     uint32_t fin_base, const uint8_t *bits_in, uint8_t *bits_out) {
+// tmed_test_finish / tmed_test_finish_zip215: the same staging in front of either finish launcher.
+static int test_finish_run(tmed_ctx *c, uint32_t m, const int32_t *xyz, const uint8_t *r, const uint32_t *perm,
+                           uint32_t fin_base, const uint8_t *bits_in, uint8_t *bits_out, int rule) {
   if (!c || !xyz || !r || !bits_in || !bits_out) return TMED_EINVAL;
   if (m == 0 || m > kFinCap || fin_base > 2 * kFinCap - m) return TMED_EINVAL;
   const size_t rows = (size_t)fin_base + m;  // signature rows and out bytes the call allocates
@@ -611,7 +625,9 @@ int tmed_test_finish(tmed_ctx *c, uint32_t m, const int32_t *xyz, const uint8_t 
       const uint32_t *dp = perm ? (const uint32_t *)d_perm : nullptr;
       if (e == hipSuccess)
         e = launch_test_fin_fill((const int32_t *)d, d_r, d_bits, dp, fin_base, m, c->d_fin, d_sig, d_out, s);
-      if (e == hipSuccess) e = launch_finish(c->d_fin, c->d_fin_pre, d_sig, d_out, fin_base, m, s, dp);
+      if (e == hipSuccess)
+        e = rule == kRuleZip215 ? launch_finish_zip(c->d_fin, d_sig, d_out, fin_base, m, s, dp)
+                                : launch_finish(c->d_fin, c->d_fin_pre, d_sig, d_out, fin_base, m, s, dp);
       if (acquired) {
         const hipError_t er = scratch_release(c, s);
         if (e == hipSuccess) e = er;
@@ -622,6 +638,16 @@ int tmed_test_finish(tmed_ctx *c, uint32_t m, const int32_t *xyz, const uint8_t 
       return rc;
     });
   });
+}
+
+int tmed_test_finish(tmed_ctx *c, uint32_t m, const int32_t *xyz, const uint8_t *r, const uint32_t *perm,
+                     uint32_t fin_base, const uint8_t *bits_in, uint8_t *bits_out) {
+  return test_finish_run(c, m, xyz, r, perm, fin_base, bits_in, bits_out, kRuleGo);
+}
+
+int tmed_test_finish_zip215(tmed_ctx *c, uint32_t m, const int32_t *xyz, const uint8_t *r, const uint32_t *perm,
+                            uint32_t fin_base, const uint8_t *bits_in, uint8_t *bits_out) {
+  return test_finish_run(c, m, xyz, r, perm, fin_base, bits_in, bits_out, kRuleZip215);
 }
 
 int tmed_sign_batch_device(tmed_ctx *c, const uint8_t *d_seeds, const uint8_t *d_msgs, const uint32_t *d_off,
@@ -636,6 +662,15 @@ int tmed_sign_batch_device(tmed_ctx *c, const uint8_t *d_seeds, const uint8_t *d
 
 int tmed_verify_batch(tmed_ctx *c, const uint8_t *pub, const uint8_t *sig, const uint32_t *sig_lens,
                       const uint8_t *msgs, const uint32_t *off, size_t n, uint8_t *out) {
+  return tmed::verify_batch_rule(c, pub, sig, sig_lens, msgs, off, n, out, TMED_RULE_GO);
+}
+
+}  // extern "C"
+
+namespace tmed {
+// tmed_verify_batch, and the seam's host-message route under its call's rule (ctx.h).
+int verify_batch_rule(tmed_ctx *c, const uint8_t *pub, const uint8_t *sig, const uint32_t *sig_lens,
+                      const uint8_t *msgs, const uint32_t *off, size_t n, uint8_t *out, int rule) {
   int rc = check_raw_batch(c, pub, sig, msgs, off, n, out);
   if (rc != TMED_OK || n == 0) return rc;
   const size_t mbytes = off[n];
@@ -653,12 +688,15 @@ int tmed_verify_batch(tmed_ctx *c, const uint8_t *pub, const uint8_t *sig, const
   rc = raw_run(c, st, timed,
                [&](const uint8_t *d_pub, const uint8_t *d_sig, const uint8_t *d_msg, const uint32_t *d_off, uint32_t m,
                    uint8_t *d_out, hipStream_t s) {
-                 return map_err(generic_verify(c, d_pub, d_sig, d_msg, d_off, m, d_out, s, false, nullptr));
+                 return map_err(generic_verify(c, d_pub, d_sig, d_msg, d_off, m, d_out, s, false, nullptr, nullptr, rule));
                },
                out, sig_lens);
   if (rc == TMED_OK) c->last_ms = st.ms;
   return rc;
 }
+}  // namespace tmed
+
+extern "C" {
 
 int tmed_sign_batch(tmed_ctx *c, const uint8_t *seeds, const uint8_t *msgs, const uint32_t *off, size_t n,
                     uint8_t *sigs_out, uint8_t *pubs_out) {

@@ -115,6 +115,7 @@ void vote_sig(const tmed_votes &v, size_t i, uint8_t *out) {
 // msg_slots mode, codes and validity bits out.
 int run_group_device(tmed_ctx *c, const tmed_vote_request *reqs, const size_t *base, const VoteGroup &g, Keyset *ks,
                      uint8_t *codes) {
+  const int rule = seam_rule(c);  // ctx->mu is held from the call's entry: one value for all its groups
   const size_t m = g.m, G = g.reqs.size();
   // each distinct set's addresses once (ADDVOTE requests only)
   std::unordered_map<const tmed_valset *, uint64_t> abase;
@@ -181,9 +182,9 @@ int run_group_device(tmed_ctx *c, const tmed_vote_request *reqs, const size_t *b
   if (e == hipSuccess) {
     const uint32_t *lens = reinterpret_cast<const uint32_t *>(d + o_len);
     e = ks ? keyset_verify_batch(c, *ks, reinterpret_cast<const uint32_t *>(d + o_key), d + o_sig, d + o_slot, lens,
-                                 (uint32_t)m, d + o_valid, s, /*msg_slots=*/true)
+                                 (uint32_t)m, d + o_valid, s, /*msg_slots=*/true, rule)
            : generic_verify(c, d + o_key, d + o_sig, d + o_slot, lens, (uint32_t)m, d + o_valid, s, /*msg_slots=*/true,
-                            nullptr);
+                            nullptr, nullptr, rule);
   }
   if (e == hipSuccess) e = hipEventRecord(c->ev1, s);
   if (acquired) {
@@ -214,6 +215,7 @@ int run_group_device(tmed_ctx *c, const tmed_vote_request *reqs, const size_t *b
 // the messages packed behind each other, the verify launchers in their offset mode.
 int run_group_host(tmed_ctx *c, const tmed_vote_request *reqs, const size_t *base, const VoteGroup &g, Keyset *ks,
                    uint8_t *codes) {
+  const int rule = seam_rule(c);  // ctx->mu is held from the call's entry: one value for all its groups
   const size_t m = g.m;
   std::vector<uint8_t> pre(m), valid(m), msgs;
   std::vector<uint32_t> off(m + 1);
@@ -255,8 +257,9 @@ int run_group_host(tmed_ctx *c, const tmed_vote_request *reqs, const size_t *bas
                [&](const uint8_t *d_key, const uint8_t *d_sig, const uint8_t *d_msg, const uint32_t *d_off, uint32_t n,
                    uint8_t *d_out, hipStream_t s) {
                  return map_err(ks ? keyset_verify_batch(c, *ks, (const uint32_t *)d_key, d_sig, d_msg, d_off, n, d_out, s,
-                                                         /*msg_slots=*/false)
-                                   : generic_verify(c, d_key, d_sig, d_msg, d_off, n, d_out, s, /*msg_slots=*/false, nullptr));
+                                                         /*msg_slots=*/false, rule)
+                                   : generic_verify(c, d_key, d_sig, d_msg, d_off, n, d_out, s, /*msg_slots=*/false, nullptr,
+                                                    nullptr, rule));
                },
                valid.data(), nullptr);
   if (rc != TMED_OK) return rc;

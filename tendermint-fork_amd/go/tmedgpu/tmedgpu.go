@@ -1182,6 +1182,53 @@ func (e *Engine) batch(pubKeys []byte, msgs, sigs [][]byte, zip215 bool) ([]bool
 	return ok, nil
 }
 
+// The signature rules of an engine's seam calls (tmed_set_rule).
+const (
+	RuleGo     = 0 // Go 1.18 crypto/ed25519.Verify: the default
+	RuleZIP215 = 1 // ZIP-215: permissive decoding of A and R, [8]([S]B - R - [k]A) = O
+)
+
+// SetRule sets the signature rule of the engine's seam calls: VerifyCommits, the Blocksync calls,
+// LightVerify, VerifyVotes (tmed_set_rule).  A chain on a release that verifies with ZIP-215 calls
+// it once after creating the engine.  Only the signature decision changes; the loops, prechecks
+// and error values stay v0.34.24's.  VerifyBatch keeps the Go rule whatever is set here.
+func (e *Engine) SetRule(rule int) error {
+	if rc := C.tmed_set_rule(e.ctx, C.int(rule)); rc != 0 {
+		return errors.New(C.GoString(C.tmed_strerror(rc)))
+	}
+	return nil
+}
+
+// Rule returns the engine's signature rule (tmed_rule).
+func (e *Engine) Rule() int { return int(C.tmed_rule(e.ctx)) }
+
+// VerifyBatchKeysetZIP215 returns the ZIP-215 decision of every (key index, message, signature)
+// tuple against a loaded key set (tmed_verify_batch_keyset_zip215): exact per signature, no random
+// weights.  A shim for a release whose VerifyCommit loops differ from 0.34's replays its own loop
+// over these bits.
+func (e *Engine) VerifyBatchKeysetZIP215(h uint64, valIdx []uint32, msgs, sigs [][]byte) ([]bool, error) {
+	n := len(msgs)
+	if len(sigs) != n || len(valIdx) != n {
+		return nil, errors.New("tmedgpu: want one key index and one signature per message")
+	}
+	if n == 0 {
+		return nil, nil
+	}
+	a := e.getArena()
+	defer e.putArena(a)
+	_, sg, sl, mg, mo := batchArgs(a, nil, msgs, sigs)
+	out := (*[1 << 28]C.uint8_t)(a.alloc(uintptr(n)))[:n:n]
+	rc := C.tmed_verify_batch_keyset_zip215(e.ctx, C.uint64_t(h), a.u32(valIdx), sg, sl, mg, mo, C.size_t(n), &out[0])
+	if rc != 0 {
+		return nil, errors.New(C.GoString(C.tmed_strerror(rc)))
+	}
+	ok := make([]bool, n)
+	for i := range ok {
+		ok[i] = out[i] != 0
+	}
+	return ok, nil
+}
+
 // Pool is one engine per GPU of the node, used from ONE process (a Tendermint node):
 // tmed_verify_commits_multi / tmed_blocksync_verify_multi shard the work over the contexts
 // concurrently; no collective is needed since host memory is shared.

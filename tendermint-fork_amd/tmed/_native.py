@@ -83,6 +83,14 @@ def lib() -> ctypes.CDLL:
     l.tmed_verify_batch_keyset.argtypes = [P, ctypes.c_uint64, P, P, P, P, P, SZ, P]
     l.tmed_verify_batch_keyset_device.restype = I
     l.tmed_verify_batch_keyset_device.argtypes = [P, ctypes.c_uint64, P, P, P, P, SZ, P, P]
+    l.tmed_verify_batch_keyset_zip215.restype = I
+    l.tmed_verify_batch_keyset_zip215.argtypes = [P, ctypes.c_uint64, P, P, P, P, P, SZ, P]
+    l.tmed_verify_batch_keyset_zip215_device.restype = I
+    l.tmed_verify_batch_keyset_zip215_device.argtypes = [P, ctypes.c_uint64, P, P, P, P, SZ, P, P]
+    l.tmed_set_rule.restype = I
+    l.tmed_set_rule.argtypes = [P, I]
+    l.tmed_rule.restype = I
+    l.tmed_rule.argtypes = [P]
     l.tmed_set_kernel_timing.restype = I
     l.tmed_set_kernel_timing.argtypes = [P, I]
     l.tmed_kernel_times.restype = I
@@ -131,6 +139,8 @@ def lib() -> ctypes.CDLL:
                                       ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
     l.tmed_test_finish.restype = I
     l.tmed_test_finish.argtypes = [P, ctypes.c_uint32, P, P, P, ctypes.c_uint32, P, P]
+    l.tmed_test_finish_zip215.restype = I
+    l.tmed_test_finish_zip215.argtypes = [P, ctypes.c_uint32, P, P, P, ctypes.c_uint32, P, P]
     l.tmed_debug_zero_bits.restype = I
     l.tmed_debug_zero_bits.argtypes = [P, SZ, ctypes.POINTER(SZ)]
     _lib = l
@@ -145,7 +155,8 @@ EXPORTED_SYMBOLS = [
     "tmed_vote_sign_bytes", "tmed_valu_peak", "tmed_verify_commits", "tmed_verify_commits_with",
     "tmed_test_pool_jitter", "tmed_test_stream_delay", "tmed_test_joint_rows", "tmed_debug_zero_bits",
     "tmed_test_b_table_entry", "tmed_test_table_chain", "tmed_test_zip_msm",
-    "tmed_test_key_order", "tmed_test_finish",
+    "tmed_test_key_order", "tmed_test_finish", "tmed_test_finish_zip215",
+    "tmed_set_rule", "tmed_rule", "tmed_verify_batch_keyset_zip215", "tmed_verify_batch_keyset_zip215_device",
     "tmed_keyset_load", "tmed_keyset_free", "tmed_keyset_extend", "tmed_verify_batch_keyset",
     "tmed_keycache_config", "tmed_keycache_stats", "tmed_keycache_flush", "tmed_keycache_warm", "tmed_keycache_wait", "tmed_verify_batch_keyset_device",
     "tmed_set_kernel_timing", "tmed_kernel_times", "tmed_blocksync_verify", "tmed_blocksync_submit", "tmed_blocksync_wait",

@@ -270,6 +270,45 @@ class Engine:
         if rc != TMED_OK:
             raise TmedError(rc, "tmed_verify_batch_keyset_device")
 
+    def verify_batch_keyset_zip215(self, handle: int, val_idx: np.ndarray, sigs: np.ndarray, msgs: np.ndarray,
+                                   offs: np.ndarray, sig_lens: np.ndarray | None = None) -> np.ndarray:
+        """The ZIP-215 rule by key index (tmed_verify_batch_keyset_zip215): the key-cached kernels and
+        the exact per-signature finish [8](P - R) == O; the contract of verify_keyset_arrays otherwise."""
+        n = val_idx.shape[0]
+        out = np.zeros(n, dtype=np.uint8)
+        if n == 0:
+            return out
+        vi = np.ascontiguousarray(val_idx, dtype=np.uint32)
+        sigs = np.ascontiguousarray(sigs, dtype=np.uint8).reshape(n, 64)
+        msgs = np.ascontiguousarray(msgs, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint32)
+        sl = None if sig_lens is None else np.ascontiguousarray(sig_lens, dtype=np.uint32)
+        rc = lib().tmed_verify_batch_keyset_zip215(self._h, handle, _p(vi), _p(sigs), None if sl is None else _p(sl),
+                                                   _p(msgs), _p(offs), n, _p(out))
+        if rc != TMED_OK:
+            raise TmedError(rc, "tmed_verify_batch_keyset_zip215")
+        return out
+
+    def verify_batch_keyset_zip215_device(self, handle: int, d_val_idx, d_sig, d_msg, d_off, d_out, n: int,
+                                          stream=None) -> None:
+        s = ctypes.c_void_p(stream) if stream else None
+        rc = lib().tmed_verify_batch_keyset_zip215_device(self._h, handle, d_val_idx.data_ptr(), d_sig.data_ptr(),
+                                                          d_msg.data_ptr(), d_off.data_ptr(), n, d_out.data_ptr(), s)
+        if rc != TMED_OK:
+            raise TmedError(rc, "tmed_verify_batch_keyset_zip215_device")
+
+    RULE_GO, RULE_ZIP215 = 0, 1
+
+    def set_rule(self, rule: int) -> None:
+        """The signature rule of this context's seam calls (tmed_set_rule): RULE_GO, the default, or
+        RULE_ZIP215.  Only the signature decision changes; the loops stay v0.34.24's."""
+        rc = lib().tmed_set_rule(self._h, int(rule))
+        if rc != TMED_OK:
+            raise TmedError(rc, "tmed_set_rule")
+
+    def rule(self) -> int:
+        return int(lib().tmed_rule(self._h))
+
     def set_kernel_timing(self, on: bool) -> None:
         rc = lib().tmed_set_kernel_timing(self._h, 1 if on else 0)
         if rc != TMED_OK:
@@ -384,6 +423,24 @@ class Engine:
                                     _p(bits_in), _p(out))
         if rc != 0:
             raise TmedError(rc, "tmed_test_finish")
+        return out
+
+    def finish_zip215(self, xyz: np.ndarray, r: np.ndarray, bits_in: np.ndarray, fin_base: int = 0, perm=None) -> np.ndarray:
+        """Tests: the ZIP-215 finish of m projective points a caller gives (tmed_test_finish_zip215);
+        the arguments and the result of finish()."""
+        m = bits_in.shape[0]
+        xyz = np.ascontiguousarray(xyz, dtype=np.int32).reshape(m, 30)
+        r = np.ascontiguousarray(r, dtype=np.uint8).reshape(m, 32)
+        bits_in = np.ascontiguousarray(bits_in, dtype=np.uint8)
+        if perm is not None:
+            perm = np.ascontiguousarray(perm, dtype=np.uint32)
+            if perm.shape[0] != fin_base + m:
+                raise ValueError("perm must hold fin_base + m entries")
+        out = np.zeros(fin_base + m, np.uint8)
+        rc = lib().tmed_test_finish_zip215(self._h, m, _p(xyz), _p(r), None if perm is None else _p(perm), fin_base,
+                                           _p(bits_in), _p(out))
+        if rc != 0:
+            raise TmedError(rc, "tmed_test_finish_zip215")
         return out
 
     def last_kernel_ms(self) -> float:
