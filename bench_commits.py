@@ -25,6 +25,14 @@
                 Vote.Verify on the device), beside the route there was before (the sign-bytes of every vote
                 on the host, then tmed_verify_batch_keyset) and oracle.port on one thread, in one run:
                 votes/s, vote_prepare_kernel's device time, the call's host share.
+  --config evidence  duplicate-vote evidence: one block at the byte cap (2,048 evidences against a 10,000-
+                validator set) and 1,000 lists x 4 evidences against 175 validators (--evidence-shapes) through
+                tmed_verify_duplicate_votes (VerifyDuplicateVote on the device: the address lookup, the checks,
+                both signatures) plus tmed_evidence_hashes (every DuplicateVoteEvidence.Hash and EvidenceList.Hash),
+                beside the route there was before (tmed_verify_duplicate_votes_host's checks on the host, then
+                tmed_verify_votes over the 2n votes; tmed_evidence_bytes, then tmed_merkle_roots), in one run, once
+                both routes agree on every code and root: evidences/s, the lookup, prepare and leaf-stage kernels'
+                device time, the calls' host share.
 Synthetic data (seeded keys, GPU RFC 8032 signer); prints one JSON line per config.
 """
 from __future__ import annotations
@@ -1165,6 +1173,136 @@ def votes(eng, runs: int, cpu: bool, shapes=(10_000, 175)):
             "tmed_verify_batch_keyset vs oracle.port on one thread", "runs": runs, "shapes": out}
 
 
+def _evidence_shape(text: str):
+    """'NxV': one list of N evidences against V validators; 'LxKxV': L lists of K evidences each."""
+    p = [int(x) for x in text.split("x")]
+    if len(p) == 2:
+        return 1, p[0], p[1]
+    if len(p) == 3:
+        return p[0], p[1], p[2]
+    raise ValueError("--evidence-shapes: NxV or LxKxV")
+
+
+def evidence(eng, runs: int, shapes=("2048x10000", "1000x4x175")):
+    """Duplicate-vote evidence per shape: L lists of K evidences (n = L x K) against a V-validator set held as
+    an explicit key set (the key-cached kernels on both routes), evidence i by validator (4877 i) mod V.
+      new   one tmed_verify_duplicate_votes call over the n evidences, one tmed_evidence_hashes call over
+            the L lists;
+      old   tmed_verify_duplicate_votes_host (GetByAddress as a scan per evidence and the checks, on one host
+            thread), one tmed_verify_votes call over the 2n votes with the key of the found validator, the
+            codes put together as the reference orders them; tmed_evidence_bytes, then tmed_merkle_roots.
+    Every 97th evidence carries a flipped byte in VoteB's signature, every 101st a wrong validator power; both
+    routes must agree on every code and every root before anything is timed.  Medians of `runs` timed calls."""
+    import tmed.evidence as EV
+    import tmed.merkle as MK
+    import tmed.votes as V
+    from tmed import pack_messages
+    from tmed.workload import make_valset, pubkeys_of, seeds_from_tag
+    med = lambda xs: float(np.median(xs))
+    chain, height, rnd = "test_chain_id", 1_000_000, 1
+    out = []
+    for text in shapes:
+        L, K, nvals = _evidence_shape(text)
+        n = L * K
+        seeds = seeds_from_tag(b"tmed-evidence-key", 0, nvals)
+        vals, order = make_valset(pubkeys_of(eng, seeds), [10] * nvals)
+        vpubs, _, vaddrs = vals.packed()
+        handle = eng.keyset_load(vpubs[:nvals])
+        vals.keyset = handle
+        who = (np.arange(n) * 4877) % nvals          # evidence -> validator
+        vwho = np.repeat(who, 2)                      # vote -> validator
+        bids = [block_id(b"evidence-a-%d" % nvals), block_id(b"evidence-b-%d" % nvals)]
+        side = np.tile(np.arange(2), n)               # vote -> 0 (VoteA) / 1 (VoteB)
+        hashes = np.stack([np.frombuffer(b.hash, np.uint8) for b in bids])[side]
+        pshs = np.stack([np.frombuffer(b.psh_hash, np.uint8) for b in bids])[side]
+        vidx = np.arange(2 * n)
+        pv = V.PackedVotes.from_arrays(
+            types=np.full(2 * n, 1), heights=np.full(2 * n, height), rounds=np.full(2 * n, rnd), block_hashes=hashes,
+            block_hash_lens=np.full(2 * n, 32), psh_totals=np.full(2 * n, 123), psh_hashes=pshs,
+            psh_hash_lens=np.full(2 * n, 32), ts_seconds=T2023 + vidx // 1000, ts_nanos=(vidx % 1000) * 1_000_000,
+            addresses=vaddrs[vwho], address_lens=np.full(2 * n, 20), validator_indexes=vwho,
+            sigs=np.zeros((2 * n, 64), np.uint8), sig_lens=np.full(2 * n, 64))
+        flat, off = pack_messages(V.sign_bytes(chain, pv))
+        sigs, _ = eng.sign_arrays(seeds[order][vwho], np.concatenate([flat, np.zeros(16, np.uint8)]), off)
+        pv.sigs[:] = sigs
+        pv.sigs[1::2][::97, 5] ^= 1
+        powers = np.full(n, 10, np.int64)
+        powers[::101] = 11
+        pe = EV.PackedEvidence.from_arrays(pv, np.full(n, vals.total_voting_power()), powers, T2023 + np.arange(n) // 7,
+                                           np.arange(n) % 1000)
+        want = np.zeros(n, np.uint8)
+        want[::97] = EV.DUPVOTE_VOTE_B_SIGNATURE
+        want[::101] = EV.DUPVOTE_VALIDATOR_POWER
+        items, list_off = np.arange(n, dtype=np.int64), (np.arange(L + 1) * K).astype(np.uint32)
+        prep = EV.PreparedEvidence([EV.EvidenceRequest(chain, vals, pe)])
+
+        def new_route():
+            t0 = time.perf_counter()
+            codes = prep.run(eng)
+            t1 = time.perf_counter()
+            k_all, (k_look, k_prep) = eng.last_kernel_ms(), EV.last_kernel_times(eng)
+            evh, roots, ev_ok, list_ok = EV.evidence_hashes_packed(eng, pe, items, list_off)
+            t2 = time.perf_counter()
+            return codes.copy(), evh, roots, (t1 - t0, t2 - t1, k_look, k_prep, k_all - k_look - k_prep, eng.last_kernel_ms())
+
+        def old_route():
+            t0 = time.perf_counter()
+            pre = prep.run(None).copy()
+            found = np.repeat(np.maximum(prep.found[:n], 0), 2).astype(np.int32)
+            t1 = time.perf_counter()
+            pv.validator_indexes[:] = found           # Vote.Verify with the key GetByAddress found
+            vc = V.verify_votes(eng, [V.VoteRequest(chain, vals, pv)])
+            k_votes = eng.last_kernel_ms()
+            a, b = vc[0::2], vc[1::2]
+            remap = np.array([0, 0, 0, 0, 0, 0, EV.DUPVOTE_ADDRESS_NOT_OF_KEY, EV.DUPVOTE_PANIC, 255, EV.DUPVOTE_GO_PATH], np.uint8)
+            ca = np.where(a == V.VOTE_INVALID_SIGNATURE, EV.DUPVOTE_VOTE_A_SIGNATURE, remap[a])
+            cb = np.where(b == V.VOTE_INVALID_SIGNATURE, EV.DUPVOTE_VOTE_B_SIGNATURE, remap[b])
+            codes = np.where(pre != 0, pre, np.where(ca != 0, ca, cb)).astype(np.uint8)
+            t2 = time.perf_counter()
+            bflat, boff, bok = EV.evidence_bytes_arrays(pe)
+            t3 = time.perf_counter()
+            roots = MK.merkle_roots_packed(eng, np.concatenate([bflat, np.zeros(8, np.uint8)]), boff.astype(np.uint64), list_off)
+            t4 = time.perf_counter()
+            return codes, bflat, boff, roots, (t1 - t0, t2 - t1, k_votes, t3 - t2, t4 - t3)
+
+        codes, evh, roots, _ = new_route()  # warm, and the agreement every timed run is held to
+        ocodes, bflat, boff, oroots, _ = old_route()
+        assert (codes == want).all(), "tmed_verify_duplicate_votes: unexpected codes"
+        assert (codes == ocodes).all(), "the two routes disagree on a code"
+        assert (roots == oroots).all(), "the two routes disagree on a root"
+        raw = bflat.tobytes()
+        for i in range(0, n, max(1, n // 64)):
+            assert bytes(evh[i]) == hashlib.sha256(raw[boff[i]:boff[i + 1]]).digest(), "DuplicateVoteEvidence.Hash differs"
+        new_t, old_t = [], []
+        for _ in range(runs):
+            c2, _, r2, t = new_route()
+            assert (c2 == codes).all() and (r2 == roots).all()
+            new_t.append(t)
+            c3_, _, _, r3, t = old_route()
+            assert (c3_ == codes).all() and (r3 == roots).all()
+            old_t.append(t)
+        nt, ot = np.array(new_t), np.array(old_t)
+        new_wall, old_wall = med(nt[:, 0] + nt[:, 1]), med(ot[:, 0] + ot[:, 1] + ot[:, 3] + ot[:, 4])
+        new_dev_ms = med(nt[:, 2] + nt[:, 3] + nt[:, 4] + nt[:, 5])
+        r = {"shape": text, "lists": L, "evidences": n, "validators": nvals, "bytes": int(boff[-1]),
+             "invalid": int((want != 0).sum()), "routes_agree": True,
+             "new_ms": round(new_wall * 1e3, 3), "new_evidences_per_s": round(n / new_wall, 1),
+             "verify_call_ms": round(med(nt[:, 0]) * 1e3, 3), "hashes_call_ms": round(med(nt[:, 1]) * 1e3, 3),
+             "lookup_kernel_ms": round(med(nt[:, 2]), 4), "prepare_kernel_ms": round(med(nt[:, 3]), 4),
+             "verify_kernels_ms": round(med(nt[:, 4]), 4), "hash_leaf_stage_ms": round(med(nt[:, 5]), 4),
+             "lookup_share_of_verify_call": round(med(nt[:, 2]) * 1e-3 / med(nt[:, 0]), 4),
+             "host_share": round(max(0.0, 1.0 - new_dev_ms * 1e-3 / new_wall), 3),
+             "old_ms": round(old_wall * 1e3, 3), "old_evidences_per_s": round(n / old_wall, 1),
+             "old_host_checks_ms": round(med(ot[:, 0]) * 1e3, 3), "old_verify_votes_ms": round(med(ot[:, 1]) * 1e3, 3),
+             "old_verify_votes_kernels_ms": round(med(ot[:, 2]), 4), "old_evidence_bytes_ms": round(med(ot[:, 3]) * 1e3, 3),
+             "old_merkle_roots_ms": round(med(ot[:, 4]) * 1e3, 3), "speedup": round(old_wall / new_wall, 3)}
+        eng.keyset_free(handle)
+        out.append(r)
+    return {"config": "evidence", "metric": "duplicate-vote evidences per second: tmed_verify_duplicate_votes + "
+            "tmed_evidence_hashes vs host checks + tmed_verify_votes + tmed_evidence_bytes + tmed_merkle_roots",
+            "runs": runs, "shapes": out}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="c1,c3,c4")
@@ -1188,6 +1326,8 @@ def main():
                     help="C4: a tmed_blocksync_verify call per window only (no submit/wait stream pass)")
     ap.add_argument("--no-pinned", action="store_true",
                     help="C4: commits in ordinary (pageable) memory: signatures go through the seam's staging copy")
+    ap.add_argument("--evidence-shapes", default="2048x10000,1000x4x175",
+                    help="evidence: NxV (one list of N evidences, V validators) or LxKxV (L lists of K), comma-separated")
     ap.add_argument("--rule", choices=["go", "zip215"], default="go",
                     help="the context's signature rule for every leg (tmed_set_rule): go, the default, or zip215")
     args = ap.parse_args()
@@ -1210,6 +1350,8 @@ def main():
             r = mt(eng, args.runs)
         elif cfg == "votes" and rank == 0:
             r = votes(eng, args.runs, not args.no_cpu)
+        elif cfg == "evidence" and rank == 0:
+            r = evidence(eng, min(args.runs, args.reps), tuple(args.evidence_shapes.split(",")))
         elif cfg == "c4":
             r = c4(eng, args.blocks, args.validators, rank, world, coll, args.window, args.batch, args.corrupt_every,
                        args.pregen, not args.no_pinned, args.c4_policy, not args.no_stream)

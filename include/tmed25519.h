@@ -631,7 +631,7 @@ int tmed_partset_roots(tmed_ctx *ctx, const uint8_t *data, const uint64_t *data_
 
 /*
  * The two other hashes Block.ValidateBasic recomputes for every block (types/block.go:55-106;
- * Evidence.Hash is a plain byte-slice tree: tmed_merkle_roots).
+ * Evidence.Hash is tmed_evidence_hashes below).
  *
  * tmed_commit_hashes: Commit.Hash() (types/block.go:894-912) for n commits =
  * HashFromByteSlices over cs.ToProto().Marshal() of every CommitSig, encoded on the device from the
@@ -1005,6 +1005,129 @@ int tmed_votes_sign_bytes(const char *chain_id, uint32_t chain_id_len, const tme
                           size_t out_cap, uint32_t *out_off, size_t *out_len, uint8_t *malformed);
 int tmed_verify_votes_host(const tmed_vote_request *reqs, size_t n_reqs, uint8_t *codes, uint32_t *msg_lens,
                            uint8_t *device_route);
+
+/* ------------------------------------------------- evidence */
+
+/*
+ * n DuplicateVoteEvidence (types/evidence.go:35-47) as flat arrays: the shared struct of
+ * tmed_verify_duplicate_votes and tmed_evidence_hashes.  A hash longer than 32 bytes, an address
+ * longer than 20 or a signature longer than 64 is described by its length alone, as in tmed_votes.
+ */
+typedef struct {
+  size_t n;                          /* evidences */
+  tmed_votes votes;                  /* 2n votes: VoteA of evidence i at 2i, VoteB at 2i+1 (votes.n == 2n) */
+  const int64_t *total_voting_powers;
+  const int64_t *validator_powers;
+  const int64_t *ts_seconds;         /* DuplicateVoteEvidence.Timestamp */
+  const int32_t *ts_nanos;
+} tmed_dup_evidence;
+
+typedef struct {
+  const char *chain_id;
+  uint32_t chain_id_len;
+  const tmed_valset *vals;  /* the set Pool.verify loads for the evidence's height (evidence/verify.go:55-59);
+                               `pubkeys`, `addresses`, `powers` and `total_power` are read; keyset 0 = the key-set
+                               cache decides, as for votes */
+  const tmed_dup_evidence *ev;
+} tmed_dup_request;
+
+/* One outcome per evidence: the FIRST check that fails, in the reference's order (evidence/verify.go:162-222). */
+#define TMED_DUPVOTE_OK 0
+#define TMED_DUPVOTE_NOT_A_VALIDATOR 1    /* "address %X was not a validator at height %d": GetByAddress(VoteA.
+                                             ValidatorAddress) finds nobody (:163-166).  The match is the first
+                                             validator, in index order, whose address equals it under bytes.Equal
+                                             (types/validator_set.go:270-278); a vote address of any length but 20
+                                             matches none */
+#define TMED_DUPVOTE_HRS_MISMATCH 2       /* "h/r/s does not match": height, round or type differ (:170-176) */
+#define TMED_DUPVOTE_ADDRESS_MISMATCH 3   /* "validator addresses do not match": !bytes.Equal(A.addr, B.addr), lengths
+                                             included (:179-184) */
+#define TMED_DUPVOTE_SAME_BLOCK_ID 4      /* "block IDs are the same (%v) - not a real duplicate vote": BlockID.Equals
+                                             (types/block.go:1170-1173): hashes, totals and part-set hashes all equal;
+                                             an empty slice equals a nil one (:187-192) */
+#define TMED_DUPVOTE_ADDRESS_NOT_OF_KEY 5 /* "address (%X) doesn't match pubkey": SHA-256(found key)[:20] differs from
+                                             VoteA's address (:195-199); the set's `addresses` may disagree with its keys */
+#define TMED_DUPVOTE_VALIDATOR_POWER 6    /* powers[found] differs from the evidence's ValidatorPower (:202-205) */
+#define TMED_DUPVOTE_TOTAL_POWER 7        /* vals->total_power differs from the evidence's TotalVotingPower (:206-209) */
+#define TMED_DUPVOTE_PANIC 8              /* VoteSignBytes of the vote now under test panics on a malformed BlockID, as
+                                             TMED_VOTE_PANIC; the caller runs the Go path, which panics as before */
+#define TMED_DUPVOTE_VOTE_A_SIGNATURE 9   /* "verifying VoteA: %w" ErrVoteInvalidSignature, a length other than 64
+                                             included (:214-216) */
+#define TMED_DUPVOTE_VOTE_B_SIGNATURE 10  /* "verifying VoteB: %w" (:217-219) */
+#define TMED_DUPVOTE_GO_PATH 11           /* the structs do not determine the outcome; the caller runs Go for this
+                                             evidence: (a) a vote timestamp StdTimeMarshal refuses, as TMED_VOTE_GO_PATH;
+                                             (b) at check 4 BlockID.Equals hangs on a pair of hashes of the same length
+                                             above 32, whose bytes are not carried (when another of its three
+                                             comparisons is false the answer is "different" and the checks go on) */
+
+/*
+ * VerifyDuplicateVote (evidence/verify.go:162-222) for many evidences per call; codes[k]: the outcome
+ * of evidence k, request r's evidences starting at the sum of the counts of the requests before it.
+ * The reference computes VoteA's sign-bytes, verifies VoteA, then VoteB's and verifies VoteB; so the
+ * code is: the first failing check of 1-7 (or GO_PATH at check 4); else VoteA's PANIC / GO_PATH; else 9
+ * if VoteA's signature is invalid; else VoteB's PANIC / GO_PATH; else 10; else 0.  Both signatures are
+ * checked against the key of the validator GetByAddress found (keyset_index[found] on the keyed
+ * route, its 32 bytes on the generic one): the votes' validator_indexes are never used for this.
+ * The context's rule (tmed_set_rule) applies, as to every seam call.
+ *
+ * Device work (csrc/evidence.hip; the checks are csrc/evidence_free.h, compiled by host and device
+ * alike): evidence_lookup_kernel (one wavefront per evidence scans the set's addresses; no sort, no
+ * host map), evidence_prepare_kernel (one lane per evidence: checks 2-7, the votes' states, both
+ * sign-bytes into kVoteSlot slots, both keys), then the unchanged verify kernels over the 2n slots.
+ * A request whose chain ID is longer than 50 bytes takes a host route by the same source, as votes
+ * do; decisions are identical.  Submitted blocksync windows are collected first.  After the call
+ * tmed_last_kernel_ms reports the two new kernels plus the verify kernels;
+ * tmed_evidence_kernel_times gives the lookup's (ms[0]) and the prepare kernel's (ms[1]) share.
+ * What stays in Go: ValidateBasic (the contract at verify.go:110), the age and time checks, the
+ * committed / pending lookups and the duplicate-hash loop of Pool.verify / CheckEvidence, and
+ * LightClientAttackEvidence (its checks map onto tmed_verify_commits).
+ * TMED_EINVAL for malformed calls only: a NULL array with n > 0, votes.n != 2n, NULL vals->pubkeys,
+ * addresses or powers with vals->n > 0, a keyset_index past the key set.
+ */
+int tmed_verify_duplicate_votes(tmed_ctx *ctx, const tmed_dup_request *reqs, size_t n_reqs, uint8_t *codes);
+int tmed_evidence_kernel_times(tmed_ctx *ctx, float ms[2]);
+
+/*
+ * DuplicateVoteEvidence.Hash() = tmhash.Sum(Bytes()) (types/evidence.go:90-103) for every evidence of
+ * `ev`, and EvidenceList.Hash() = HashFromByteSlices(evl[i].Bytes()) (:431-442) for n_lists lists.
+ * List l's items are items[list_off[l] .. list_off[l+1]): items[k] >= 0 names an evidence of ev;
+ * items[k] < 0 names the host-marshalled byte string -1 - items[k] of opaque / opaque_off (string j =
+ * opaque[opaque_off[j] .. opaque_off[j+1])): that is how a LightClientAttackEvidence enters a list.
+ * ev_hashes: n x 32 (nullable); roots: n_lists x 32; ev_ok: n (nullable); list_ok: n_lists (nullable).
+ * ev_ok[i] = 0, with the hash zeroed, where the struct cannot reproduce Bytes(): a hash longer than
+ * 32 or an address longer than 20 (bytes not carried), a signature longer than 64, or a timestamp,
+ * a vote's or the evidence's, that StdTimeMarshal refuses (Bytes() panics).  list_ok[l] = 0, with the
+ * root zeroed, if one of its evidences has ev_ok = 0.  An empty list gives SHA-256("") with list_ok = 1.
+ *
+ * The Bytes() rule is DERIVED from the generated marshallers (evidence.pb.go:449-497, types.pb.go:
+ * 1431-1489, :1153-1171, :1233-1256; csrc/evidence_free.h states it field by field): the reference
+ * holds no known answer and no size bound for these bytes (evidence_test.go only round-trips), so
+ * unlike CommitSig's 109 the 234-byte Vote and 520-byte evidence bounds are this library's own.
+ *
+ * Device work: evidence_hash_kernel (one lane per evidence encodes into an LDS slot and hashes it
+ * twice: SHA-256(bytes) and the leaf SHA-256(0x00 || bytes)), the byte-slice leaf kernel over the
+ * opaque items, a gather into level 0, then the level builder of the other root calls.
+ * tmed_last_kernel_ms reports the leaf stage (those three kernels).  TMED_EINVAL: a NULL array that
+ * is needed, votes.n != 2n, offsets that decrease, an item naming an evidence >= ev->n.
+ */
+int tmed_evidence_hashes(tmed_ctx *ctx, const tmed_dup_evidence *ev, const int64_t *items, const uint32_t *list_off,
+                         size_t n_lists, const uint8_t *opaque, const uint64_t *opaque_off, uint8_t *ev_hashes,
+                         uint8_t *roots, uint8_t *ev_ok, uint8_t *list_ok);
+
+/*
+ * Host entries, no device and no context (csrc/evidence_host.h over csrc/evidence_free.h):
+ * tmed_evidence_bytes: Bytes() of every evidence, evidence i at out[out_off[i] .. out_off[i+1])
+ *   (sizing and TMED_ENOMEM as tmed_vote_sign_bytes).  Where ev_ok would be 0 nothing is encoded (an
+ *   empty range) and ok[i] = 0; with ok NULL such an evidence is TMED_EINVAL.
+ * tmed_verify_duplicate_votes_host: lane by lane, pre_codes[k] = the first failing check of 1-7 (or
+ *   GO_PATH at check 4; 0 where the signatures would decide); vote_states[2k], [2k+1] (nullable) = 0,
+ *   PANIC or GO_PATH of VoteA / VoteB; found[k] (nullable) = the validator GetByAddress finds or -1;
+ *   msg_lens[2k], [2k+1] (nullable) = the lengths of the sign-bytes (0 where none are made);
+ *   device_route[r] (nullable) = 1 when request r's messages are assembled on the device.
+ */
+int tmed_evidence_bytes(const tmed_dup_evidence *ev, uint8_t *out, size_t out_cap, uint32_t *out_off, size_t *out_len,
+                        uint8_t *ok);
+int tmed_verify_duplicate_votes_host(const tmed_dup_request *reqs, size_t n_reqs, uint8_t *pre_codes,
+                                     uint8_t *vote_states, int32_t *found, uint32_t *msg_lens, uint8_t *device_route);
 
 /* ------------------------------------------------- blocksync replay (f4) */
 

@@ -36,6 +36,7 @@
 #include "host_pool.h"
 #include "signbytes.h"
 #include "votes_host.h"
+#include "evidence_host.h"
 
 // One translation unit, by role (each header is included here only, in this order):
 //   seam_host.h   planning, aliasing, staging groups, scatter, replay: host C++ only
@@ -367,6 +368,36 @@ extern "C" int tmed_verify_votes(tmed_ctx *ctx, const tmed_vote_request *reqs, s
     std::vector<tmed_vote_request> rq(reqs, reqs + n_reqs);
     for (size_t q = 0; q < n_reqs; q++) rq[q].vals = resolved[q].vals;
     return tmed::locked(ctx, /*collect=*/true, [&] { return tmed::verify_votes_locked(ctx, rq.data(), n_reqs, codes); });
+  });
+}
+
+// ---- evidence: VerifyDuplicateVote (evidence.hip) --------------------------------------------------
+// The requests' sets go through the key-set cache as the votes' do: each request stands in as a commit
+// request of two signatures per evidence.
+extern "C" int tmed_verify_duplicate_votes(tmed_ctx *ctx, const tmed_dup_request *reqs, size_t n_reqs, uint8_t *codes) {
+  if (!ctx || (n_reqs && !reqs)) return TMED_EINVAL;
+  return c_guard(ctx, [&] {
+    size_t total = 0;
+    for (size_t q = 0; q < n_reqs; q++) {
+      if (tmed_evidence_host::check_request(reqs[q]) != TMED_OK) return (int)TMED_EINVAL;
+      total += reqs[q].ev->n;
+    }
+    if (total && !codes) return (int)TMED_EINVAL;
+    std::vector<tmed_commit> shadow_commits(n_reqs);
+    std::vector<tmed_commit_request> shadow(n_reqs);
+    for (size_t q = 0; q < n_reqs; q++) {
+      memset(&shadow_commits[q], 0, sizeof(tmed_commit));
+      memset(&shadow[q], 0, sizeof(tmed_commit_request));
+      shadow_commits[q].n_sigs = 2 * reqs[q].ev->n;
+      shadow[q].vals = reqs[q].vals;
+      shadow[q].commit = &shadow_commits[q];
+    }
+    KcCall kc;  // pins the cache's pool until the batch below is collected
+    const tmed_commit_request *resolved = keycache_resolve(ctx, shadow.data(), n_reqs, kc);
+    std::vector<tmed_dup_request> rq(reqs, reqs + n_reqs);
+    for (size_t q = 0; q < n_reqs; q++) rq[q].vals = resolved[q].vals;
+    return tmed::locked(ctx, /*collect=*/true,
+                        [&] { return tmed::verify_dup_votes_locked(ctx, rq.data(), n_reqs, codes); });
   });
 }
 

@@ -151,6 +151,19 @@ int median_times_locked(tmed_ctx *c, const tmed_median_request *reqs, size_t n, 
 // votes.hip: tmed_verify_votes over n checked requests (votes_host.h check_request) whose sets the
 // key-set cache has resolved; ctx->mu held.
 int verify_votes_locked(tmed_ctx *c, const tmed_vote_request *reqs, size_t n, uint8_t *codes);
+// evidence.hip: tmed_verify_duplicate_votes over n checked requests (evidence_host.h check_request)
+// whose sets the key-set cache has resolved; ctx->mu held.
+int verify_dup_votes_locked(tmed_ctx *c, const tmed_dup_request *reqs, size_t n, uint8_t *codes);
+// merkle.hip's tree builder for evidence.hip (EvidenceList.Hash): room for the plan's nodes, the
+// node buffer's start (a leaf stage writes level 0 there), leafHash of n device-resident byte
+// slices into out (32-byte digests as state words), the levels, the roots; ctx->mu held, everything
+// queued on stream s without waiting.
+struct MerkleLevels;
+int merkle_ensure_nodes(tmed_ctx *c, const MerkleLevels &plan);
+void *merkle_level0(tmed_ctx *c);
+hipError_t merkle_leaf_hashes(const uint8_t *d_leaves, const uint64_t *d_off, uint32_t n, void *d_out, hipStream_t s);
+hipError_t merkle_build_levels(tmed_ctx *c, const MerkleLevels &plan, hipStream_t s);
+hipError_t merkle_emit_roots(tmed_ctx *c, const MerkleLevels &plan, uint8_t *d_roots, hipStream_t s);
 // keyset.hip: a key-cached batch of device-resident tuples on stream s, as the commit seam runs it
 // (latency kernels up to lat_max, the throughput kernels above); inside a scratch_acquire/release pair.
 // rule: TMED_RULE_* of the call (the seam passes the rule it read once at its entry).
@@ -337,14 +350,16 @@ struct tmed_ctx {
   // totals / indexes and codes)
   tmed::DevBuf d_proof_off, d_proof_out, d_proof_in;
   // The staging arena of commit_hashes_locked, header_hashes_fused (merkle.hip), median_times_locked
-  // (median.hip) and run_group_device (votes.hip), each laid out by its own layout struct.  One pair
-  // serves all four: each packs, copies in, launches, copies out, waits (finish_call) and reads its
+  // (median.hip), run_group_device (votes.hip) and the two device batches of evidence.hip, each laid out
+  // by its own layout struct.  One pair serves them all: each packs, copies in, launches, copies out, waits (finish_call) and reads its
   // results before it returns, all inside one hold of ctx->mu, so no two are ever live at once (a
   // light-client call takes its header hashes, set hashes and commit checks under separate holds, one
   // after the other).  No batch of a submitted blocksync window touches it: those hold the vote slots.
   tmed::Staged stage;
   hipEvent_t vote_ev = nullptr;  // the end of vote_prepare_kernel (last_vote_prep_ms)
   float last_vote_prep_ms = 0.f;
+  hipEvent_t ev_lookup = nullptr;        // the end of evidence_lookup_kernel (evidence.hip)
+  float last_ev_ms[2] = {0.f, 0.f};      // evidence_lookup_kernel, evidence_prepare_kernel (tmed_evidence_kernel_times)
   tmed::DevBuf d_korder;  // key-grouped order of a key-cached batch: counts / cursors + permutation
   tmed::DevBuf d_zip;     // ZIP-215 batch mode scratch (zip215.hip zip_bufs: points, digits, sort, buckets)
   bool zip_dense = false; // ZIP-215: the last large chunk had failures (zip215.hip: decide the next one singly first)

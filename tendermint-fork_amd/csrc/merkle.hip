@@ -781,6 +781,17 @@ int forest_proofs(tmed_ctx *c, const uint8_t *leaves, const uint64_t *leaf_off, 
 
 namespace tmed {
 
+// The tree builder as evidence.hip uses it (ctx.h).
+int merkle_ensure_nodes(tmed_ctx *c, const MerkleLevels &plan) { return ensure_nodes(c, plan); }
+void *merkle_level0(tmed_ctx *c) { return dev_nodes(c); }
+hipError_t merkle_leaf_hashes(const uint8_t *d_leaves, const uint64_t *d_off, uint32_t n, void *d_out, hipStream_t s) {
+  return launch(hipSuccess, merkle_leaf_kernel, n, s, d_leaves, d_off, n, (Digest *)d_out);
+}
+hipError_t merkle_build_levels(tmed_ctx *c, const MerkleLevels &plan, hipStream_t s) { return build_levels(c, plan, s); }
+hipError_t merkle_emit_roots(tmed_ctx *c, const MerkleLevels &plan, uint8_t *d_roots, hipStream_t s) {
+  return emit_roots(c, plan, d_roots, s);
+}
+
 bool header_pointers_ok(const tmed_header &h) {
   for (int k = 0; k < 9; k++)
     if (h.hash_lens[k] && !h.hashes[k]) return false;

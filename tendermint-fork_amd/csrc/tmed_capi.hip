@@ -233,6 +233,7 @@ void tmed_destroy(tmed_ctx *c) {
     b->release();
   c->stage.release();
   if (c->vote_ev) hipEventDestroy(c->vote_ev);
+  if (c->ev_lookup) hipEventDestroy(c->ev_lookup);
   c->h_kup.release();
   if (c->kup_ev) hipEventDestroy(c->kup_ev);
   c->h_zip.release();

@@ -1696,3 +1696,172 @@ func (e *Engine) VerifyVotes(reqs []VoteRequest) ([][]uint8, error) {
 	}
 	return out, nil
 }
+
+// ---- evidence: VerifyDuplicateVote (evidence/verify.go:162-222), DuplicateVoteEvidence.Hash and
+// EvidenceList.Hash (types/evidence.go:90-103, :431-442) ----
+
+// Outcome codes of VerifyDuplicateVotes: the first check that fails, in the reference's order (see
+// tmed25519.h, which cites the reference line and error string of each).
+const (
+	DupVoteOK              = C.TMED_DUPVOTE_OK
+	DupVoteNotAValidator   = C.TMED_DUPVOTE_NOT_A_VALIDATOR
+	DupVoteHRSMismatch     = C.TMED_DUPVOTE_HRS_MISMATCH
+	DupVoteAddressMismatch = C.TMED_DUPVOTE_ADDRESS_MISMATCH
+	DupVoteSameBlockID     = C.TMED_DUPVOTE_SAME_BLOCK_ID
+	DupVoteAddressNotOfKey = C.TMED_DUPVOTE_ADDRESS_NOT_OF_KEY
+	DupVoteValidatorPower  = C.TMED_DUPVOTE_VALIDATOR_POWER
+	DupVoteTotalPower      = C.TMED_DUPVOTE_TOTAL_POWER
+	// DupVotePanic: VoteSignBytes of the vote under test panics (a malformed BlockID hash); the caller
+	// runs the original Go path, which panics as before.
+	DupVotePanic          = C.TMED_DUPVOTE_PANIC
+	DupVoteVoteASignature = C.TMED_DUPVOTE_VOTE_A_SIGNATURE
+	DupVoteVoteBSignature = C.TMED_DUPVOTE_VOTE_B_SIGNATURE
+	// DupVoteGoPath: the flat fields do not determine the reference's outcome: the caller runs
+	// VerifyDuplicateVote itself for this evidence.
+	DupVoteGoPath = C.TMED_DUPVOTE_GO_PATH
+)
+
+// DupEvidenceData is a flat copy of n types.DuplicateVoteEvidence values: VoteA of evidence i is
+// vote 2i of Votes, VoteB vote 2i+1.
+type DupEvidenceData struct {
+	Votes             *VoteData // 2n votes
+	TotalVotingPowers []int64
+	ValidatorPowers   []int64
+	TsSeconds         []int64 // DuplicateVoteEvidence.Timestamp
+	TsNanos           []int32
+}
+
+// NewDupEvidenceData: n evidences in Go memory (copied into the call's arena once).
+func NewDupEvidenceData(n int) *DupEvidenceData {
+	return &DupEvidenceData{Votes: NewVoteData(2 * n), TotalVotingPowers: make([]int64, n), ValidatorPowers: make([]int64, n),
+		TsSeconds: make([]int64, n), TsNanos: make([]int32, n)}
+}
+
+func (a *arena) dupEvidenceC(d *DupEvidenceData) C.tmed_dup_evidence {
+	n := len(d.TotalVotingPowers)
+	t := C.tmed_dup_evidence{n: C.size_t(n), votes: a.votesC(d.Votes)}
+	if n == 0 {
+		return t
+	}
+	t.total_voting_powers, t.validator_powers = a.i64(d.TotalVotingPowers), a.i64(d.ValidatorPowers)
+	t.ts_seconds, t.ts_nanos = a.i64(d.TsSeconds), a.i32(d.TsNanos)
+	return t
+}
+
+// DupVoteRequest is one batch of duplicate-vote evidence against the validator set of its height
+// (the set Pool.verify loads, evidence/verify.go:55-59).
+type DupVoteRequest struct {
+	ChainID  string
+	Vals     *ValSet
+	Evidence *DupEvidenceData
+}
+
+// VerifyDuplicateVotes runs VerifyDuplicateVote on every evidence of every request in ONE device
+// batch (tmed_verify_duplicate_votes) and returns the DupVote* outcome codes, one slice per request.
+// ValidateBasic, the age checks and the pool's lookups stay with the caller.  An error means "take
+// the original Go path".
+func (e *Engine) VerifyDuplicateVotes(reqs []DupVoteRequest) ([][]uint8, error) {
+	n := len(reqs)
+	if n == 0 {
+		return nil, nil
+	}
+	a := e.getArena()
+	defer e.putArena(a)
+	creqs := (*[1 << 24]C.tmed_dup_request)(a.alloc(uintptr(n) * unsafe.Sizeof(C.tmed_dup_request{})))[:n:n]
+	ce := (*[1 << 22]C.tmed_dup_evidence)(a.alloc(uintptr(n) * unsafe.Sizeof(C.tmed_dup_evidence{})))[:n:n]
+	vs := (*[1 << 24]C.tmed_valset)(a.alloc(uintptr(n) * unsafe.Sizeof(C.tmed_valset{})))[:n:n]
+	seenV := make(map[*ValSet]*C.tmed_valset, n)
+	total := 0
+	for i := range reqs {
+		r := &reqs[i]
+		if r.Vals == nil || r.Evidence == nil || r.Evidence.Votes == nil ||
+			len(r.Evidence.Votes.Types) != 2*len(r.Evidence.TotalVotingPowers) {
+			return nil, errors.New("tmedgpu: VerifyDuplicateVotes: nil evidence or validator set, or not two votes per evidence")
+		}
+		set, ok := seenV[r.Vals]
+		if !ok {
+			vs[i] = a.valset(r.Vals)
+			set = &vs[i]
+			seenV[r.Vals] = set
+		}
+		ce[i] = a.dupEvidenceC(r.Evidence)
+		creqs[i] = C.tmed_dup_request{chain_id: a.cstring(r.ChainID), chain_id_len: C.uint32_t(len(r.ChainID)),
+			vals: set, ev: &ce[i]}
+		total += len(r.Evidence.TotalVotingPowers)
+	}
+	codes := make([]uint8, total+1)
+	if rc := C.tmed_verify_duplicate_votes(e.ctx, &creqs[0], C.size_t(n), (*C.uint8_t)(unsafe.Pointer(&codes[0]))); rc != 0 {
+		return nil, errors.New(C.GoString(C.tmed_strerror(rc)))
+	}
+	out := make([][]uint8, n)
+	at := 0
+	for i := range reqs {
+		m := len(reqs[i].Evidence.TotalVotingPowers)
+		out[i] = codes[at : at+m : at+m]
+		at += m
+	}
+	return out, nil
+}
+
+// EvidenceItem names one entry of an evidence list: evidence Index of the call's DupEvidenceData, or,
+// when Opaque is not nil, the bytes the caller marshalled itself (a LightClientAttackEvidence's Bytes()).
+type EvidenceItem struct {
+	Index  int
+	Opaque []byte
+}
+
+// EvidenceHashes returns DuplicateVoteEvidence.Hash() of every evidence of d and EvidenceList.Hash()
+// of every list (tmed_evidence_hashes: Bytes() is encoded and hashed on the device).  evOK[i] is false
+// where the flat fields cannot reproduce Bytes() (a hash longer than 32, an address longer than 20, a
+// signature longer than 64, a timestamp the reference's Marshal rejects), listOK[l] where list l names
+// such an evidence: the caller runs the Go method for those.
+func (e *Engine) EvidenceHashes(d *DupEvidenceData, lists [][]EvidenceItem) (hashes [][32]byte, roots [][32]byte, evOK []bool, listOK []bool, err error) {
+	if d == nil || d.Votes == nil {
+		return nil, nil, nil, nil, errors.New("tmedgpu: EvidenceHashes: nil evidence")
+	}
+	n, nl := len(d.TotalVotingPowers), len(lists)
+	if n+nl == 0 {
+		return nil, nil, nil, nil, nil
+	}
+	var items []int64
+	var opaque []byte
+	listOff := []uint32{0}
+	opOff := []uint64{0}
+	for _, l := range lists {
+		for _, it := range l {
+			if it.Opaque != nil {
+				items = append(items, int64(-len(opOff)))
+				opaque = append(opaque, it.Opaque...)
+				opOff = append(opOff, uint64(len(opaque)))
+			} else {
+				items = append(items, int64(it.Index))
+			}
+		}
+		listOff = append(listOff, uint32(len(items)))
+	}
+	opaque = append(opaque, make([]byte, 8)...) // the device reader may touch the last dword
+	a := e.getArena()
+	defer e.putArena(a)
+	ce := (*C.tmed_dup_evidence)(a.alloc(unsafe.Sizeof(C.tmed_dup_evidence{})))
+	*ce = a.dupEvidenceC(d)
+	ho := (*[1 << 26][32]byte)(a.alloc(uintptr(n+1) * 32))[: n+1 : n+1]
+	ro := (*[1 << 26][32]byte)(a.alloc(uintptr(nl+1) * 32))[: nl+1 : nl+1]
+	eok := (*[1 << 30]C.uint8_t)(a.alloc(uintptr(n + 1)))[: n+1 : n+1]
+	lok := (*[1 << 30]C.uint8_t)(a.alloc(uintptr(nl + 1)))[: nl+1 : nl+1]
+	var citems *C.int64_t
+	if len(items) > 0 {
+		citems = a.i64(items)
+	}
+	if rc := C.tmed_evidence_hashes(e.ctx, ce, citems, a.u32(listOff), C.size_t(nl), a.bytes(opaque), a.u64(opOff),
+		(*C.uint8_t)(unsafe.Pointer(&ho[0])), (*C.uint8_t)(unsafe.Pointer(&ro[0])), &eok[0], &lok[0]); rc != 0 {
+		return nil, nil, nil, nil, errors.New(C.GoString(C.tmed_strerror(rc)))
+	}
+	evOK, listOK = make([]bool, n), make([]bool, nl)
+	for i := range evOK {
+		evOK[i] = eok[i] != 0
+	}
+	for i := range listOK {
+		listOK[i] = lok[i] != 0
+	}
+	return append([][32]byte(nil), ho[:n]...), append([][32]byte(nil), ro[:nl]...), evOK, listOK, nil
+}

@@ -8,3 +8,5 @@ from ._native import LIB_PATH, TmedError, lib  # noqa: F401
 from .engine import Engine, PinnedBuffer, pack_messages  # noqa: F401
 from .state import median_times  # noqa: F401
 from .votes import Vote, VoteRequest, verify_votes  # noqa: F401
+from .evidence import (DuplicateVoteEvidence, EvidenceRequest, evidence_bytes, evidence_hashes,  # noqa: F401
+                       verify_duplicate_votes)
