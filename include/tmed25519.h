@@ -311,6 +311,17 @@ int tmed_test_joint_rows(tmed_ctx *ctx, const uint8_t *a, const uint8_t *r, cons
                          uint8_t *rows);
 
 /*
+ * Tests only (tests/test_gpu_lds_rows.py): the same table built through the accessor of the default
+ * main kernel, which keeps rows 1 (-+R) and 5 (-A) in LDS without Z and the other ten in the
+ * slab.  rows: n x 12 x 128 bytes in and out, the slab: rows 1 and 5 of every triple come back as
+ * they went in.  out: n x 13 x 2 x 40 int32, every row 0..12 (0: the identity) read back through
+ * the accessor, first as stored, then with Y+X and Y-X exchanged (a negative digit's read), as the
+ * ten limbs each of Y+X, Y-X, Z, 2dT that the kernel computes with.
+ */
+int tmed_test_lds_rows(tmed_ctx *ctx, const uint8_t *a, const uint8_t *r, const uint8_t *dneg, size_t n,
+                       uint8_t *rows, int32_t *out);
+
+/*
  * Tests only (tests/test_gpu_table_rows.py): the fixed-base tables of B, row by row.  table: 0 the
  * radix-256 comb (32 windows x 129 rows), 1 the radix-2^16 table (32769 rows), 2 the radix-2^16
  * comb (16 x 32769), 3 the two radix-2^26 tables (2 x (2^25 + 1)), 4 the radix-2^24 comb

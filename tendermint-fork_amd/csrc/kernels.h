@@ -200,6 +200,11 @@ hipError_t launch_test_delay(hipStream_t stream, uint32_t us);
 // rows ([i][12][128 B], n * kSlabJointSlotBytes bytes).
 hipError_t launch_test_joint_rows(const uint8_t *a, const uint8_t *r, const uint8_t *dneg, uint32_t n, int4 *rows,
                                   hipStream_t stream);
+// Tests (tmed_test_lds_rows): the same tables built through verify_main_hs_kernel<26>'s accessor (rows
+// 1 and 5 in LDS: their lines of rows are left as they were), then rows 0..12 read back, swap false
+// and true, as limbs into out ([i][13][2][40 int32]).
+hipError_t launch_test_lds_rows(const uint8_t *a, const uint8_t *r, const uint8_t *dneg, uint32_t n, int4 *rows,
+                                int32_t *out, hipStream_t stream);
 // Tests (tmed_test_table_chain): one lane per row of a whole table of `units` x `windows` windows,
 // window w's rows at w * entries (the last window holds top_entries rows), one unit after the
 // other from base, or key by key through a key set's chunk table.  Row (w, 0) must be the

@@ -14,7 +14,7 @@
 //   pub   n x 32 B, sig n x 64 B (16-B aligned rows -> dwordx4 loads)
 //   msgs  concatenated bytes, off[n+1] u32 (or fixed 256-B vote slots)
 //   slab  per-lane variable-base tables: 12 (joint table of -A and R) or 8 cached points x 128 B (fe_pack256),
-//         lane-major [slot][entry][chunk]
+//         lane-major [slot][entry][chunk]; the default main kernel keeps entries 1 and 5 in LDS instead
 //   b16   32769 niels multiples of B in 128-B rows in HBM (4.2 MB; the full-length fallback, variant 5)
 //   combs key-set combs [key][window][entry] and the shared combs of B (radix 256, radix 2^16)
 #include "kernels.h"
@@ -91,6 +91,95 @@ struct SlabTabN {
 using SlabTab = SlabTabN<8>;
 using SlabTabJ = SlabTabN<kJointRows>;
 static_assert(kSlabSlotBytes == 8 * 128 && kSlabJointSlotBytes == kJointRows * 128, "slab rows are 128 B");
+
+// The joint table of verify_main_hs_kernel<26>: SlabTabJ with rows 1 (Q) and 5 (P) in LDS.  One
+// sub-step lookup in four reads P or Q alone (a radix-4 digit pair (+-1, 0) or (0, +-1)), the two
+// rows that are affine and that build_table_joint reads back, so they stay on the CU: lds is the
+// block's [2][kLdsRowInt4][kHsBlock] array (row, piece, lane — lane l's piece q of P at
+// lds[(kLdsRowInt4 + q) * kHsBlock + l], as the B rows are staged), Y+X, Y-X and 2dT in
+// fe_pack256 form; Z = 1 is not stored.  Their slab lines are never written or read (the slot
+// stride stays kSlabJointSlotBytes).  prefetch issues the slab loads (the lanes whose row is in LDS
+// read the shared identity row with them); take reads LDS into the same registers for those lanes.
+// The slab loads stay global_load and the LDS reads ds_read (see kIdentityRow: no select between
+// the two pointers).
+constexpr int kLdsRowInt4 = 6;
+constexpr uint32_t kLdsRowsInt4 = 2 * kLdsRowInt4 * kThreadsPerBlock;  // int4 per block: 48 KB
+// (the two kinds of load through pointers of their own address spaces: through generic pointers the
+// compiler merged a prefetch and the take after it into one flat load from a selected pointer)
+typedef int v4i __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) v4i glb_v4i;
+typedef __attribute__((address_space(3))) v4i lds_v4i;
+struct SlabLdsTabJ {
+  int4 *blk;     // the slab slot of the block's lane 0 (uniform) and the lane's index in the block:
+  uint32_t tid;  // a row's address is made from the two where it is loaded, no 64-bit one is kept per lane
+  int4 *lds;     // the block's array + the lane's index in the block
+  __device__ __forceinline__ int4 *slab_row(int j) const { return blk + (tid * kJointRows + (uint32_t)(j - 1)) * 8u; }
+
+  __device__ __forceinline__ static bool in_lds(int j) { return j == 1 || j == 5; }
+
+  __device__ __forceinline__ void store(int j, const ge_cached &c) const {
+    if (j == 0) return;
+    if (in_lds(j)) {
+      lds_v4i *r = (lds_v4i *)lds + (j == 5 ? kLdsRowInt4 : 0) * kThreadsPerBlock;
+      const fe *fs[3] = {&c.YpX, &c.YmX, &c.T2d};
+#pragma unroll
+      for (int f = 0; f < 3; f++) {
+        uint32_t w[8];
+        fe_pack256(w, *fs[f]);
+        r[(2 * f) * kThreadsPerBlock] = v4i{(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
+        r[(2 * f + 1) * kThreadsPerBlock] = v4i{(int)w[4], (int)w[5], (int)w[6], (int)w[7]};
+      }
+      return;
+    }
+    glb_v4i *r = (glb_v4i *)slab_row(j);
+    const fe *fs[4] = {&c.YpX, &c.YmX, &c.Z, &c.T2d};
+#pragma unroll
+    for (int f = 0; f < 4; f++) {
+      uint32_t w[8];
+      fe_pack256(w, *fs[f]);
+      r[2 * f] = v4i{(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
+      r[2 * f + 1] = v4i{(int)w[4], (int)w[5], (int)w[6], (int)w[7]};
+    }
+  }
+  v4i pv[8];
+  bool inl, isp, swp;  // the prefetched row is in LDS; it is P; Y+X and Y-X exchanged (lane masks in
+                       // scalar registers: the kernel has no vector register to spare)
+  // The lanes whose row is in LDS load the shared identity row, an L2 hit as for digit 0: with the
+  // slab loads under a branch of their own the compiler's wait counts at the join were vmcnt(0),
+  // the whole prefetch distance.
+  __device__ __forceinline__ void prefetch(int j, bool swap = false) {
+    inl = in_lds(j);
+    isp = j == 5;
+    swp = swap;
+    const glb_v4i *r = (const glb_v4i *)(j == 0 || inl ? kIdentityRow : slab_row(j));
+    const int sx = swap ? 2 : 0;
+#pragma unroll
+    for (int q = 0; q < 8; q++) pv[q] = r[q < 4 ? (q ^ sx) : q];
+  }
+  __device__ __forceinline__ void take(ge_cached &c) {
+    if (inl) {
+      const lds_v4i *r = (const lds_v4i *)lds + (isp ? kLdsRowInt4 : 0) * (int)kThreadsPerBlock;
+      const int sx = swp ? 2 * (int)kThreadsPerBlock : 0;  // swap, through the read addresses
+      const lds_v4i *a = r + sx, *b = r + (2 * (int)kThreadsPerBlock - sx);
+      pv[0] = a[0];
+      pv[1] = a[kThreadsPerBlock];
+      pv[2] = b[0];
+      pv[3] = b[kThreadsPerBlock];
+      pv[4] = v4i{1, 0, 0, 0};  // Z = 1: fe_unpack256 gives exactly fe_1
+      pv[5] = v4i{0, 0, 0, 0};
+      pv[6] = r[4 * kThreadsPerBlock];
+      pv[7] = r[5 * kThreadsPerBlock];
+    }
+    fe *fs[4] = {&c.YpX, &c.YmX, &c.Z, &c.T2d};
+#pragma unroll
+    for (int f = 0; f < 4; f++) {
+      const uint32_t w[8] = {(uint32_t)pv[2 * f].x, (uint32_t)pv[2 * f].y, (uint32_t)pv[2 * f].z,
+                             (uint32_t)pv[2 * f].w, (uint32_t)pv[2 * f + 1].x, (uint32_t)pv[2 * f + 1].y,
+                             (uint32_t)pv[2 * f + 1].z, (uint32_t)pv[2 * f + 1].w};
+      fe_unpack256(*fs[f], w);
+    }
+  }
+};
 
 typedef __attribute__((address_space(1))) void global_void;
 typedef __attribute__((address_space(3))) void lds_void;
@@ -305,51 +394,84 @@ __global__ __launch_bounds__(kHsBlock, kPrepRWaves) void verify_prep_r_kernel(
     prep2[(size_t)q * stride + pos] = make_int4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
 }
 
+// The lane's index in its wave, computed afresh where it is used (two v_mbcnt on an operand the
+// compiler cannot see through, so the value is neither hoisted out of a loop nor kept): the main
+// kernel has no register for a lane index that a read per eight windows needs.
+__device__ __forceinline__ uint32_t lane_fresh() {
+  uint32_t z = 0;
+  asm volatile("" : "+v"(z));
+  return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, z));
+}
+
 // Digits of the recoded c / |d| straight from the hand-off (one dword per eight windows).
 // Lanes past count read all-zero digits (0x88888888): their hand-off positions hold a previous
 // batch's recodings, whose top digit (hs_top_digit) could leave [-8, 8] at this wave's W and
 // index past the lane's table rows.
 struct HsDigitsDev {
   const int4 *p2;
-  uint32_t stride, slot;
+  uint32_t stride, slot0;  // slot0: the position of the wave's lane 0 (wave-uniform)
   bool active;
   __device__ __forceinline__ uint32_t word(int w) const {
-    return active ? reinterpret_cast<const uint32_t *>(p2 + (size_t)(w >> 2) * stride + slot)[w & 3] : 0x88888888u;
+    // a 32-bit word index, its uniform part apart, beside the uniform base: no address of the lane's
+    // own live through the loop.  (The digits are words 0..12, below 4 * stride int4, and a
+    // context's hand-off and slab, ~2.5 KB per slot, bound stride far below 2^28.)
+    const uint32_t u = ((uint32_t)(w >> 2) * stride + slot0) * 4u + (uint32_t)(w & 3);
+    return active ? reinterpret_cast<const uint32_t *>(p2)[u + lane_fresh() * 4u] : 0x88888888u;
   }
   __device__ __forceinline__ uint32_t cword(int w) const { return word(w); }
   __device__ __forceinline__ uint32_t dword(int w) const { return w < 5 ? word(8 + w) : 0x88888888u; }
 };
 
-// Phase 2: the joint radix-4 table of -A and -sign(d) R in the slab (twelve rows per lane), the
-// 3-point Straus sum over the wave's largest window count, B digits from windows 0 and 8 of the
-// radix-2^16 comb (each entry fetched into LDS 16 doublings ahead), identity test.  Every
+// Phase 2: the joint radix-4 table of -A and -sign(d) R (twelve rows per lane: ten in the slab and
+// the two points themselves in LDS, SlabLdsTabJ; radix 16: all twelve in the slab), the 3-point
+// Straus sum over the wave's largest window count, B digits from the two radix-2^26 tables (radix
+// 16: windows 0 and 8 of the radix-2^16 comb), each row fetched into LDS ahead of its addition,
+// identity test.  Every
 // lane of the grid stays to the end (the wave maximum of W is a shuffle reduction); lanes
 // past count run on the identity and store nothing.
-constexpr int kHsWaves = 2;  // waves per SIMD of the half-size main kernel (248 VGPRs at 2)
+constexpr int kHsWaves = 2;  // waves per SIMD of the half-size main kernel (all 256 VGPRs at 2, no scratch)
 // BB: radix of the B windows — 26 (the default: btab, two 2^25-entry tables, ten B additions) or
 // 16 (windows 0 and 8 of the 2^16 comb, sixteen; when the 8.6-GB tables are unavailable).  The
 // hand-off carries e unrecoded (hs_prep_r raw_e); radix 16 recodes it here.
+// LDS per block.  Radix 26: one B-row buffer per wave — BH's row is fetched into it right after
+// BL's take (hs_b26_add), a cached addition (~3k issue cycles) before its own — and the P and Q
+// table rows (SlabLdsTabJ): 32 + 48 = 80 KB, two blocks fill a CU's 160 KB.  Radix 16 (sixteen B
+// steps, each row fetched a whole step ahead): a buffer each for BL and BH, the table in the slab.
+static_assert(kHsBlock == kThreadsPerBlock, "SlabLdsTabJ's lane stride");
+template <int BB>
+struct HsLds;
+template <>
+struct HsLds<26> {
+  int4 bl[kHsBlock / 64][8 * 64];
+  int4 pq[kLdsRowsInt4];
+  __device__ __forceinline__ int4 *bh(uint32_t wv) { return bl[wv]; }
+};
+template <>
+struct HsLds<16> {
+  int4 bl[kHsBlock / 64][8 * 64];
+  int4 bhs[kHsBlock / 64][8 * 64];
+  __device__ __forceinline__ int4 *bh(uint32_t wv) { return bhs[wv]; }
+};
 template <int BB>
 __global__ __launch_bounds__(kHsBlock, kHsWaves) void verify_main_hs_kernel(
     uint32_t base, uint32_t count, const int4 *__restrict__ prep, const int4 *__restrict__ prep2, uint32_t stride,
     int4 *__restrict__ slab, const int4 *__restrict__ btab, uint8_t *__restrict__ out, int zip215) {
-  __shared__ int4 sbl[kHsBlock / 64][8 * 64];
-  __shared__ int4 sbh[kHsBlock / 64][8 * 64];  // BL and BH prefetch into a buffer each
+  __shared__ HsLds<BB> sm;
   const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;  // position in the placed hand-off
   const bool active = slot < count;
   int32_t w[64];
+  // e, R, flags, the signature's slot, A (words 12..63); radix 26 reads e (words 13..20) after the
+  // table build, the kernel's register peak
 #pragma unroll
-  for (int q = 3; q < kPrepHsInt4; q++) {  // e, R, flags, the signature's slot, A (words 12..63)
+  for (int q = BB == 26 ? 5 : 3; q < kPrepHsInt4; q++) {
     const int4 v = active ? prep2[(size_t)q * stride + slot] : make_int4(0, 0, 0, 0);
     w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
   }
   uint32_t er[8];
-#pragma unroll
-  for (int j = 0; j < 8; j++) er[j] = (uint32_t)w[13 + j];
-  if (BB == 16) {
+  if constexpr (BB == 16) {
     uint32_t e[8];
 #pragma unroll
-    for (int j = 0; j < 8; j++) e[j] = er[j];
+    for (int j = 0; j < 8; j++) e[j] = (uint32_t)w[13 + j];
     sc_recode_b<16>(er, e);
   }
   fe Rx, Ry;
@@ -372,14 +494,40 @@ __global__ __launch_bounds__(kHsBlock, kHsWaves) void verify_main_hs_kernel(
   if (W < 29) W = 29;
   if (W > 64) W = 64;
   const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-  const HsDigitsDev ds{prep2, stride, slot, active};
-  SlabTabJ tj{slab, slot};
+  const uint32_t slot0 = blockIdx.x * blockDim.x + ((uint32_t)__builtin_amdgcn_readfirstlane((int)threadIdx.x) & ~63u);
+  const HsDigitsDev ds{prep2, stride, slot0, active};
   // the high table: the second radix-2^26 table, or window 8 (j * 2^128 B) of the 2^16 comb
   const size_t hi = BB == 26 ? (size_t)kB26Entries * kCombEntryInt4 : (size_t)8 * kB16Entries * kCombEntryInt4;
-  BPf<BB> bl{btab, sbl[wv], lane};
-  BPf<BB> bh{btab + hi, sbh[wv], lane};
-  const bool id = verify_main_hsj(ds, (flags & 2) != 0, er, W, A, Rx, Ry, tj, bl, bh, zip215 != 0);
-  if (active) out[base + (uint32_t)w[42]] = ((flags & 1) && id) ? 1 : 0;
+  BPf<BB> bl{btab, sm.bl[wv], lane};
+  BPf<BB> bh{btab + hi, sm.bh(wv), lane};
+  bool id;
+  if constexpr (BB == 26) {
+    SlabLdsTabJ tj{slab + (size_t)blockIdx.x * blockDim.x * (kJointRows * 8), threadIdx.x, sm.pq + threadIdx.x};
+    ge_p3 P, Q;  // verify_main_hsj's steps
+    hs_points(P, Q, (flags & 2) != 0, A, Rx, Ry);
+    build_table_joint(tj, P, Q);
+#pragma unroll
+    for (int q = 3; q < 6; q++) {
+      const int4 v = active ? prep2[(size_t)q * stride + slot0 + lane_fresh()] : make_int4(0, 0, 0, 0);
+      w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; j++) er[j] = (uint32_t)w[13 + j];
+    ge_p2 q;
+    hs_straus_joint(q, ds, er, W, tj, bl, bh);
+    if (zip215) p2_mul8(q);
+    id = p2_is_identity(q);
+  } else {
+    SlabTabJ tj{slab, slot};
+    id = verify_main_hsj(ds, (flags & 2) != 0, er, W, A, Rx, Ry, tj, bl, bh, zip215 != 0);
+  }
+  if (active) {
+    // the verdict bit and the signature's slot once more from the hand-off (word 41, 42), at an
+    // index the compiler cannot match with the first read's: kept from there they cost registers
+    // (spilled ones, with the P and Q rows in LDS) through the whole sum
+    const int4 v = prep2[(size_t)10 * stride + slot0 + lane_fresh()];
+    out[base + (uint32_t)v.z] = ((v.y & 1) && id) ? 1 : 0;
+  }
 }
 
 // Diagnostics (tmed_window_stats): the lattice step's window count W of every lane of the last
@@ -436,6 +584,54 @@ hipError_t launch_test_joint_rows(const uint8_t *a, const uint8_t *r, const uint
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(test_joint_rows_kernel, dim3((n + kHsBlock - 1) / kHsBlock), dim3(kHsBlock), 0, stream, a, r,
                      dneg, n, rows);
+  return hipGetLastError();
+}
+
+// Tests (tmed_test_lds_rows): the same table through the main kernel's accessor (SlabLdsTabJ: rows 1
+// and 5 in the block's LDS array, the others in rows, whose lines 1 and 5 stay as the caller filled
+// them), then every row 0..kJointRows read back through prefetch / take, swap false and true, into
+// out ([i][row][swap][40 int32]: the limbs of Y+X, Y-X, Z, 2dT).
+__global__ __launch_bounds__(kHsBlock) void test_lds_rows_kernel(const uint8_t *__restrict__ a,
+                                                                 const uint8_t *__restrict__ r,
+                                                                 const uint8_t *__restrict__ dneg, uint32_t n,
+                                                                 int4 *__restrict__ rows, int32_t *__restrict__ out) {
+  __shared__ int4 pq[kLdsRowsInt4];
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t aw[8], rw[8];
+  load_row_words(aw, a + 32 * (size_t)i, 2);
+  load_row_words(rw, r + 32 * (size_t)i, 2);
+  ge_p3 A, R, P, Q;
+  ge_frombytes_go(A, aw);
+  ge_frombytes_go(R, rw);
+  hs_points(P, Q, dneg[i] != 0, A, R.X, R.Y);
+  SlabLdsTabJ tj{rows + (size_t)blockIdx.x * blockDim.x * (kJointRows * 8), threadIdx.x, pq + threadIdx.x};
+  build_table_joint(tj, P, Q);
+  int32_t *o = out + (size_t)i * (kJointRows + 1) * 2 * 40;
+#pragma unroll 1
+  for (int j = 0; j <= kJointRows; j++) {
+#pragma unroll 1
+    for (int s = 0; s < 2; s++) {
+      ge_cached c;
+      tj.prefetch(j, s != 0);
+      tj.take(c);
+#pragma unroll
+      for (int l = 0; l < 10; l++) {
+        o[l] = c.YpX.v[l];
+        o[10 + l] = c.YmX.v[l];
+        o[20 + l] = c.Z.v[l];
+        o[30 + l] = c.T2d.v[l];
+      }
+      o += 40;
+    }
+  }
+}
+
+hipError_t launch_test_lds_rows(const uint8_t *a, const uint8_t *r, const uint8_t *dneg, uint32_t n, int4 *rows,
+                                int32_t *out, hipStream_t stream) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(test_lds_rows_kernel, dim3((n + kHsBlock - 1) / kHsBlock), dim3(kHsBlock), 0, stream, a, r, dneg,
+                     n, rows, out);
   return hipGetLastError();
 }
 

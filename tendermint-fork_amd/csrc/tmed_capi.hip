@@ -463,6 +463,33 @@ int tmed_test_joint_rows(tmed_ctx *c, const uint8_t *a, const uint8_t *r, const 
   return rc;
 }
 
+int tmed_test_lds_rows(tmed_ctx *c, const uint8_t *a, const uint8_t *r, const uint8_t *dneg, size_t n, uint8_t *rows,
+                       int32_t *out) {
+  if (!c || !a || !r || !dneg || !rows || !out || n == 0 || n > 65536) return TMED_EINVAL;
+  std::lock_guard<std::mutex> lk(c->mu);
+  (void)hipSetDevice(c->device);
+  uint8_t *d_in = nullptr;  // a (32 n), r (32 n), dneg (n)
+  int4 *d_rows = nullptr;
+  int32_t *d_out = nullptr;
+  const size_t row_bytes = n * kSlabJointSlotBytes, out_bytes = n * 26 * 40 * sizeof(int32_t);
+  hipError_t e = hipMalloc((void **)&d_in, 65 * n);
+  if (e == hipSuccess) e = hipMalloc((void **)&d_rows, row_bytes);
+  if (e == hipSuccess) e = hipMalloc((void **)&d_out, out_bytes);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_in, a, 32 * n, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_in + 32 * n, r, 32 * n, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_in + 64 * n, dneg, n, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_rows, rows, row_bytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess)
+    e = launch_test_lds_rows(d_in, d_in + 32 * n, d_in + 64 * n, (uint32_t)n, d_rows, d_out, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(rows, d_rows, row_bytes, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream);
+  const int rc = finish_call(c, c->stream, e);
+  if (d_in) (void)hipFree(d_in);
+  if (d_rows) (void)hipFree(d_rows);
+  if (d_out) (void)hipFree(d_out);
+  return rc;
+}
+
 // The B tables by the index tmed_test_b_table_entry / tmed_test_table_chain take; false: no
 // such table on this context.
 static bool b_table_plan(const tmed_ctx *c, int table, ChainPlan &p) {

@@ -388,18 +388,21 @@ TMED_HD void hs_b26_digits(int dl[5], int dh[5], const uint32_t er[8]) {
 }
 
 // The B step of position m (radix 2^26): r <- t (p1p1 -> p3) + digit lo + digit hi; leaves the sum
-// in t (p1p1); the next position's rows are fetched into the buffers right after each take.
+// in t (p1p1).  BL and BH may share one prefetch buffer (verify_main_hs_kernel<26>): one row is in
+// flight at a time — this position's high row from the low row's take on (one mixed addition and
+// one conversion ahead of its own take), the next position's low row from the high row's take on.
+// The caller prefetches position 4's low row only.
 template <class BL, class BH>
 TMED_HD void hs_b26_add(ge_p1p1 &t, ge_p3 &r, int m, const int dl[5], const int dh[5], BL &bl, BH &bh) {
   ge_niels nb;
   ge_p1p1_to_p3(r, t);
   bl.take(nb);
-  if (m > 0) bl.prefetch(dl[m - 1] < 0 ? -dl[m - 1] : dl[m - 1]);
+  bh.prefetch(dh[m] < 0 ? -dh[m] : dh[m]);
   niels_apply_sign(nb, dl[m] < 0);
   ge_madd_niels(t, r, nb, false);
   ge_p1p1_to_p3(r, t);
   bh.take(nb);
-  if (m > 0) bh.prefetch(dh[m - 1] < 0 ? -dh[m - 1] : dh[m - 1]);
+  if (m > 0) bl.prefetch(dl[m - 1] < 0 ? -dl[m - 1] : dl[m - 1]);
   niels_apply_sign(nb, dh[m] < 0);
   ge_madd_niels(t, r, nb, false);
 }
@@ -424,8 +427,7 @@ TMED_HD void hs_straus(ge_p2 &out, const DS &ds, const uint32_t er[8], int W, TA
   int d26l[5] = {0, 0, 0, 0, 0}, d26h[5] = {0, 0, 0, 0, 0};
   if (b26) {
     hs_b26_digits(d26l, d26h, er);
-    bl.prefetch(d26l[4] < 0 ? -d26l[4] : d26l[4]);
-    bh.prefetch(d26h[4] < 0 ? -d26h[4] : d26h[4]);
+    bl.prefetch(d26l[4] < 0 ? -d26l[4] : d26l[4]);  // (the high row: hs_b26_add)
   } else {
     const int dl = (int)(el[3] >> 16) - 32768, dh = (int)(eh[3] >> 16) - 32768;
     bl.prefetch(dl < 0 ? -dl : dl);
@@ -533,8 +535,7 @@ TMED_HD void hs_straus_joint(ge_p2 &out, const DS &ds, const uint32_t er[8], int
   int d26l[5] = {0, 0, 0, 0, 0}, d26h[5] = {0, 0, 0, 0, 0};
   if (b26) {
     hs_b26_digits(d26l, d26h, er);
-    bl.prefetch(d26l[4] < 0 ? -d26l[4] : d26l[4]);
-    bh.prefetch(d26h[4] < 0 ? -d26h[4] : d26h[4]);
+    bl.prefetch(d26l[4] < 0 ? -d26l[4] : d26l[4]);  // (the high row: hs_b26_add)
   } else {
     const int dl = (int)(el[3] >> 16) - 32768, dh = (int)(eh[3] >> 16) - 32768;
     bl.prefetch(dl < 0 ? -dl : dl);

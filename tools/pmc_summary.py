@@ -44,6 +44,7 @@ def main():
     out_path, srcs = sys.argv[1], sys.argv[2:]
     acc = collections.defaultdict(lambda: collections.defaultdict(list))
     grid = collections.defaultdict(list)
+    cdur = collections.defaultdict(dict)  # a --pmc pass without a trace beside it: the dispatches' own timestamps
     for f in files(srcs):
         for r in csv.DictReader(open(f)):
             k = short(r["Kernel_Name"])
@@ -51,6 +52,8 @@ def main():
                 continue
             acc[k][r["Counter_Name"]].append(float(r["Counter_Value"]))
             grid[k].append(int(r["Grid_Size"]))
+            if r.get("Start_Timestamp") and r.get("End_Timestamp") and r["Counter_Name"] == "GRBM_GUI_ACTIVE":
+                cdur[k][(f, r["Dispatch_Id"])] = int(r["End_Timestamp"]) - int(r["Start_Timestamp"])
     # dispatch durations from the kernel traces of the same runs (effective clock)
     dur = collections.defaultdict(list)
     for a in srcs:
@@ -59,6 +62,9 @@ def main():
                 k = short(r["Kernel_Name"])
                 if k:
                     dur[k].append(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))
+    for k, v in cdur.items():  # (the durations of the dispatches GRBM_GUI_ACTIVE was counted on)
+        if not dur[k]:
+            dur[k] = [x for x in v.values() if x > 0]
     res = {}
     for k, cs in acc.items():
         d = {c: sum(v) / len(v) for c, v in cs.items()}
