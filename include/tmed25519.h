@@ -322,6 +322,19 @@ int tmed_test_lds_rows(tmed_ctx *ctx, const uint8_t *a, const uint8_t *r, const 
                        uint8_t *rows, int32_t *out);
 
 /*
+ * Tests only (tests/test_gpu_hs_k.py): tmed_verify_batch's generic kernels at a chosen k.  Verifies
+ * n signatures over empty messages as an ordinary generic call of this context would (the latency
+ * kernels up to TMED_GLAT_MAX signatures, the throughput kernels above, the context's main variant
+ * and B radix, its chunks), except that signature i uses k32[i] (32 bytes, little-endian, < L) in
+ * place of SHA-512(R || A || M) mod L: the lattice step, the recodings, e = d S mod L, the window
+ * count and the wave's loop length then follow from a k a test chooses, which no signature can.
+ * zip215 != 0: the throughput kernels with the cofactored test, whatever n.  TMED_EINVAL for a
+ * k >= L.
+ */
+int tmed_test_verify_k(tmed_ctx *ctx, const uint8_t *pubkeys, const uint8_t *sigs, const uint8_t *k32, size_t n,
+                       int zip215, uint8_t *out);
+
+/*
  * Tests only (tests/test_gpu_table_rows.py): the fixed-base tables of B, row by row.  table: 0 the
  * radix-256 comb (32 windows x 129 rows), 1 the radix-2^16 table (32769 rows), 2 the radix-2^16
  * comb (16 x 32769), 3 the two radix-2^26 tables (2 x (2^25 + 1)), 4 the radix-2^24 comb

@@ -409,21 +409,25 @@ inline uint32_t last_chunk_count(uint32_t n, uint32_t chunk) {
 // generic_uses_glat says they run; the caller then skips assemble_votes).
 // rule = TMED_RULE_ZIP215: the exact single check of the half-size path (launch_verify zip215) for
 // every batch size: the latency kernels have no ZIP-215 form and are not taken.
+// test_k (tests only, tmed_test_verify_k): the device's n x 32 bytes of chosen k, used in place of
+// the hashes on whichever route the batch takes; null everywhere else.
 inline int seam_rule(const tmed_ctx *c) { return c->rule.load(std::memory_order_relaxed); }
 inline bool generic_uses_glat(const tmed_ctx *c, uint32_t n, int rule = TMED_RULE_GO) {
   return rule == TMED_RULE_GO && n <= c->glat_max;
 }
 inline hipError_t generic_verify(tmed_ctx *c, const uint8_t *pub, const uint8_t *sig, const uint8_t *msgs,
                                  const uint32_t *off, uint32_t n, uint8_t *out, hipStream_t s, bool msg_slots,
-                                 KernelTimer *timer, const VoteAsm *va = nullptr, int rule = TMED_RULE_GO) {
+                                 KernelTimer *timer, const VoteAsm *va = nullptr, int rule = TMED_RULE_GO,
+                                 const uint8_t *test_k = nullptr) {
   if (generic_uses_glat(c, n, rule)) {
     c->last_hs_count = 0;  // no half-size hand-off in d_prep (tmed_window_stats)
-    return launch_verify_glat(pub, sig, msgs, off, n, out, c->d_bcomb16, c->d_glat, s, msg_slots, timer, va);
+    return launch_verify_glat(pub, sig, msgs, off, n, out, c->d_bcomb16, c->d_glat, s, msg_slots, timer, va,
+                              test_k);
   }
   if (va) return hipErrorInvalidValue;
   hipError_t e = launch_verify(pub, sig, msgs, off, n, out, c->d_slab, c->slab_slots, BTabs{c->d_b16, c->d_bcomb16, c->d_b26},
                                c->d_prep, c->d_fin, c->d_fin_pre, s, c->chunk, c->main_waves, msg_slots, timer,
-                               rule == TMED_RULE_ZIP215);
+                               rule == TMED_RULE_ZIP215, test_k);
   c->last_hs_count = (e != hipSuccess || (c->main_waves == 5 && rule == TMED_RULE_GO)) ? 0 : last_chunk_count(n, c->chunk);
   return e;
 }

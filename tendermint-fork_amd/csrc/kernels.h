@@ -94,11 +94,14 @@ constexpr size_t kBComb16Bytes = 16 * kB16Bytes;
 void host_bcomb16_bases(int32_t out[16 * 40]);
 hipError_t launch_build_bcomb16(const int32_t *d_bases, int4 *comb, hipStream_t stream);
 
+// test_k (tests only, tmed_test_verify_k; null on every product call, which then launches nothing
+// more): n x 32 bytes on the device, signature i's k in place of its hash (test_set_k_kernel
+// after each chunk's verify_prep_kernel).  launch_verify_glat's test_k likewise.
 hipError_t launch_verify(const uint8_t *pub, const uint8_t *sig, const uint8_t *msgs, const uint32_t *off,
                          uint32_t n, uint8_t *out, int4 *slab, uint32_t slab_stride, BTabs btab,
                          int4 *prep, int4 *fin, int4 *fin_pre, hipStream_t stream, uint32_t chunk = 0,
                          int main_waves = 6, bool msg_slots = false, KernelTimer *timer = nullptr,
-                         bool zip215 = false);
+                         bool zip215 = false, const uint8_t *test_k = nullptr);
 
 // The generic prep alone (k, S checks, decode of A) for signatures [base, base + count) into prep
 // slots 0..count-1 (the ZIP-215 batch mode's first phase).
@@ -256,7 +259,8 @@ struct VoteAsm {
 // first (no separate assemble_votes launch in front of the latency kernels).
 hipError_t launch_verify_glat(const uint8_t *pub, const uint8_t *sig, const uint8_t *msgs, const uint32_t *off,
                               uint32_t n, uint8_t *out, const int4 *comb16, int4 *hand, hipStream_t stream,
-                              bool msg_slots = false, KernelTimer *timer = nullptr, const VoteAsm *va = nullptr);
+                              bool msg_slots = false, KernelTimer *timer = nullptr, const VoteAsm *va = nullptr,
+                              const uint8_t *test_k = nullptr);
 
 // f1: on-device CanonicalVote assembly.  Templates are kVoteTmplBytes records
 // ([pre_len, bid_len, cid_len, 0] + bytes); message i is written to out + i * kVoteSlot

@@ -635,6 +635,21 @@ hipError_t launch_test_lds_rows(const uint8_t *a, const uint8_t *r, const uint8_
   return hipGetLastError();
 }
 
+// Tests (tmed_test_verify_k): words 0..7 of the first prep region (int4 rows 0 and 1 at slot, where
+// verify_prep_kernel left k = H(R || A || M) mod L) overwritten with the caller's k of signature
+// base + slot (k32: 32 little-endian bytes a signature, the whole batch's).  Launched between
+// verify_prep_kernel and the chunk's next kernel, which reads k from there.
+__global__ __launch_bounds__(kHsBlock) void test_set_k_kernel(const uint8_t *__restrict__ k32, uint32_t base,
+                                                              uint32_t count, int4 *__restrict__ prep, uint32_t stride) {
+  const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+  if (slot >= count) return;
+  uint32_t k[8];
+  load_row_words(k, k32 + 32 * (size_t)(base + slot), 2);
+#pragma unroll
+  for (int q = 0; q < 2; q++)
+    prep[(size_t)q * stride + slot] = make_int4((int)k[4 * q], (int)k[4 * q + 1], (int)k[4 * q + 2], (int)k[4 * q + 3]);
+}
+
 // (s_sleep 127 is ~8k clocks, ~3.4 us at 2.4 GHz; a bounded loop, no memory access)
 __global__ __launch_bounds__(64) void test_delay_kernel(uint32_t iters) {
   for (uint32_t i = 0; i < iters; i++) __builtin_amdgcn_s_sleep(127);
@@ -778,7 +793,7 @@ hipError_t launch_test_fin_fill(const int32_t *xyz, const uint8_t *r, const uint
 hipError_t launch_verify(const uint8_t *pub, const uint8_t *sig, const uint8_t *msgs, const uint32_t *off,
                          uint32_t n, uint8_t *out, int4 *slab, uint32_t slab_stride, BTabs btab,
                          int4 *prep, int4 *fin, int4 *fin_pre, hipStream_t stream, uint32_t chunk, int main_waves,
-                         bool msg_slots, KernelTimer *timer, bool zip215) {
+                         bool msg_slots, KernelTimer *timer, bool zip215, const uint8_t *test_k) {
   const MsgSrc ms{msgs, off, msg_slots};
   // Chunks of at most slab_stride signatures (the per-lane tables and the prep hand-off are
   // sized for one chunk; tmed_init keeps both multiples of kThreadsPerBlock, so every lane of
@@ -799,6 +814,9 @@ hipError_t launch_verify(const uint8_t *pub, const uint8_t *sig, const uint8_t *
 
       hipLaunchKernelGGL(verify_prep_kernel, dim3(hblocks), dim3(kHsBlock), 0, stream, pub, sig, ms, base,
                          count, prep, slab_stride, hs ? place : nullptr);
+      if (test_k)  // tests only (tmed_test_verify_k): a chosen k in place of the hash
+        hipLaunchKernelGGL(test_set_k_kernel, dim3(hblocks), dim3(kHsBlock), 0, stream, test_k, base, count, prep,
+                           slab_stride);
       if (timer) timer->mark(stream, 0);
       if (hs) {  // default: half-size scalars (verify_hs.h): R decode + lattice, main; no finish
         int4 *prep2 = prep + (size_t)kPrepInt4 * slab_stride;

@@ -247,9 +247,39 @@ __global__ __launch_bounds__(64) void verify_glat_main_kernel(const int4 *__rest
     out[gi] = ((flags & 1u) && ok0 && okR && z0 && z1 && !z2) ? 1 : 0;
 }
 
+// Tests (tmed_test_verify_k): the scalar region of signature i rewritten for the caller's k
+// (k32: 32 little-endian bytes a signature) in place of the hash: hs_scalars(k, S) as the hash lanes
+// of verify_glat_prep_kernel run it, S as verify_prep_comb hands it over (zero when the S checks
+// fail), the same seven int4 (cr, dr, er, flags), bit 0 of the flags (the S verdict) kept.  Launched
+// between the two product kernels.
+__global__ __launch_bounds__(64) void test_glat_set_k_kernel(const uint8_t *__restrict__ sig,
+                                                             const uint8_t *__restrict__ k32, uint32_t n,
+                                                             int4 *__restrict__ hand, uint32_t cap) {
+  const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  int4 *sc = hand + (size_t)kDecInt4 * 2 * cap;
+  const bool ok = (sc[(size_t)6 * cap + i].x & 1) != 0;  // word 24: the flags
+  uint32_t sw[16], k[8], s[8], cr[8], dr[8], er[8];
+  load_row_words(sw, sig + 64 * (size_t)i, 4);
+  load_row_words(k, k32 + 32 * (size_t)i, 2);
+#pragma unroll
+  for (int w = 0; w < 8; w++) s[w] = ok ? sw[8 + w] : 0u;
+  bool dneg;
+  int W;
+  hs_scalars(k, s, cr, dr, er, dneg, W);
+  uint32_t o[28];
+#pragma unroll
+  for (int j = 0; j < 8; j++) { o[j] = cr[j]; o[8 + j] = dr[j]; o[16 + j] = er[j]; }
+  o[24] = (ok ? 1u : 0u) | (dneg ? 2u : 0u) | ((uint32_t)W << 8);
+  o[25] = o[26] = o[27] = 0;
+#pragma unroll
+  for (int q = 0; q < kScInt4; q++)
+    sc[(size_t)q * cap + i] = make_int4((int)o[4 * q], (int)o[4 * q + 1], (int)o[4 * q + 2], (int)o[4 * q + 3]);
+}
+
 hipError_t launch_verify_glat(const uint8_t *pub, const uint8_t *sig, const uint8_t *msgs, const uint32_t *off,
                               uint32_t n, uint8_t *out, const int4 *comb16, int4 *hand, hipStream_t stream,
-                              bool msg_slots, KernelTimer *timer, const VoteAsm *va) {
+                              bool msg_slots, KernelTimer *timer, const VoteAsm *va, const uint8_t *test_k) {
   if (n == 0) return hipSuccess;
   if (n > kGLatMax) return hipErrorInvalidValue;  // the hand-off is sized for kGLatMax signatures
   const MsgSrc ms{msgs, off, msg_slots};
@@ -258,6 +288,8 @@ hipError_t launch_verify_glat(const uint8_t *pub, const uint8_t *sig, const uint
   if (va && !msg_slots) return hipErrorInvalidValue;
   hipLaunchKernelGGL(verify_glat_prep_kernel, dim3(nD + nH), dim3(64), 0, stream, pub, sig, ms, n, nD, hand,
                      kGLatMax, va ? *va : VoteAsm{}, va ? 1 : 0);
+  if (test_k)  // tests only (tmed_test_verify_k): a chosen k in place of the hash
+    hipLaunchKernelGGL(test_glat_set_k_kernel, dim3(nH), dim3(64), 0, stream, sig, test_k, n, hand, kGLatMax);
   if (timer) timer->mark(stream, 0);
   hipLaunchKernelGGL(verify_glat_main_kernel, dim3((n + 7) / 8), dim3(64), 0, stream, hand, n, kGLatMax, comb16, out);
   if (timer) timer->mark(stream, 1);

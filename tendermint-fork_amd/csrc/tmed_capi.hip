@@ -490,6 +490,45 @@ int tmed_test_lds_rows(tmed_ctx *c, const uint8_t *a, const uint8_t *r, const ui
   return rc;
 }
 
+int tmed_test_verify_k(tmed_ctx *c, const uint8_t *pub, const uint8_t *sig, const uint8_t *k32, size_t n, int zip215,
+                       uint8_t *out) {
+  if (!c || !out) return TMED_EINVAL;
+  if (n == 0) return TMED_OK;
+  if (!pub || !sig || !k32 || n > 0xffffffffu) return TMED_EINVAL;
+  // k < L (little-endian bytes against L's, most significant first)
+  static const uint8_t kL[32] = {0xed, 0xd3, 0xf5, 0x5c, 0x1a, 0x63, 0x12, 0x58, 0xd6, 0x9c, 0xf7, 0xa2, 0xde, 0xf9, 0xde, 0x14,
+                                 0,    0,    0,    0,    0,    0,    0,    0,    0,    0,    0,    0,    0,    0,    0,    0x10};
+  for (size_t i = 0; i < n; i++) {
+    int b = 31;
+    while (b >= 0 && k32[32 * i + b] == kL[b]) b--;
+    if (b < 0 || k32[32 * i + b] > kL[b]) return TMED_EINVAL;
+  }
+  std::lock_guard<std::mutex> lk(c->mu);
+  (void)hipSetDevice(c->device);
+  RawStage st;
+  int rc = raw_stage(c, 32, n, 0, st);  // empty messages: every offset 0
+  if (rc != TMED_OK) return rc;
+  memcpy(st.keys, pub, n * 32);
+  memcpy(st.sigs, sig, n * 64);
+  memset(st.off, 0, (n + 1) * 4);
+  uint8_t *d_k = nullptr;
+  hipError_t e = hipMalloc((void **)&d_k, 32 * n);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_k, k32, 32 * n, hipMemcpyHostToDevice, c->stream);
+  if (e != hipSuccess) {
+    rc = finish_call(c, c->stream, e);
+  } else {
+    rc = raw_run(c, st, /*timed=*/false,
+                 [&](const uint8_t *d_pub, const uint8_t *d_sig, const uint8_t *d_msg, const uint32_t *d_off, uint32_t m,
+                     uint8_t *d_out, hipStream_t s) {
+                   return map_err(generic_verify(c, d_pub, d_sig, d_msg, d_off, m, d_out, s, false, nullptr, nullptr,
+                                                 zip215 ? TMED_RULE_ZIP215 : TMED_RULE_GO, d_k));
+                 },
+                 out, nullptr);
+  }
+  if (d_k) (void)hipFree(d_k);
+  return rc;
+}
+
 // The B tables by the index tmed_test_b_table_entry / tmed_test_table_chain take; false: no
 // such table on this context.
 static bool b_table_plan(const tmed_ctx *c, int table, ChainPlan &p) {

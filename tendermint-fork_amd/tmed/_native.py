@@ -129,6 +129,9 @@ def lib() -> ctypes.CDLL:
     if hasattr(l, "tmed_test_lds_rows"):  # (absent from an older library build: A/B runs through TMED_LIB)
         l.tmed_test_lds_rows.restype = I
         l.tmed_test_lds_rows.argtypes = [P, P, P, P, SZ, P, P]
+    if hasattr(l, "tmed_test_verify_k"):  # (likewise)
+        l.tmed_test_verify_k.restype = I
+        l.tmed_test_verify_k.argtypes = [P, P, P, P, SZ, I, P]
     l.tmed_test_b_table_entry.restype = I
     l.tmed_test_b_table_entry.argtypes = [P, I, ctypes.c_uint32, ctypes.c_uint32, P]
     l.tmed_test_table_chain.restype = I
@@ -156,7 +159,7 @@ EXPORTED_SYMBOLS = [
     "tmed_verify_batch", "tmed_verify_batch_device",
     "tmed_sign_batch", "tmed_sign_batch_device", "tmed_last_kernel_ms",
     "tmed_vote_sign_bytes", "tmed_valu_peak", "tmed_verify_commits", "tmed_verify_commits_with",
-    "tmed_test_pool_jitter", "tmed_test_stream_delay", "tmed_test_joint_rows", "tmed_test_lds_rows", "tmed_debug_zero_bits",
+    "tmed_test_pool_jitter", "tmed_test_stream_delay", "tmed_test_joint_rows", "tmed_test_lds_rows", "tmed_test_verify_k", "tmed_debug_zero_bits",
     "tmed_test_b_table_entry", "tmed_test_table_chain", "tmed_test_zip_msm",
     "tmed_test_key_order", "tmed_test_finish", "tmed_test_finish_zip215",
     "tmed_set_rule", "tmed_rule", "tmed_verify_batch_keyset_zip215", "tmed_verify_batch_keyset_zip215_device",

@@ -331,6 +331,21 @@ class Engine:
             raise TmedError(rc, "tmed_window_stats")
         return lh, wh
 
+    def test_verify_k(self, pubs: np.ndarray, sigs: np.ndarray, ks: np.ndarray, zip215: bool = False) -> np.ndarray:
+        """Tests only (tmed_test_verify_k): the generic kernels of this context on n signatures over
+        empty messages, signature i with ks[i] (32 little-endian bytes, < L) in place of its hash."""
+        n = pubs.shape[0]
+        out = np.zeros(n, dtype=np.uint8)
+        if n == 0:
+            return out
+        pubs = np.ascontiguousarray(pubs, dtype=np.uint8).reshape(n, 32)
+        sigs = np.ascontiguousarray(sigs, dtype=np.uint8).reshape(n, 64)
+        ks = np.ascontiguousarray(ks, dtype=np.uint8).reshape(n, 32)
+        rc = lib().tmed_test_verify_k(self._h, _p(pubs), _p(sigs), _p(ks), n, 1 if zip215 else 0, _p(out))
+        if rc != TMED_OK:
+            raise TmedError(rc, "tmed_test_verify_k")
+        return out
+
     def b_window_bits(self) -> int:
         """Radix (bits) of the default path's fixed-base B windows: 26 or 16 (tmed_b_window_bits)."""
         return int(lib().tmed_b_window_bits(self._h))

@@ -258,6 +258,42 @@ void hostsim_verify_batch_hs16(const uint8_t *pub, const uint8_t *sig, const uin
   verify_batch_hs_impl(pub, sig, msgs, off, n, out, wins, nullptr, true);
 }
 
+// The host twin of tmed_test_verify_k (tests/hs_k_cases.py, tests/test_hs_k_host.py): the half-size
+// path over empty messages as verify_batch_hs_impl runs it, with signature i's k taken from k32
+// (32 bytes, little-endian, < L) after verify_prep instead of its hash.  wins (optional): the tight
+// window count of each k; wmin (optional): as above, the wave's loop length; b16: the radix-2^16 B
+// windows; cofactor8: the ZIP-215 form (R decoded like A, [8] times the sum tested).
+void hostsim_verify_hs_k(const uint8_t *pub, const uint8_t *sig, const uint8_t *k32, size_t n, uint8_t *out,
+                         int32_t *wins, const int32_t *wmin, int b16, int cofactor8) {
+  const ge_niels *lo = b16tab().data();
+  const ge_niels *hi = b16hi_tab().data();
+  const ge_p3 *b26 = b26_bases();
+#pragma omp parallel for schedule(dynamic, 16)
+  for (long i = 0; i < (long)n; i++) {
+    HostTab ta, tr;
+    HostBRef<16> bl{lo}, bh{hi};
+    HostB26Ref bl26{&b26[0]}, bh26{&b26[1]};
+    uint32_t pw[8], sw[16], k[8], s[8], er[8];
+    load_words8(pw, pub + 32 * i);
+    load_words8(sw, sig + 64 * i);
+    load_words8(sw + 8, sig + 64 * i + 32);
+    ge_p3 A;
+    const uint8_t empty[16] = {0};
+    const bool ok = verify_prep(pw, sw, empty, 0, k, s, A);
+    load_words8(k, k32 + 32 * i);  // the chosen k in place of the hash
+    bool dneg;
+    fe Rx, Ry;
+    int W, Wl;
+    HsDigits dg;
+    const bool rok = hs_prep_r(k, s, sw, dg.cr, dg.dr, er, dneg, Rx, Ry, Wl, cofactor8 != 0, !b16, &W);
+    const int Wrun = (wmin && wmin[i] > W) ? (wmin[i] > 64 ? 64 : wmin[i]) : W;
+    const bool id = b16 ? verify_main_hs(dg, dneg, er, Wrun, A, Rx, Ry, ta, tr, bl, bh, cofactor8 != 0)
+                        : verify_main_hs(dg, dneg, er, Wrun, A, Rx, Ry, ta, tr, bl26, bh26, cofactor8 != 0);
+    out[i] = ok && rok && id ? 1 : 0;
+    if (wins) wins[i] = W;
+  }
+}
+
 // The lattice step alone: c, |d| (32-byte LE each), dneg, window count (and the tight count).
 int hostsim_halfsize_impl(const uint8_t *k32, uint8_t *c32, uint8_t *d32, int *dneg, int fast, int *tight = nullptr) {
   uint32_t k[8], c[8], dm[8];
@@ -285,8 +321,9 @@ int hostsim_halfsize_tight(const uint8_t *k32, uint8_t *c32, uint8_t *d32, int *
   return hostsim_halfsize_impl(k32, c32, d32, dneg, fast, tight);
 }
 
-// The radix-2^26 digits of e (hs_b26_digits) at a chosen e: the half-size path's e = d S mod L
-// cannot be chosen end to end (tests/test_scalar_edges_host.py).
+// The radix-2^26 digits of e (hs_b26_digits) at a chosen e: no signature chooses the half-size
+// path's e = d S mod L (tests/test_scalar_edges_host.py); hostsim_verify_hs_k above, with k chosen
+// too, runs such an e end to end (tests/hs_k_cases.py family c).
 void hostsim_b26_digits(const uint8_t *e32, int32_t *dl, int32_t *dh) {
   uint32_t er[8];
   load_words8(er, e32);

@@ -3,9 +3,8 @@ verify_main_hs_kernel (the throughput kernels, TMED_GLAT_MAX=0) through tmed_ver
 the oracle's port on small batches around a wave's size — valid signatures of the C2 stream, one
 tuple of every C5 class and the golden edge vectors — a wave mixing window counts 32 and 33, and
 the twelve rows build_table_joint stores per lane (tmed_test_joint_rows) against the host build of
-the same source (tests/native/joint_host.cpp).  The (k, 1) fallback lane (W = 64) has no entry
-point of its own in the library and is covered on the host only (tests/test_joint_table_host.py,
-tests/test_kernel_host.py)."""
+the same source (tests/native/joint_host.cpp).  A wave holding the (k, 1) fallback lane (W = 64),
+which no signature's hash reaches, runs on the device at a chosen k: tests/test_gpu_hs_k.py."""
 import ctypes
 import os
 import subprocess

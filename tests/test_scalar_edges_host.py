@@ -5,7 +5,8 @@ The models reconstruct their scalars; every (radix, window, edge digit) a scalar
 hit by some case (the unreachable ones derived here from L, not taken from the case builder); the
 expected bits agree with the oracle's C port under both rules; the host build of every verify path
 decides each case as the oracle does; hs_b26_digit, whose input e = d S mod L no signature chooses,
-is driven at chosen e."""
+is driven at chosen e (as a digit function here; through the B additions of the half-size sum, with
+k chosen beside the signature, in tests/test_hs_k_host.py and tests/test_gpu_hs_k.py)."""
 import ctypes
 
 import numpy as np
