@@ -2,7 +2,9 @@
 // arguments, take ctx->mu (locked), stage into the context's pinned buffers, queue copies and launches
 // on the context stream, wait for the stream whatever happened (finish_call), map the error.  The raw
 // host batch (keys, signatures, messages in; one byte per signature out) is raw_stage / raw_run, for
-// its three public entries and the votes' host route.  api_guard.h, included here, is the frame's
+// its three public entries and, through slot_batch.h, the host routes of the votes and the evidence.
+// slot_batch.h builds the frame of those two calls on this one (grouping by route and key set, the
+// device-route envelope around finish_call, verify_sigs).  api_guard.h, included here, is the frame's
 // outermost part (guarded); a HIP unit includes this header and has the frame and ctx.h.
 #pragma once
 #include <hip/hip_runtime.h>

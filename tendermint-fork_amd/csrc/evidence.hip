@@ -2,7 +2,11 @@
 // (VerifyDuplicateVote, evidence/verify.go:162-222) and tmed_evidence_hashes
 // (DuplicateVoteEvidence.Hash and EvidenceList.Hash, types/evidence.go:90-103, :431-442).
 // include/tmed25519.h states the calls; evidence_free.h holds the checks and the Bytes() encoder,
-// shared with the host; evidence_host.h the host entries.
+// shared with the host; evidence_host.h the host entries.  What tmed_verify_duplicate_votes shares
+// with tmed_verify_votes lives in slot_rows.h (device: record staging, slot zeroing, the coalesced
+// slot write-out, the key words) and slot_batch.h (host: the grouping by route and key set, the
+// distinct sets, the device-route envelope, the host route's second half, the choice of verifier);
+// the signature helpers are votes_host.h's.
 //
 // evidence_lookup_kernel: GetByAddress, one wavefront per evidence.  The lanes stride over the set's
 // 20-byte addresses, each read as five dwords from the call's packed, 4-byte-aligned address array;
@@ -26,7 +30,7 @@
 // lane encoding at the end, or every lane would scan a whole set alone.
 //
 // The signatures are decided by the commit seam's launchers in their msg_slots mode over the 2n
-// slots (keyset_verify_batch / generic_verify), none of which changes.
+// slots (verify_sigs), none of which changes.
 //
 // evidence_hash_kernel: one lane per evidence, 64 lanes per workgroup.  A lane stages the two VoteRecs
 // and the EvRec, writes Bytes() into its LDS slot (kEvSlotDw = 131 dwords: the 520-byte bound, on an
@@ -38,22 +42,23 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 
-#include <map>
-#include <unordered_map>
+#include <algorithm>
+#include <utility>
 #include <vector>
 
 #include "../../include/tmed25519.h"
-#include "call_frame.h"
 #include "evidence_host.h"
 #include "host_for.h"
 #include "merkle_levels.h"
+#include "slot_batch.h"
+#include "slot_rows.h"
 
 namespace tmed {
 
-constexpr uint32_t kEvLanes = 64;
+constexpr uint32_t kEvLanes = kSlotLanes;
 constexpr uint32_t kEvVoteInt4 = kVoteRecBytes / 16;  // 9
 constexpr uint32_t kEvRecInt4 = kEvRecBytes / 16;     // 4
-constexpr uint32_t kEvSlotInt4 = kVoteSlot / 16;      // 16
+constexpr uint32_t kEvSlotInt4 = kSlotInt4;           // 16
 
 // The inputs and outputs of the lookup and prepare kernels (device pointers).
 struct EvPrep {
@@ -105,19 +110,9 @@ __global__ __launch_bounds__(kEvLanes) void evidence_prepare_kernel(EvPrep p, ui
   __shared__ int4 ob[kEvLanes][2 * kEvSlotInt4];
   const uint32_t lane = threadIdx.x, i0 = blockIdx.x * kEvLanes, i = i0 + lane;
   if (i < n) {
-    {
-      const int4 *src = p.recs + (size_t)i * 2 * kEvVoteInt4;
-      int4 v[2 * kEvVoteInt4];
-#pragma unroll
-      for (int q = 0; q < (int)(2 * kEvVoteInt4); q++) v[q] = src[q];
-#pragma unroll
-      for (int q = 0; q < (int)(2 * kEvVoteInt4); q++) rl[lane][q] = v[q];
-      const int4 *es = p.evs + (size_t)i * kEvRecInt4;
-#pragma unroll
-      for (int q = 0; q < (int)kEvRecInt4; q++) el[lane][q] = es[q];
-    }
-#pragma unroll
-    for (int q = 0; q < (int)(2 * kEvSlotInt4); q++) ob[lane][q] = make_int4(0, 0, 0, 0);
+    lds_stage<2 * kEvVoteInt4>(rl[lane], p.recs + (size_t)i * 2 * kEvVoteInt4);
+    lds_stage<kEvRecInt4>(el[lane], p.evs + (size_t)i * kEvRecInt4);
+    lds_zero<2 * kEvSlotInt4>(ob[lane]);
     const VoteRec *vr[2] = {reinterpret_cast<const VoteRec *>(rl[lane]),
                             reinterpret_cast<const VoteRec *>(rl[lane] + kEvVoteInt4)};
     const EvRec &e = *reinterpret_cast<const EvRec *>(el[lane]);
@@ -129,10 +124,8 @@ __global__ __launch_bounds__(kEvLanes) void evidence_prepare_kernel(EvPrep p, ui
     const int4 *kp = reinterpret_cast<const int4 *>(p.set_pub ? p.set_pub + 32 * v : p.key_pub + 32 * (size_t)kidx);
     int4 k0 = make_int4(0, 0, 0, 0), k1 = k0;
     if (has) { k0 = kp[0]; k1 = kp[1]; }
-    uint8_t pre = ev_prechecks(*vr[0], *vr[1], e, s, has ? found : kEvNone, has ? p.set_pow[v] : 0, [&](uint32_t w[8]) {
-      w[0] = (uint32_t)k0.x; w[1] = (uint32_t)k0.y; w[2] = (uint32_t)k0.z; w[3] = (uint32_t)k0.w;
-      w[4] = (uint32_t)k1.x; w[5] = (uint32_t)k1.y; w[6] = (uint32_t)k1.z; w[7] = (uint32_t)k1.w;
-    });
+    uint8_t pre = ev_prechecks(*vr[0], *vr[1], e, s, has ? found : kEvNone, has ? p.set_pow[v] : 0,
+                               [&](uint32_t w[8]) { key_words(k0, k1, w); });
     // the host sends only requests whose chain ID fits (evidence_host.h device_route); never write past the slot
     if (pre == 0 && s.cid_len > kVoteChainMax) pre = kEvGoPath;
 #pragma unroll 1
@@ -154,14 +147,7 @@ __global__ __launch_bounds__(kEvLanes) void evidence_prepare_kernel(EvPrep p, ui
     p.pre[i] = pre;
   }
   __syncthreads();
-  const uint32_t nslots = 2 * (n - i0 < kEvLanes ? n - i0 : kEvLanes);
-  int4 *dst = reinterpret_cast<int4 *>(p.slots + (size_t)2 * i0 * kVoteSlot);
-  const int4 *src = &ob[0][0];
-#pragma unroll
-  for (uint32_t q = 0; q < 2 * kEvSlotInt4; q++) {
-    const uint32_t c = q * kEvLanes + lane;  // int4 index in the wave's 32-KB run of slots
-    if (c / kEvSlotInt4 < nslots) dst[c] = src[c];
-  }
+  wave_store_slots<2>(&ob[0][0], p.slots, i0, n);
 }
 
 // The inputs and outputs of the hash kernel.
@@ -179,17 +165,8 @@ __global__ __launch_bounds__(kEvLanes) void evidence_hash_kernel(EvHash p, uint3
   __shared__ uint32_t sl[kEvLanes][kEvSlotDw];
   const uint32_t lane = threadIdx.x, i = blockIdx.x * kEvLanes + lane;
   if (i >= n) return;  // a lane touches its own rows of LDS only: no barrier in this kernel
-  {
-    const int4 *src = p.recs + (size_t)i * 2 * kEvVoteInt4;
-    int4 v[2 * kEvVoteInt4];
-#pragma unroll
-    for (int q = 0; q < (int)(2 * kEvVoteInt4); q++) v[q] = src[q];
-#pragma unroll
-    for (int q = 0; q < (int)(2 * kEvVoteInt4); q++) rl[lane][q] = v[q];
-    const int4 *es = p.evs + (size_t)i * kEvRecInt4;
-#pragma unroll
-    for (int q = 0; q < (int)kEvRecInt4; q++) el[lane][q] = es[q];
-  }
+  lds_stage<2 * kEvVoteInt4>(rl[lane], p.recs + (size_t)i * 2 * kEvVoteInt4);
+  lds_stage<kEvRecInt4>(el[lane], p.evs + (size_t)i * kEvRecInt4);
   for (uint32_t q = 0; q < kEvSlotDw; q++) sl[lane][q] = 0;
   const VoteRec &a = *reinterpret_cast<const VoteRec *>(rl[lane]);
   const VoteRec &b = *reinterpret_cast<const VoteRec *>(rl[lane] + kEvVoteInt4);
@@ -227,20 +204,8 @@ namespace {
 
 namespace EH = tmed_evidence_host;
 
-// One group of the call: the requests that share a route and a key set.
-struct EvGroup {
-  bool device;
-  uint64_t keyset;
-  std::vector<size_t> reqs;
-  size_t m = 0;  // evidences
-};
-
-void vote_sig(const tmed_votes &v, size_t i, uint8_t *out) {
-  const uint32_t sl = v.sig_lens ? v.sig_lens[i] : 64;
-  memcpy(out, v.sigs + 64 * i, sl < 64 ? sl : 64);
-  if (sl < 64) memset(out + sl, 0, 64 - sl);
-}
-bool sig_full(const tmed_votes &v, size_t i) { return !v.sig_lens || v.sig_lens[i] == 64; }  // crypto/ed25519/ed25519.go:150-152
+using tmed_votes_host::sig_full;
+using tmed_votes_host::vote_sig;
 
 // Every validator's key-set index of set vs into out; false for one past the key set.
 bool set_key_indexes(const tmed_valset &vs, size_t nkeys, uint32_t *out) {
@@ -252,21 +217,15 @@ bool set_key_indexes(const tmed_valset &vs, size_t nkeys, uint32_t *out) {
   return ok;
 }
 
-// Device route: records, steps and the sets' arrays in, the lookup and the prepare launch, the verify
-// launchers in msg_slots mode, pre-codes, states and validity bits out.
-int run_group_device(tmed_ctx *c, const tmed_dup_request *reqs, const size_t *base, const EvGroup &g, Keyset *ks,
+// Device route (slot_batch.h slot_batch_device): records, steps and the sets' arrays in, the lookup
+// and the prepare launch, pre-codes, states and validity bits out.
+int run_group_device(tmed_ctx *c, const tmed_dup_request *reqs, const size_t *base, const SlotGroup &g, Keyset *ks,
                      uint8_t *codes) {
   const int rule = seam_rule(c);  // ctx->mu is held from the call's entry: one value for all its groups
   const size_t m = g.m, G = g.reqs.size();
-  std::unordered_map<const tmed_valset *, uint64_t> abase;  // each distinct set once
-  std::vector<const tmed_valset *> asets;
-  size_t n_addr = 0;
-  for (const size_t q : g.reqs)
-    if (abase.emplace(reqs[q].vals, n_addr).second) {
-      asets.push_back(reqs[q].vals);
-      n_addr += reqs[q].vals->n;
-    }
-  const size_t kb = ks ? 4 : 32;
+  SetTable sets;
+  for (const size_t q : g.reqs) sets.add(reqs[q].vals);
+  const size_t kb = ks ? 4 : 32, n_addr = sets.n_vals;
   const size_t o_rec = 0, o_ev = align256(o_rec + 2 * m * kVoteRecBytes), o_step = align256(o_ev + m * kEvRecBytes),
                o_addr = align256(o_step + G * sizeof(EvStep)), o_pow = align256(o_addr + 20 * n_addr),
                o_setkey = align256(o_pow + 8 * n_addr), o_sig = align256(o_setkey + kb * n_addr),
@@ -283,14 +242,14 @@ int run_group_device(tmed_ctx *c, const tmed_dup_request *reqs, const size_t *ba
   std::vector<size_t> start(G);
   for (size_t j = 0; j < G; j++) {
     const tmed_dup_request &rq = reqs[g.reqs[j]];
-    EH::fill_step(rq, abase.find(rq.vals)->second, steps[j]);
+    EH::fill_step(rq, sets.at(rq.vals), steps[j]);
     start[j] = at;
     at += rq.ev->n;
   }
   bool keys_ok = true;
-  for (const tmed_valset *vs : asets) {
+  for (const tmed_valset *vs : sets.sets) {
     if (!vs->n) continue;
-    const uint64_t b = abase[vs];
+    const uint64_t b = sets.at(vs);
     memcpy(h + o_addr + 20 * b, vs->addresses, 20 * vs->n);
     memcpy(h + o_pow + 8 * b, vs->powers, 8 * vs->n);
     if (ks) keys_ok = set_key_indexes(*vs, ks->n, reinterpret_cast<uint32_t *>(h + o_setkey) + b) && keys_ok;
@@ -308,46 +267,28 @@ int run_group_device(tmed_ctx *c, const tmed_dup_request *reqs, const size_t *ba
       vote_sig(ev.votes, 2 * i + 1, h + o_sig + 64 * (2 * k + 1));
     }
   });
-  hipStream_t s = c->stream;
-  e = hipMemcpyAsync(d, h, o_found, hipMemcpyHostToDevice, s);  // one copy in
-  if (e == hipSuccess) e = scratch_acquire(c, s);
-  const bool acquired = e == hipSuccess;
   const EvPrep p{reinterpret_cast<const int4 *>(d + o_rec), reinterpret_cast<const int4 *>(d + o_ev),
                  reinterpret_cast<const EvStep *>(d + o_step), d + o_addr, reinterpret_cast<const int64_t *>(d + o_pow),
                  ks ? reinterpret_cast<const uint32_t *>(d + o_setkey) : nullptr, ks ? nullptr : d + o_setkey,
                  ks ? ks->d_pub : nullptr, reinterpret_cast<uint32_t *>(d + o_found), d + o_key, d + o_slot,
                  reinterpret_cast<uint32_t *>(d + o_len), d + o_pre, d + o_state};
-  if (e == hipSuccess) e = hipEventRecord(c->ev0, s);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(evidence_lookup_kernel, dim3((uint32_t)m), dim3(kEvLanes), 0, s, p, (uint32_t)m);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipEventRecord(c->ev_lookup, s);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(evidence_prepare_kernel, dim3((uint32_t)((m + kEvLanes - 1) / kEvLanes)), dim3(kEvLanes), 0, s, p,
-                       (uint32_t)m);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipEventRecord(c->vote_ev, s);
-  if (e == hipSuccess) {
-    const uint32_t *lens = reinterpret_cast<const uint32_t *>(d + o_len);
-    e = ks ? keyset_verify_batch(c, *ks, reinterpret_cast<const uint32_t *>(d + o_key), d + o_sig, d + o_slot, lens,
-                                 (uint32_t)(2 * m), d + o_valid, s, /*msg_slots=*/true, rule)
-           : generic_verify(c, d + o_key, d + o_sig, d + o_slot, lens, (uint32_t)(2 * m), d + o_valid, s,
-                            /*msg_slots=*/true, nullptr, nullptr, rule);
-  }
-  if (e == hipSuccess) e = hipEventRecord(c->ev1, s);
-  if (acquired) {
-    const hipError_t er = scratch_release(c, s);
-    if (e == hipSuccess) e = er;
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(h + o_found, d + o_found, o_key - o_found, hipMemcpyDeviceToHost, s);
-  float ms = 0.f, lms = 0.f, pms = 0.f;
-  const int rc = finish_call(c, s, e, &ms);
+  const int rc = slot_batch_device(
+      c, o_found, o_found, o_key,
+      [&](hipStream_t s) {
+        hipLaunchKernelGGL(evidence_lookup_kernel, dim3((uint32_t)m), dim3(kEvLanes), 0, s, p, (uint32_t)m);
+        hipError_t el = hipGetLastError();
+        if (el == hipSuccess) el = hipEventRecord(c->ev_lookup, s);
+        if (el != hipSuccess) return el;
+        hipLaunchKernelGGL(evidence_prepare_kernel, dim3((uint32_t)((m + kEvLanes - 1) / kEvLanes)), dim3(kEvLanes), 0, s, p,
+                           (uint32_t)m);
+        el = hipGetLastError();
+        return el == hipSuccess ? hipEventRecord(c->vote_ev, s) : el;
+      },
+      SlotSigs{ks, d + o_key, d + o_sig, d + o_slot, p.lens, (uint32_t)(2 * m), d + o_valid, rule});
   if (rc != TMED_OK) return rc;
+  float lms = 0.f, pms = 0.f;
   (void)hipEventElapsedTime(&lms, c->ev0, c->ev_lookup);
   (void)hipEventElapsedTime(&pms, c->ev_lookup, c->vote_ev);
-  c->last_ms += ms;
   c->last_ev_ms[0] += lms;
   c->last_ev_ms[1] += pms;
   for (size_t j = 0; j < G; j++) {
@@ -362,76 +303,56 @@ int run_group_device(tmed_ctx *c, const tmed_dup_request *reqs, const size_t *ba
   return TMED_OK;
 }
 
-// Host route (a chain ID past kVoteChainMax): lookup, checks and messages by the same source on the
-// host, the messages packed behind each other, the verify launchers in their offset mode.
-int run_group_host(tmed_ctx *c, const tmed_dup_request *reqs, const size_t *base, const EvGroup &g, Keyset *ks,
+// Host route (a chain ID past kVoteChainMax; slot_batch.h slot_batch_host): lookup, checks and
+// messages by the same source on the host, the messages packed behind each other.
+int run_group_host(tmed_ctx *c, const tmed_dup_request *reqs, const size_t *base, const SlotGroup &g, Keyset *ks,
                    uint8_t *codes) {
-  const int rule = seam_rule(c);
   const size_t m = g.m;
   std::vector<EH::HostLane> lanes(m);
-  std::vector<uint8_t> valid(2 * m), msgs;
-  std::vector<uint32_t> off(2 * m + 1);
-  size_t k = 0, pos = 0;
+  std::vector<uint8_t> valid(2 * m);
+  std::vector<std::pair<size_t, size_t>> src(m);  // evidence k: its request and its index there
+  MsgPack mp;
+  size_t k = 0;
   for (const size_t q : g.reqs) {
     const tmed_dup_evidence &ev = *reqs[q].ev;
     EH::request_lanes_host(reqs[q], lanes.data() + k);
-    for (size_t i = 0; i < ev.n; i++, k++)
+    for (size_t i = 0; i < ev.n; i++, k++) {
+      src[k] = {q, i};
       for (size_t w = 0; w < 2; w++) {
-        off[2 * k + w] = (uint32_t)pos;
-        const size_t len = lanes[k].len[w];
-        if (!len) continue;
+        if (!lanes[k].len[w]) {
+          mp.skip();
+          continue;
+        }
         VoteRec r;
         tmed_votes_host::fill_rec(ev.votes, 2 * i + w, 0, 0, r);
-        if (pos + len > 0xffffffffu) return TMED_EINVAL;
-        msgs.resize(pos + len);
-        vote_free_write(r, (const uint8_t *)reqs[q].chain_id, reqs[q].chain_id_len, msgs.data() + pos);
-        pos += len;
-      }
-  }
-  off[2 * m] = (uint32_t)pos;
-  RawStage st;
-  int rc = raw_stage(c, ks ? 4 : 32, 2 * m, pos, st);
-  if (rc != TMED_OK) return rc;
-  k = 0;
-  for (const size_t q : g.reqs) {
-    const tmed_dup_evidence &ev = *reqs[q].ev;
-    const tmed_valset &vs = *reqs[q].vals;
-    for (size_t i = 0; i < ev.n; i++, k++) {
-      const uint32_t f = lanes[k].found;
-      for (size_t w = 0; w < 2; w++) {
-        if (ks) {
-          const uint32_t key = f == kEvNone ? 0 : vs.keyset_index ? vs.keyset_index[f] : f;
-          if (key >= ks->n) return TMED_EINVAL;
-          ((uint32_t *)st.keys)[2 * k + w] = key;
-        } else if (f == kEvNone) {
-          memset(st.keys + 32 * (2 * k + w), 0, 32);
-        } else {
-          memcpy(st.keys + 32 * (2 * k + w), vs.pubkeys + 32 * (size_t)f, 32);
-        }
-        vote_sig(ev.votes, 2 * i + w, st.sigs + 64 * (2 * k + w));
+        uint8_t *msg = mp.next(lanes[k].len[w]);
+        if (!msg) return TMED_EINVAL;
+        vote_free_write(r, (const uint8_t *)reqs[q].chain_id, reqs[q].chain_id_len, msg);
       }
     }
   }
-  if (pos) memcpy(st.msgs, msgs.data(), pos);
-  memcpy(st.off, off.data(), (2 * m + 1) * 4);
-  rc = raw_run(c, st, /*timed=*/true,
-               [&](const uint8_t *d_key, const uint8_t *d_sig, const uint8_t *d_msg, const uint32_t *d_off, uint32_t n,
-                   uint8_t *d_out, hipStream_t s) {
-                 return map_err(ks ? keyset_verify_batch(c, *ks, (const uint32_t *)d_key, d_sig, d_msg, d_off, n, d_out, s,
-                                                         /*msg_slots=*/false, rule)
-                                   : generic_verify(c, d_key, d_sig, d_msg, d_off, n, d_out, s, /*msg_slots=*/false, nullptr,
-                                                    nullptr, rule));
-               },
-               valid.data(), nullptr);
+  const int rc = slot_batch_host(
+      c, ks, seam_rule(c), mp,
+      [&](size_t j, uint8_t *out) {  // both votes' key: the found validator's (key 0, or zeros, for nobody)
+        const tmed_valset &vs = *reqs[src[j / 2].first].vals;
+        const uint32_t f = lanes[j / 2].found;
+        if (ks) {
+          const uint32_t key = f == kEvNone ? 0 : vs.keyset_index ? vs.keyset_index[f] : f;
+          *reinterpret_cast<uint32_t *>(out) = key;
+          return key < ks->n;
+        }
+        if (f == kEvNone) memset(out, 0, 32);
+        else memcpy(out, vs.pubkeys + 32 * (size_t)f, 32);
+        return true;
+      },
+      [&](size_t j, uint8_t *out) { vote_sig(reqs[src[j / 2].first].ev->votes, 2 * src[j / 2].second + j % 2, out); },
+      valid.data());
   if (rc != TMED_OK) return rc;
-  c->last_ms += st.ms;
-  k = 0;
-  for (const size_t q : g.reqs) {
+  for (k = 0; k < m; k++) {
+    const size_t q = src[k].first, i = src[k].second;
     const tmed_votes &v = reqs[q].ev->votes;
-    uint8_t *out = codes + base[q];
-    for (size_t i = 0; i < reqs[q].ev->n; i++, k++)
-      out[i] = ev_outcome(lanes[k].pre, lanes[k].state[0], valid[2 * k] && sig_full(v, 2 * i), lanes[k].state[1],
-                          valid[2 * k + 1] && sig_full(v, 2 * i + 1));
+    codes[base[q] + i] = ev_outcome(lanes[k].pre, lanes[k].state[0], valid[2 * k] && sig_full(v, 2 * i), lanes[k].state[1],
+                                    valid[2 * k + 1] && sig_full(v, 2 * i + 1));
   }
   return TMED_OK;
 }
@@ -439,35 +360,15 @@ int run_group_host(tmed_ctx *c, const tmed_dup_request *reqs, const size_t *base
 }  // namespace
 
 int verify_dup_votes_locked(tmed_ctx *c, const tmed_dup_request *reqs, size_t n, uint8_t *codes) {
-  std::vector<size_t> base(n + 1, 0);
-  std::map<std::pair<bool, uint64_t>, EvGroup> groups;
-  for (size_t q = 0; q < n; q++) {
-    base[q + 1] = base[q] + reqs[q].ev->n;
-    if (reqs[q].ev->n == 0) continue;
-    const bool dev = EH::device_route(reqs[q]);
-    EvGroup &g = groups[{!dev, reqs[q].vals->keyset}];
-    g.device = dev;
-    g.keyset = reqs[q].vals->keyset;
-    g.reqs.push_back(q);
-    g.m += reqs[q].ev->n;
-  }
   c->last_ms = 0.f;
   c->last_ev_ms[0] = c->last_ev_ms[1] = 0.f;
   (void)hipSetDevice(c->device);
-  for (auto &kv : groups) {
-    const EvGroup &g = kv.second;
-    if (g.m > 0x3fffffffu) return TMED_EINVAL;
-    Keyset *ks = nullptr;
-    if (g.keyset) {
-      auto it = c->keysets.find(g.keyset);
-      if (it == c->keysets.end()) return TMED_ENOKEYSET;
-      ks = &it->second;
-    }
-    const int rc = g.device ? run_group_device(c, reqs, base.data(), g, ks, codes)
-                            : run_group_host(c, reqs, base.data(), g, ks, codes);
-    if (rc != TMED_OK) return rc;
-  }
-  return TMED_OK;
+  return run_slot_groups(
+      c, n, 0x3fffffffu, [&](size_t q) { return (size_t)reqs[q].ev->n; }, [&](size_t q) { return EH::device_route(reqs[q]); },
+      [&](size_t q) { return reqs[q].vals->keyset; },
+      [&](const SlotGroup &g, Keyset *ks, const size_t *base) {
+        return g.device ? run_group_device(c, reqs, base, g, ks, codes) : run_group_host(c, reqs, base, g, ks, codes);
+      });
 }
 
 namespace {

@@ -102,11 +102,8 @@ inline void lane_host(const tmed_dup_request &q, const EvStep &s, const VoteRec 
   const tmed_valset &vs = *q.vals;
   const uint32_t found = lookup_host(vs, va, r);
   out.found = found;
-  out.pre = tmed::ev_prechecks(va, vb, r, s, found, found == tmed::kEvNone ? 0 : vs.powers[found], [&](uint32_t w[8]) {
-    const uint8_t *k = vs.pubkeys + 32 * (size_t)found;
-    for (int j = 0; j < 8; j++)
-      w[j] = (uint32_t)k[4 * j] | ((uint32_t)k[4 * j + 1] << 8) | ((uint32_t)k[4 * j + 2] << 16) | ((uint32_t)k[4 * j + 3] << 24);
-  });
+  out.pre = tmed::ev_prechecks(va, vb, r, s, found, found == tmed::kEvNone ? 0 : vs.powers[found],
+                               [&](uint32_t w[8]) { tmed_votes_host::key_words(vs.pubkeys + 32 * (size_t)found, w); });
   const VoteRec *vr[2] = {&va, &vb};
   for (int k = 0; k < 2; k++) {
     out.state[k] = tmed::ev_vote_state(*vr[k]);

@@ -22,6 +22,7 @@
 #include "verify_hs.h"
 #include "kernel_util.h"
 #include "rows.h"
+#include "slot_rows.h"
 #include "votes_dev.h"
 
 namespace tmed {
@@ -259,29 +260,20 @@ __global__ __launch_bounds__(kHsBlock, kPrepWaves) void verify_prep_kernel(
 // (votes_dev.h assemble_vote_into: vote_wire.h's vote_splice on the staged template; this kernel
 // serves the throughput and key-cached paths, the latency kernels assemble in their hash lanes.)  One wave per block: every lane assembles its
 // vote in LDS (byte stores to LDS, beside its staged template), then the wave writes its 64
-// consecutive 256-B slots as sixteen coalesced 1-KB rows.  Assembled straight into the global
-// slots, each lane's ~114 byte stores went to 64 different lines per instruction: 0.29 ms per
-// 853k-vote blocksync batch (profiles/r03/fin2/kernel_stats.csv).
-constexpr uint32_t kAsmLanes = 64;
+// consecutive 256-B slots as sixteen coalesced 1-KB rows (slot_rows.h wave_store_slots, which
+// records what stores straight into the global slots cost).
+constexpr uint32_t kAsmLanes = kSlotLanes;
 __global__ __launch_bounds__(kAsmLanes) void assemble_votes_kernel(VoteAsm va, uint32_t n, uint8_t *__restrict__ out,
                                                                   uint32_t *__restrict__ out_len) {
   __shared__ int4 tl[kAsmLanes][kVoteTmplBytes / 16];
   __shared__ int4 ob[kAsmLanes][kVoteSlot / 16];
   const uint32_t lane = threadIdx.x, i0 = blockIdx.x * kAsmLanes, i = i0 + lane;
   if (i < n) {
-#pragma unroll
-    for (int q = 0; q < (int)(kVoteSlot / 16); q++) ob[lane][q] = make_int4(0, 0, 0, 0);
+    lds_zero<kSlotInt4>(ob[lane]);
     out_len[i] = assemble_vote_into(va, i, reinterpret_cast<uint8_t *>(ob[lane]), tl[lane]);
   }
   __syncthreads();
-  const uint32_t nslots = n - i0 < kAsmLanes ? n - i0 : kAsmLanes;
-  int4 *dst = reinterpret_cast<int4 *>(out + (size_t)i0 * kVoteSlot);
-  const int4 *src = &ob[0][0];
-#pragma unroll
-  for (uint32_t q = 0; q < kVoteSlot / 16; q++) {
-    const uint32_t c = q * kAsmLanes + lane;  // int4 index in the wave's 16-KB run of slots
-    if (c / (kVoteSlot / 16) < nslots) dst[c] = src[c];
-  }
+  wave_store_slots<1>(&ob[0][0], out, i0, n);
 }
 
 // Phase 2 of the full-length fallback (TMED_MAIN_WAVES=5): table of -A, Straus [k](-A) + [s]B

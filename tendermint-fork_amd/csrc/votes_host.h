@@ -47,6 +47,21 @@ inline int check_request(const tmed_vote_request &r) {
 
 inline uint8_t clip_len(uint32_t len) { return (uint8_t)(len > 255 ? 255 : len); }
 
+// The reference's length rule: a signature whose length is not 64 is rejected (crypto/ed25519/ed25519.go:150-152).
+inline bool sig_full(const tmed_votes &v, size_t i) { return !v.sig_lens || v.sig_lens[i] == 64; }
+// Vote i's signature as the verify kernels read it: 64 bytes, a shorter one padded with zeros.
+inline void vote_sig(const tmed_votes &v, size_t i, uint8_t *out) {
+  const uint32_t sl = v.sig_lens ? v.sig_lens[i] : 64;
+  memcpy(out, v.sigs + 64 * i, sl < 64 ? sl : 64);
+  if (sl < 64) memset(out + sl, 0, 64 - sl);
+}
+// A key's 32 bytes as the eight little-endian words the address check hashes (the device twin:
+// slot_rows.h key_words).
+inline void key_words(const uint8_t *k, uint32_t w[8]) {
+  for (int j = 0; j < 8; j++)
+    w[j] = (uint32_t)k[4 * j] | ((uint32_t)k[4 * j + 1] << 8) | ((uint32_t)k[4 * j + 2] << 16) | ((uint32_t)k[4 * j + 3] << 24);
+}
+
 // The fields VoteSignBytes reads of vote i.
 inline void fill_sign_fields(const tmed_votes &v, size_t i, VoteRec &r) {
   memset(&r, 0, sizeof(r));
@@ -70,7 +85,7 @@ inline void fill_rec(const tmed_votes &v, size_t i, uint32_t req, uint32_t key, 
   r.addr_len = clip_len(al);
   memcpy(r.addr, v.addresses + 20 * i, al < 20 ? al : 20);
   r.val_index = v.validator_indexes[i];
-  r.sig_full = !v.sig_lens || v.sig_lens[i] == 64;
+  r.sig_full = sig_full(v, i);
   r.key = key;
   r.req = req;
 }
@@ -100,12 +115,7 @@ void request_prechecks_host(const tmed_vote_request &q, uint8_t *codes);
 // Checks 1-7 of vote i of request q on the host (the key read from the request's set).
 inline uint8_t precheck_host(const tmed_vote_request &q, const VoteStep &s, const VoteRec &r) {
   const tmed_valset &vs = *q.vals;
-  return tmed::vote_prechecks(r, s, vs.addresses, [&](uint32_t w[8]) {
-    uint8_t k[32];
-    memcpy(k, vs.pubkeys + 32 * (size_t)r.val_index, 32);
-    for (int j = 0; j < 8; j++)
-      w[j] = (uint32_t)k[4 * j] | ((uint32_t)k[4 * j + 1] << 8) | ((uint32_t)k[4 * j + 2] << 16) | ((uint32_t)k[4 * j + 3] << 24);
-  });
+  return tmed::vote_prechecks(r, s, vs.addresses, [&](uint32_t w[8]) { key_words(vs.pubkeys + 32 * (size_t)r.val_index, w); });
 }
 
 // The checks of every vote of request q, codes[i] for vote i.

@@ -168,6 +168,47 @@ def test_long_chain_id_beside_a_device_request(engine, main):
         engine.keyset_free(h)
 
 
+def test_four_groups_interleaved_in_one_call(engine):
+    """One call whose requests alternate over all four (route, key set) groups, every group owning
+    non-adjacent requests: keyed-device, generic-host (a 51-byte chain ID), generic-device, keyed-host, and
+    the four once more with the other set.  Two sets share one key set, so every group packs two distinct
+    sets behind each other.  The codes land at each request's prefix sum, and each request alone gives the
+    same codes."""
+    long_chain = "c" * 51
+    va, sa = EC.valset(9, "evmain", wrong_address_at=7)
+    sets = [(EC.repeated(va, 2, 5), sa), EC.valset(6, "evgrp", wrong_address_at=1)]
+    corpus = {(si, chain): [e for _, e in EC.check_cases(chain, vs, seeds, "g%d" % si)]
+              for si, (vs, seeds) in enumerate(sets) for chain in (EC.CHAIN, long_chain)}
+    h = engine.keyset_load(np.concatenate([vs.packed()[0][:len(vs.validators)] for vs, _ in sets]))
+    try:
+        first = [0, len(sets[0][0].validators)]
+        keyed = [T.ValidatorSet(vs.validators, keyset=h, keyset_index=np.arange(len(vs.validators), dtype=np.uint32) + b)
+                 for (vs, _), b in zip(sets, first)]
+        # (set, keyed, chain): keyed-dev, generic-host, generic-dev, keyed-host, and again with the other set
+        plan = [(0, True, EC.CHAIN), (0, False, long_chain), (1, False, EC.CHAIN), (1, True, long_chain),
+                (0, False, EC.CHAIN), (1, True, EC.CHAIN), (1, False, long_chain), (0, True, long_chain)]
+        reqs = []
+        for j, (si, is_keyed, chain) in enumerate(plan):
+            cs = corpus[si, chain]
+            ev = cs[:1] + cs[1 + j::8][:4 + j % 3]  # the valid evidence and every eighth case from 1 + j
+            reqs.append(EV.EvidenceRequest(chain, keyed[si] if is_keyed else sets[si][0], ev))
+        exp = [[EC.expected(r, e) for e in r.evidence] for r in reqs]
+        assert len({len(x) for x in exp}) > 1 and all(x[0] == 0 and len(set(x)) >= 3 for x in exp)
+        pe = EV.PreparedEvidence(reqs)
+        pe.run(None)
+        assert list(pe.device_route[:8]) == [1, 0, 1, 0, 1, 1, 0, 0]
+        got = EV.verify_duplicate_votes(engine, reqs)
+        off = 0
+        for r, x in zip(reqs, exp):
+            _check(got[off:off + len(x)], x)
+            off += len(x)
+        assert off == len(got)
+        for r, x in zip(reqs, exp):
+            _check(EV.verify_duplicate_votes(engine, [r]), x)
+    finally:
+        engine.keyset_free(h)
+
+
 # ----------------------------------------------------------------------------- the lookup
 
 @pytest.fixture(scope="module")

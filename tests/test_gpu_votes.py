@@ -148,6 +148,49 @@ def test_two_requests_and_a_long_chain_id(engine):
         _check(V.verify_votes(engine, [r]), e)
 
 
+def test_four_groups_interleaved_in_one_call(engine):
+    """One call whose requests alternate over all four (route, key set) groups, every group owning
+    non-adjacent requests: keyed-device, generic-host (a 51-byte chain ID), generic-device, keyed-host, and
+    the four once more.  Two sets share one key set (and, on the generic route, one group), one request is
+    Vote.Verify alone (no ADDVOTE: its set's addresses are not staged).  The codes land at each request's
+    prefix sum, and each request alone gives the same codes."""
+    sets = [VC.valset(4, "grp-a"), VC.valset(7, "grp-b", wrong_address_at=2)]
+    long_chain = "c" * 51
+    h = engine.keyset_load(np.concatenate([vs.packed()[0][:len(vs.validators)] for vs, _ in sets]))
+    try:
+        first = [0, len(sets[0][0].validators)]
+        keyed = [T.ValidatorSet(vs.validators, keyset=h, keyset_index=np.arange(len(vs.validators), dtype=np.uint32) + b)
+                 for (vs, _), b in zip(sets, first)]
+        # (set, keyed, chain): keyed-dev, generic-host, generic-dev, keyed-host, and again with the other set
+        plan = [(0, True, VC.CHAIN), (0, False, long_chain), (1, False, VC.CHAIN), (1, True, long_chain),
+                (0, False, "other-chain"), (1, True, VC.CHAIN), (1, False, long_chain), (0, True, long_chain)]
+        reqs = []
+        for j, (si, is_keyed, chain) in enumerate(plan):
+            vs, seeds = sets[si]
+            vals = keyed[si] if is_keyed else vs
+            if j == 4:  # Vote.Verify alone
+                reqs.append(V.VoteRequest(chain, vals, [v for _, v in VC.verify_cases(chain, vs, seeds, "g4")[4::3]]))
+                continue
+            cs = VC.step_cases(chain, vs, seeds, 1 + j % 2, height=20 + j, round_=j, tag="g%d" % j)
+            votes = [v for _, v in cs[:1] + cs[1 + j::5][:4 + j % 3]]  # the valid vote and every fifth class from 1 + j
+            reqs.append(V.VoteRequest(chain, vals, votes, True, 20 + j, j, 1 + j % 2))
+        exp = [[VC.expected(r, v) for v in r.votes] for r in reqs]
+        assert len({len(e) for e in exp}) > 1 and all(V.VOTE_OK in e and len(set(e)) >= 3 for e in exp)
+        pv = V.PreparedVotes(reqs)
+        pv.run(None)
+        assert list(pv.device_route[:8]) == [1, 0, 1, 0, 1, 1, 0, 0]
+        got = V.verify_votes(engine, reqs)
+        off = 0
+        for r, e in zip(reqs, exp):
+            _check(got[off:off + len(r.votes)], e)
+            off += len(r.votes)
+        assert off == len(got)
+        for r, e in zip(reqs, exp):
+            _check(V.verify_votes(engine, [r]), e)
+    finally:
+        engine.keyset_free(h)
+
+
 def test_commit_turned_into_votes(engine):
     """Commit.GetVote (types/block.go:784-796) of a 175-signature commit: every vote OK, equal to
     verify_batch's bits on the same (key, sign-bytes, signature) tuples; one flipped signature gives
