@@ -33,6 +33,11 @@
                 tmed_verify_votes over the 2n votes; tmed_evidence_bytes, then tmed_merkle_roots), in one run, once
                 both routes agree on every code and root: evidences/s, the lookup, prepare and leaf-stage kernels'
                 device time, the calls' host share.
+  --config lca   light-client-attack evidence: E lunatic evidences x V validators (default 1x10000 and
+                 50x175; every common validator signs the conflicting block): one
+                 tmed_verify_light_client_attacks call against the route there was before:
+                 tmed_verify_commits on the Trusting + Light pairs, tmed_header_hashes on the 2E
+                 headers, tmed_byzantine_validators_host on one thread.
 Synthetic data (seeded keys, GPU RFC 8032 signer); prints one JSON line per config.
 """
 from __future__ import annotations
@@ -1303,6 +1308,96 @@ def evidence(eng, runs: int, shapes=("2048x10000", "1000x4x175")):
             "runs": runs, "shapes": out}
 
 
+def lca(eng, runs: int, shapes=("1x10000", "50x175")):
+    """Light-client-attack evidence per shape ExV: E lunatic evidences against one V-validator set (common and
+    conflicting set alike: every common validator signs the conflicting block), each with its own conflicting
+    header and commit, commonHeader at another height (so VerifyCommitLightTrusting runs beside
+    VerifyCommitLight), the claimed list = all V validators in the reference's order.
+      new   one tmed_verify_light_client_attacks call;
+      old   tmed_verify_commits over the 2E commit requests, tmed_header_hashes over the 2E headers,
+            tmed_byzantine_validators_host (GetByAddress as a scan per signature and a sort, one host thread).
+    The seam's key-set cache is on and warm for both.  Both routes must agree (every code OK, equal lists)
+    before anything is timed.  Medians of `runs` timed calls."""
+    import tmed.evidence as EV
+    import tmed.merkle as MK
+    import tmed.types as T
+    from tmed.workload import make_valset, pubkeys_of, seeds_from_tag, sign_commits
+    med = lambda xs: float(np.median(xs))
+    chain = "test_chain_id"
+    eng.keycache_config(True)
+    out = []
+    for text in shapes:
+        E, nvals = [int(x) for x in text.split("x")]
+        seeds = seeds_from_tag(b"tmed-lca-key", 0, nvals)
+        vals, order = make_valset(pubkeys_of(eng, seeds), [10] * nvals)
+        _, vpowers, vaddrs = vals.packed()
+
+        def header(tag, height):
+            h = lambda t: hashlib.sha256(tag + t).digest()
+            return {"version_block": 11, "version_app": 0, "chain_id": chain, "height": height, "time": (T2023, 0),
+                    "last_block_id": (h(b"/last"), 1, h(b"/last-psh")), "last_commit_hash": h(b"/lc"), "data_hash": h(b"/data"),
+                    "validators_hash": h(b"/vals"), "next_validators_hash": h(b"/next"), "consensus_hash": h(b"/cons"),
+                    "app_hash": h(b"/app"), "last_results_hash": h(b"/res"), "evidence_hash": h(b"/ev"),
+                    "proposer_address": vaddrs[0].tobytes()}
+
+        commits = sign_commits(eng, chain, [(seeds[order], vaddrs[:nvals], 10, 1, block_id(b"lca-%d-%d" % (nvals, e)), T2023, None)
+                                            for e in range(E)])
+        trusted_commit = T.Commit(10, 1, block_id(b"lca-trusted"), [])
+        claimed = (vaddrs[:nvals], vpowers[:nvals])
+        reqs, creqs, headers = [], [], []
+        for e in range(E):
+            ch, th = header(b"lca-conflicting-%d" % e, 10), header(b"lca-trusted-%d" % e, 10)
+            ev = EV.LightClientAttackEvidence(ch, commits[e], vals, 4, claimed, vals.total_voting_power())
+            reqs.append(EV.LcaRequest(ev, 4, th, trusted_commit, vals))
+            creqs += [(T.MODE_LIGHT_TRUSTING, vals, chain, None, 0, commits[e], 1, 3),
+                      (T.MODE_LIGHT, vals, chain, commits[e].block_id, 10, commits[e], 0, 0)]
+            headers += [ch, th]
+        prep, pb, hb = EV.PreparedLca(reqs), T.PreparedBatch(creqs), MK.HeaderBatch(headers)
+
+        def new_route():
+            t0 = time.perf_counter()
+            prep.run(eng)
+            t1 = time.perf_counter()
+            return prep.codes(), (t1 - t0,) + EV.last_lca_kernel_times(eng)
+
+        def old_route():
+            t0 = time.perf_counter()
+            pb.run(eng)
+            t1 = time.perf_counter()
+            hb.run(eng)
+            t2 = time.perf_counter()
+            lists = prep.byzantine(None)
+            t3 = time.perf_counter()
+            return pb.codes(), lists, (t1 - t0, t2 - t1, t3 - t2)
+
+        new_route()                 # the first call meets a cold key-set cache
+        eng.keycache_wait()
+        codes, _ = new_route()
+        new_lists = prep.lists()
+        ocodes, olists, _ = old_route()
+        assert (codes == EV.LCA_OK).all(), "tmed_verify_light_client_attacks: unexpected codes %s" % codes[:8]
+        assert (ocodes == 0).all(), "tmed_verify_commits: unexpected codes"
+        want = list(range(nvals))   # equal powers: ascending addresses, the set's own order
+        assert all(l == want for l in new_lists) and all(l == (EV.LCA_LUNATIC, EV.BYZ_OK, want) for l in olists), \
+            "the two routes disagree on a list"
+        new_t, old_t = [], []
+        for _ in range(runs):
+            c2, t = new_route()
+            assert (c2 == codes).all()
+            new_t.append(t)
+            old_t.append(old_route()[2])
+        nt, ot = np.array(new_t), np.array(old_t)
+        new_wall, old_wall = med(nt[:, 0]), med(ot.sum(axis=1))
+        out.append({"shape": text, "evidences": E, "validators": nvals, "signatures": E * nvals, "routes_agree": True,
+                    "new_ms": round(new_wall * 1e3, 3), "new_evidences_per_s": round(E / new_wall, 1),
+                    "lookup_kernel_ms": round(med(nt[:, 1]), 4), "rank_kernel_ms": round(med(nt[:, 2]), 4),
+                    "old_ms": round(old_wall * 1e3, 3), "old_evidences_per_s": round(E / old_wall, 1),
+                    "old_verify_commits_ms": round(med(ot[:, 0]) * 1e3, 3), "old_header_hashes_ms": round(med(ot[:, 1]) * 1e3, 3),
+                    "old_byzantine_host_ms": round(med(ot[:, 2]) * 1e3, 3), "speedup": round(old_wall / new_wall, 3)})
+    return {"config": "lca", "metric": "light-client-attack evidences per second: tmed_verify_light_client_attacks vs "
+            "tmed_verify_commits + tmed_header_hashes + tmed_byzantine_validators_host", "runs": runs, "shapes": out}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="c1,c3,c4")
@@ -1328,6 +1423,7 @@ def main():
                     help="C4: commits in ordinary (pageable) memory: signatures go through the seam's staging copy")
     ap.add_argument("--evidence-shapes", default="2048x10000,1000x4x175",
                     help="evidence: NxV (one list of N evidences, V validators) or LxKxV (L lists of K), comma-separated")
+    ap.add_argument("--lca-shapes", default="1x10000,50x175", help="lca: ExV (E evidences, V validators), comma-separated")
     ap.add_argument("--rule", choices=["go", "zip215"], default="go",
                     help="the context's signature rule for every leg (tmed_set_rule): go, the default, or zip215")
     args = ap.parse_args()
@@ -1352,6 +1448,8 @@ def main():
             r = votes(eng, args.runs, not args.no_cpu)
         elif cfg == "evidence" and rank == 0:
             r = evidence(eng, min(args.runs, args.reps), tuple(args.evidence_shapes.split(",")))
+        elif cfg == "lca" and rank == 0:
+            r = lca(eng, min(args.runs, args.reps), tuple(args.lca_shapes.split(",")))
         elif cfg == "c4":
             r = c4(eng, args.blocks, args.validators, rank, world, coll, args.window, args.batch, args.corrupt_every,
                        args.pregen, not args.no_pinned, args.c4_policy, not args.no_stream)

@@ -1102,8 +1102,8 @@ typedef struct {
  * tmed_last_kernel_ms reports the two new kernels plus the verify kernels;
  * tmed_evidence_kernel_times gives the lookup's (ms[0]) and the prepare kernel's (ms[1]) share.
  * What stays in Go: ValidateBasic (the contract at verify.go:110), the age and time checks, the
- * committed / pending lookups and the duplicate-hash loop of Pool.verify / CheckEvidence, and
- * LightClientAttackEvidence (its checks map onto tmed_verify_commits).
+ * committed / pending lookups and the duplicate-hash loop of Pool.verify / CheckEvidence.
+ * LightClientAttackEvidence has its own call, tmed_verify_light_client_attacks (below).
  * TMED_EINVAL for malformed calls only: a NULL array with n > 0, votes.n != 2n, NULL vals->pubkeys,
  * addresses or powers with vals->n > 0, a keyset_index past the key set.
  */
@@ -1152,6 +1152,167 @@ int tmed_evidence_bytes(const tmed_dup_evidence *ev, uint8_t *out, size_t out_ca
                         uint8_t *ok);
 int tmed_verify_duplicate_votes_host(const tmed_dup_request *reqs, size_t n_reqs, uint8_t *pre_codes,
                                      uint8_t *vote_states, int32_t *found, uint32_t *msg_lens, uint8_t *device_route);
+
+/* ------------------------------------------------- evidence: light client attacks */
+
+/*
+ * The arguments of one VerifyLightClientAttack call (evidence/verify.go:113-154) as existing structs.
+ * The chain ID of both commit checks is trusted_header's (:118, :130).
+ */
+typedef struct {
+  /* e.ConflictingBlock */
+  const tmed_header *conflicting_header;
+  const tmed_commit *conflicting_commit;  /* `addresses` is read (n_sigs x 20; address_lens NULL = all 20) */
+  const tmed_valset *conflicting_vals;    /* `addresses` and `powers` are read beside the keys */
+  int64_t common_height;                  /* e.CommonHeight: read by Hash() only */
+  int64_t total_voting_power;             /* e.TotalVotingPower */
+  /* e.ByzantineValidators, the claimed list */
+  size_t n_byz;
+  uint8_t byz_is_nil;                     /* 1: the slice is nil (a detector-made evidence may hold nil; n_byz must be
+                                             0); 0: non-nil, possibly empty: LightClientAttackEvidenceFromProto makes
+                                             an empty non-nil slice (types/evidence.go:405) */
+  const uint8_t *byz_addresses;           /* n_byz x 20 */
+  const uint32_t *byz_address_lens;       /* NULL = all 20; else len(Address) per entry (the 20-byte slot of any
+                                             other length is ignored: it equals no validator's) */
+  const int64_t *byz_powers;              /* n_byz */
+  /* commonHeader, trustedHeader, commonVals */
+  int64_t common_header_height;           /* commonHeader.Height */
+  const tmed_header *trusted_header;
+  const tmed_commit *trusted_commit;      /* trustedHeader.Commit: only round, n_sigs and flags are read */
+  const tmed_valset *common_vals;         /* `addresses`, `powers` and `total_power` are read beside the keys */
+} tmed_lca_request;
+
+/* What GetByzantineValidators takes the evidence for (types/evidence.go:233-279). */
+#define TMED_LCA_LUNATIC 0      /* ConflictingHeaderIsInvalid(trusted.Header) (:285-292): one of ValidatorsHash,
+                                   NextValidatorsHash, ConsensusHash, AppHash, LastResultsHash differs under
+                                   bytes.Equal (lengths count, nil equals empty) */
+#define TMED_LCA_EQUIVOCATION 1 /* otherwise, and trusted_commit->round == conflicting_commit->round (:253) */
+#define TMED_LCA_AMNESIA 2      /* otherwise: no validators, a nil list (:275-278) */
+
+#define TMED_BYZ_OK 0
+#define TMED_BYZ_PANIC 1 /* the reference panics inside GetByzantineValidators (equivocation only): a non-absent
+                            conflicting signature at an index >= trusted_commit->n_sigs (:264, index out of range),
+                            or a lookup that finds nobody while the list has >= 2 entries (:269-272: the nil
+                            *Validator reaches ValidatorsByVotingPower.Less, which dereferences it; Go 1.18's
+                            sort.Sort compares every element at least once for n >= 2) */
+
+typedef struct {
+  int kind;       /* TMED_LCA_* */
+  int state;      /* TMED_BYZ_* (count is 0 under PANIC) */
+  uint32_t count; /* entries written; 0 = the reference returns nil (`var validators []*Validator` never appended to) */
+} tmed_byz_result;
+
+/*
+ * GetByzantineValidators (types/evidence.go:233-279) for n evidences per call, without a host map and
+ * without a host sort.  Request r's list is written to byz[byz_off[r] .. byz_off[r+1]), a range that
+ * must hold conflicting_commit->n_sigs entries; out[r].count of them are written, the rest of the
+ * range is left as it was.  The entries are validator INDICES, into common_vals for a lunatic attack
+ * and into conflicting_vals for an equivocation, in the reference's order.
+ *   Lunatic: for each ForBlock signature of the conflicting commit, in commit order,
+ *     GetByAddress(sig.ValidatorAddress) in common_vals: the first match in index order; an address
+ *     whose address_lens entry is not 20 matches nobody; signatures that find nobody are dropped; a
+ *     validator found by two signatures appears twice.
+ *   Equivocation: for each i with conflicting sig i not absent and trusted sig i not absent,
+ *     GetByAddress(conflicting sig i's address) in conflicting_vals (not vals[i]).  TMED_BYZ_PANIC as
+ *     stated above.  A single-entry list whose one lookup found nobody is count 1, entry -1 (the
+ *     reference returns a slice holding one nil *Validator).
+ *   Order: ValidatorsByVotingPower (types/validator_set.go:906-911): power descending as int64, then
+ *     address ascending under bytes.Compare.  On found validators (power, address) determines the
+ *     index (the first match wins), so the output is unique although sort.Sort is not stable.
+ * Only the round, n_sigs and flags of trusted_commit, the hashes of the two headers and the flags,
+ * addresses and address_lens of conflicting_commit are read, besides the two sets' addresses and
+ * powers; no signature is.
+ *
+ * Device work (csrc/lca.hip; the rule is csrc/lca_free.h, compiled by host and device alike):
+ * lca_lookup_kernel, one wavefront per candidate signature (the address scan of
+ * evidence_lookup_kernel: one routine, two callers), writes the found validator's ordering key;
+ * lca_rank_kernel, one lane per candidate, counts the candidates of its request that order before it
+ * (ties by commit position, so the ranks are a permutation) over LDS tiles and writes its validator
+ * index at its rank.  Nothing is sorted.  Requests of any size mix in one launch.
+ * tmed_lca_kernel_times gives the two kernels' times of the context's last call (ms[0] lookup,
+ * ms[1] rank), of tmed_byzantine_validators or tmed_verify_light_client_attacks.
+ * tmed_byzantine_validators_host: the same rule lane by lane on the host (csrc/lca_host.h), no context.
+ * TMED_EINVAL for malformed calls only: a NULL struct or array that is read, n_byz > 0 with
+ * byz_is_nil, byz_off not ascending or a range shorter than conflicting_commit->n_sigs.
+ */
+int tmed_byzantine_validators(tmed_ctx *ctx, const tmed_lca_request *reqs, size_t n, int32_t *byz,
+                              const uint64_t *byz_off, tmed_byz_result *out);
+int tmed_byzantine_validators_host(const tmed_lca_request *reqs, size_t n, int32_t *byz, const uint64_t *byz_off,
+                                   tmed_byz_result *out);
+int tmed_lca_kernel_times(tmed_ctx *ctx, float ms[2]);
+
+/* Outcome codes of tmed_verify_light_client_attacks, numbered in the order the reference checks; the
+ * first failing check wins. */
+#define TMED_LCA_OK 0
+#define TMED_LCA_TRUSTING 1          /* verify.go:117-121: common_header_height != conflicting height and
+                                        commonVals.VerifyCommitLightTrusting(chain, commit, 1/3) failed, its outcome
+                                        in `commit` ("skipping verification of conflicting block failed: %w") */
+#define TMED_LCA_NOT_DERIVED 2       /* :124-127: the same heights and ConflictingHeaderIsInvalid(trusted.Header) */
+#define TMED_LCA_COMMIT 3            /* :130-133: conflicting_vals.VerifyCommitLight(chain, commit.BlockID,
+                                        conflicting height, commit) failed, its outcome in `commit` ("invalid commit
+                                        from conflicting block: %w").  The expected BlockID is the commit's own, so
+                                        only the height precheck and the loop can fail */
+#define TMED_LCA_TOTAL_POWER 4       /* :136-139 (and again :231-234): expected = e.TotalVotingPower, actual =
+                                        common_vals->total_power, the order the message prints them in */
+#define TMED_LCA_TIME_NOT_VIOLATED 5 /* :142-145: conflicting height > trusted height and
+                                        ConflictingBlock.Time.After(trustedHeader.Time) */
+#define TMED_LCA_SAME_HASH 6         /* :148-151: bytes.Equal(trustedHeader.Hash(), ConflictingBlock.Hash()); two nil
+                                        hashes are equal */
+#define TMED_LCA_AMNESIA_HAS_VALIDATORS 7 /* :243-248: the computed list is nil and byz_is_nil == 0; actual = n_byz */
+#define TMED_LCA_BYZ_COUNT 8         /* :250-252: expected = the computed count, actual = n_byz */
+#define TMED_LCA_BYZ_ADDRESS 9       /* :255-260: !bytes.Equal(claimed[idx].Address, computed[idx].Address), lengths
+                                        included; idx, and val_idx = the expected validator's index */
+#define TMED_LCA_BYZ_POWER 10        /* :262-267: the powers differ; idx, val_idx, expected = the validator's power,
+                                        actual = the claimed one */
+#define TMED_LCA_PANIC 11            /* the reference panics; the caller runs Go, which panics as before: a
+                                        TMED_COMMIT_PANIC of either commit check (carried in `commit`), a
+                                        TMED_BYZ_PANIC, or a computed list of one nil entry against a claimed list of
+                                        one entry (:255 dereferences nil; any other claimed count is BYZ_COUNT first) */
+#define TMED_LCA_GO_PATH 12          /* a header time outside the range documented at TMED_LIGHT_GO_PATH */
+
+typedef struct {
+  int code;
+  int kind;                   /* TMED_LCA_LUNATIC / EQUIVOCATION / AMNESIA, whatever the code */
+  tmed_commit_result commit;  /* TRUSTING / COMMIT / PANIC of a commit check: the failing call's result (else zero) */
+  int64_t expected, actual;   /* TOTAL_POWER, AMNESIA_HAS_VALIDATORS, BYZ_COUNT, BYZ_POWER */
+  int32_t idx, val_idx;       /* BYZ_ADDRESS / BYZ_POWER: the list position and the expected validator's index */
+  uint32_t n_byz_expected;    /* the computed list's length where it was computed (the byz range holds it) */
+  uint32_t verified_trusting; /* signatures sent to the verifier for VerifyCommitLightTrusting */
+  uint32_t verified_light;    /* ... and for VerifyCommitLight */
+  uint8_t hash[32];           /* LightClientAttackEvidence.Hash() (types/evidence.go:302-309) of every request whose
+                                 header hashes were computed (any code but NOT_DERIVED and GO_PATH; else zero) */
+} tmed_lca_result;
+
+/*
+ * VerifyLightClientAttack (evidence/verify.go:113-154, with validateABCIEvidence :226-271 and
+ * GetByzantineValidators) for n evidences in one call, the reference's checks replayed in its order
+ * (csrc/lca_host.h).  Request r's computed list is written to byz[byz_off[r] ..) as by
+ * tmed_byzantine_validators, for the requests that reach validateABCIEvidence.
+ *
+ * Hash(): SHA-256 over a buffer of 32 + n bytes, n = the length of binary.PutVarint(CommonHeight), the
+ * ZIGZAG varint: the first 31 bytes of the conflicting header's hash (copy(bz[:tmhash.Size-1], ...);
+ * a nil header hash leaves 31 zero bytes), byte 31 zero, then the varint.
+ *
+ * Device work of one call: GO_PATH and NOT_DERIVED are decided on the host first and send nothing to
+ * the device; header_hash_kernel over the two headers of every other request; one plan -> batch ->
+ * replay pass of the commit seam over the Trusting + Light pair on the one Commit for requests whose
+ * heights differ and the Light request alone otherwise (key-set cache, context rule and pipelining as
+ * for tmed_verify_commits); then, for the requests still undecided, the two kernels of
+ * tmed_byzantine_validators, and lca_hash_kernel (one lane per request) for Hash().  The claimed list
+ * is compared on the host.  Submitted blocksync windows are collected first.  flags must be 0.
+ * TMED_EINVAL for malformed calls only.
+ *
+ * tmed_verify_light_client_attacks_with: the same replay with no device: the header hashes
+ * (conflicting_* / trusted_*: n x 32 with n ok bytes, 0 = nil) and the batch verifier are the
+ * caller's, the lists and Hash() are computed on the host by the same source.
+ */
+int tmed_verify_light_client_attacks(tmed_ctx *ctx, const tmed_lca_request *reqs, size_t n, uint32_t flags,
+                                     int32_t *byz, const uint64_t *byz_off, tmed_lca_result *out);
+int tmed_verify_light_client_attacks_with(const tmed_lca_request *reqs, size_t n, uint32_t flags, int32_t *byz,
+                                          const uint64_t *byz_off, tmed_lca_result *out,
+                                          const uint8_t *conflicting_hashes, const uint8_t *conflicting_ok,
+                                          const uint8_t *trusted_hashes, const uint8_t *trusted_ok,
+                                          tmed_batch_verify_fn verify, void *user);
 
 /* ------------------------------------------------- blocksync replay (f4) */
 

@@ -37,6 +37,7 @@
 #include "signbytes.h"
 #include "votes_host.h"
 #include "evidence_host.h"
+#include "lca_host.h"
 
 // One translation unit, by role (each header is included here only, in this order):
 //   seam_host.h   planning, aliasing, staging groups, scatter, replay: host C++ only
@@ -44,7 +45,7 @@
 //   blocksync.h   the context's pipelined batch stream and the tmed_blocksync_* entry points
 //                 (c_guard.h: the entry points' wrapper; debug_zero.h: diagnostics)
 // This file: the verify path of one seam call, the light client's hashes, the tmed_verify_commits,
-// tmed_light_verify and *_multi entry points.
+// tmed_light_verify, tmed_verify_light_client_attacks and *_multi entry points.
 #include "seam_host.h"
 #include "kc_resolve.h"
 #include "blocksync.h"
@@ -337,6 +338,52 @@ extern "C" int tmed_light_verify(tmed_ctx *ctx, const tmed_light_request *reqs, 
             uint8_t *vh) { return light_hashes_device(ctx, reqs, need_hdr, need_vals, hh, hok, vh); },
         [&](const tmed_commit_request *rq, size_t m, tmed_commit_result *res) {
           return verify_commits_impl(ctx, rq, m, res, rule);
+        });
+  });
+}
+
+// ---- VerifyLightClientAttack (evidence/verify.go:113-154; the replay is lca_host.h) ----------------
+// Header.Hash of both headers of the requests `live` under one hold of the context's lock (submitted
+// blocksync windows are collected first), the commit checks as tmed_verify_commits runs them, then
+// the byzantine lists and Hash() under another hold (lca.hip lca_tail_locked).
+extern "C" int tmed_verify_light_client_attacks(tmed_ctx *ctx, const tmed_lca_request *reqs, size_t n, uint32_t flags,
+                                                int32_t *byz, const uint64_t *byz_off, tmed_lca_result *out) {
+  if (!ctx) return TMED_EINVAL;
+  const int rule = tmed::seam_rule(ctx);
+  return c_guard(ctx, [&] {
+    return tmed_lca::lca_run(
+        reqs, n, flags, byz, byz_off, out,
+        [&](const std::vector<size_t> &live, uint8_t *ch, uint8_t *cok, uint8_t *th, uint8_t *tok) {
+          const size_t m = live.size();
+          std::vector<tmed_header> hs;
+          hs.reserve(2 * m);
+          for (const size_t i : live) {
+            if (!tmed::header_pointers_ok(*reqs[i].conflicting_header) || !tmed::header_pointers_ok(*reqs[i].trusted_header))
+              return (int)TMED_EINVAL;
+            hs.push_back(*reqs[i].conflicting_header);
+            hs.push_back(*reqs[i].trusted_header);
+          }
+          std::vector<uint8_t> ho(64 * m), ok(2 * m);
+          const int rc = tmed::locked(ctx, /*collect=*/true, [&] {
+            return tmed::header_hashes_locked(ctx, hs.data(), 2 * m, ho.data(), ok.data());
+          });
+          if (rc != TMED_OK) return rc;
+          for (size_t j = 0; j < m; j++) {
+            memcpy(ch + 32 * live[j], ho.data() + 64 * j, 32);
+            memcpy(th + 32 * live[j], ho.data() + 64 * j + 32, 32);
+            cok[live[j]] = ok[2 * j];
+            tok[live[j]] = ok[2 * j + 1];
+          }
+          return (int)TMED_OK;
+        },
+        [&](const tmed_commit_request *rq, size_t m, tmed_commit_result *res) {
+          return verify_commits_impl(ctx, rq, m, res, rule);
+        },
+        [&](const std::vector<size_t> &live, const uint8_t *ch, const uint8_t *cok, const std::vector<size_t> &need,
+            const int *kinds, tmed_byz_result *bres, uint8_t *ev_hash) {
+          return tmed::locked(ctx, /*collect=*/true, [&] {
+            return tmed::lca_tail_locked(ctx, reqs, live, ch, cok, need, kinds, byz, byz_off, bres, ev_hash);
+          });
         });
   });
 }

@@ -154,6 +154,13 @@ int verify_votes_locked(tmed_ctx *c, const tmed_vote_request *reqs, size_t n, ui
 // evidence.hip: tmed_verify_duplicate_votes over n checked requests (evidence_host.h check_request)
 // whose sets the key-set cache has resolved; ctx->mu held.
 int verify_dup_votes_locked(tmed_ctx *c, const tmed_dup_request *reqs, size_t n, uint8_t *codes);
+// lca.hip: the device tail of lca_host.h's lca_run over checked requests: the byzantine list of every
+// request of `need` (kinds[i]: its attack kind) into byz[byz_off[i] ..) with bres[i], and
+// LightClientAttackEvidence.Hash() of every request of `live` (ch / cok: its conflicting header's hash)
+// into ev_hash[32 i ..); all arrays are indexed by request; ctx->mu held.
+int lca_tail_locked(tmed_ctx *c, const tmed_lca_request *reqs, const std::vector<size_t> &live, const uint8_t *ch,
+                    const uint8_t *cok, const std::vector<size_t> &need, const int *kinds, int32_t *byz,
+                    const uint64_t *byz_off, tmed_byz_result *bres, uint8_t *ev_hash);
 // merkle.hip's tree builder for evidence.hip (EvidenceList.Hash): room for the plan's nodes, the
 // node buffer's start (a leaf stage writes level 0 there), leafHash of n device-resident byte
 // slices into out (32-byte digests as state words), the levels, the roots; ctx->mu held, everything
@@ -350,7 +357,7 @@ struct tmed_ctx {
   // totals / indexes and codes)
   tmed::DevBuf d_proof_off, d_proof_out, d_proof_in;
   // The staging arena of commit_hashes_locked, header_hashes_fused (merkle.hip), median_times_locked
-  // (median.hip), run_group_device (votes.hip) and the two device batches of evidence.hip, each laid out
+  // (median.hip), run_group_device (votes.hip), the two device batches of evidence.hip and lca_tail_locked (lca.hip), each laid out
   // by its own layout struct.  One pair serves them all: each packs, copies in, launches, copies out, waits (finish_call) and reads its
   // results before it returns, all inside one hold of ctx->mu, so no two are ever live at once (a
   // light-client call takes its header hashes, set hashes and commit checks under separate holds, one
@@ -360,6 +367,7 @@ struct tmed_ctx {
   float last_vote_prep_ms = 0.f;
   hipEvent_t ev_lookup = nullptr;        // the end of evidence_lookup_kernel (evidence.hip)
   float last_ev_ms[2] = {0.f, 0.f};      // evidence_lookup_kernel, evidence_prepare_kernel (tmed_evidence_kernel_times)
+  float last_lca_ms[2] = {0.f, 0.f};     // lca_lookup_kernel (its end is ev_lookup too), lca_rank_kernel (tmed_lca_kernel_times)
   tmed::DevBuf d_korder;  // key-grouped order of a key-cached batch: counts / cursors + permutation
   tmed::DevBuf d_zip;     // ZIP-215 batch mode scratch (zip215.hip zip_bufs: points, digits, sort, buckets)
   bool zip_dense = false; // ZIP-215: the last large chunk had failures (zip215.hip: decide the next one singly first)

@@ -12,7 +12,7 @@
 // 20-byte addresses, each read as five dwords from the call's packed, 4-byte-aligned address array;
 // the first stride in which a lane matches ends the scan, and the lowest matching lane of that stride
 // (the wave-wide minimum of the matching index, taken from the ballot) is the first match in index
-// order.  No sort and no host map.
+// order (addr_scan.h wave_first_address, shared with lca.hip).  No sort and no host map.
 //
 // evidence_prepare_kernel: one lane per evidence, one wavefront per workgroup of 64, laid out like
 // vote_prepare_kernel (votes.hip).  A lane stages its two 144-byte VoteRecs and its 64-byte EvRec
@@ -47,6 +47,7 @@
 #include <vector>
 
 #include "../../include/tmed25519.h"
+#include "addr_scan.h"
 #include "evidence_host.h"
 #include "host_for.h"
 #include "merkle_levels.h"
@@ -89,17 +90,7 @@ __global__ __launch_bounds__(kEvLanes) void evidence_lookup_kernel(EvPrep p, uin
     uint32_t want[5];
 #pragma unroll
     for (int k = 0; k < 5; k++) want[k] = rec[28 + k];  // VoteRec::addr
-    const uint32_t *set = reinterpret_cast<const uint32_t *>(p.set_addr) + 5 * s.addr_base;
-    const uint32_t nv = s.n_vals;
-    for (uint32_t base = 0; base < nv; base += kEvLanes) {  // wave-uniform: every lane runs every stride
-      const uint32_t v = base + lane;
-      const bool m = v < nv && ev_addr_match(want, set + 5 * (size_t)v);
-      const unsigned long long hit = __ballot(m);
-      if (hit) {
-        found = base + (uint32_t)__ffsll(hit) - 1;
-        break;
-      }
-    }
+    found = wave_first_address(want, reinterpret_cast<const uint32_t *>(p.set_addr) + 5 * s.addr_base, s.n_vals, lane);
   }
   if (lane == 0) p.found[i] = found;
 }

@@ -1865,3 +1865,195 @@ func (e *Engine) EvidenceHashes(d *DupEvidenceData, lists [][]EvidenceItem) (has
 	}
 	return append([][32]byte(nil), ho[:n]...), append([][32]byte(nil), ro[:nl]...), evOK, listOK, nil
 }
+
+// ---- evidence: VerifyLightClientAttack (evidence/verify.go:113-154, :226-271) and
+// GetByzantineValidators (types/evidence.go:233-279) ----
+
+// Outcome codes of VerifyLightClientAttacks: the first check that fails, in the reference's order
+// (see tmed25519.h, which cites the reference lines of each).
+const (
+	LcaOK                   = C.TMED_LCA_OK
+	LcaTrusting             = C.TMED_LCA_TRUSTING
+	LcaNotDerived           = C.TMED_LCA_NOT_DERIVED
+	LcaCommit               = C.TMED_LCA_COMMIT
+	LcaTotalPower           = C.TMED_LCA_TOTAL_POWER
+	LcaTimeNotViolated      = C.TMED_LCA_TIME_NOT_VIOLATED
+	LcaSameHash             = C.TMED_LCA_SAME_HASH
+	LcaAmnesiaHasValidators = C.TMED_LCA_AMNESIA_HAS_VALIDATORS
+	LcaByzCount             = C.TMED_LCA_BYZ_COUNT
+	LcaByzAddress           = C.TMED_LCA_BYZ_ADDRESS
+	LcaByzPower             = C.TMED_LCA_BYZ_POWER
+	// LcaPanic: the reference panics (a commit check, GetByzantineValidators, or a nil validator in
+	// the compare); the caller runs the original Go function, which panics as before.
+	LcaPanic = C.TMED_LCA_PANIC
+	// LcaGoPath: a header time outside the Timestamp range: the caller runs the Go function.
+	LcaGoPath = C.TMED_LCA_GO_PATH
+	// The attack kinds GetByzantineValidators distinguishes.
+	LcaLunatic      = C.TMED_LCA_LUNATIC
+	LcaEquivocation = C.TMED_LCA_EQUIVOCATION
+	LcaAmnesia      = C.TMED_LCA_AMNESIA
+	ByzOK           = C.TMED_BYZ_OK
+	ByzPanic        = C.TMED_BYZ_PANIC
+)
+
+// LcaRequest holds the arguments of one VerifyLightClientAttack call as flat copies: the evidence
+// (ConflictingBlock, CommonHeight, ByzantineValidators, TotalVotingPower), commonHeader.Height, the
+// trusted SignedHeader and commonVals.
+type LcaRequest struct {
+	ConflictingHeader *HeaderData
+	ConflictingCommit *CommitData
+	ConflictingVals   *ValSet
+	CommonHeight      int64
+	TotalVotingPower  int64
+	// e.ByzantineValidators: ByzIsNil tells a nil slice from an empty one
+	// (LightClientAttackEvidenceFromProto makes an empty non-nil slice).
+	ByzIsNil     bool
+	ByzAddresses []byte   // n x 20
+	ByzAddrLens  []uint32 // nil: all 20
+	ByzPowers    []int64  // n
+	// commonHeader.Height, trustedHeader (its Commit: round, size and flags are read), commonVals
+	CommonHeaderHeight int64
+	TrustedHeader      *HeaderData
+	TrustedCommit      *CommitData
+	CommonVals         *ValSet
+}
+
+// ByzResult is GetByzantineValidators of one request: validator indices into CommonVals (LcaLunatic)
+// or ConflictingVals (LcaEquivocation) in the reference's order; -1 is a nil entry; a nil List is the
+// reference's nil slice.  State ByzPanic: the reference panics.
+type ByzResult struct {
+	Kind, State int
+	List        []int32
+}
+
+// LcaResult is one request's outcome; the caller builds the reference's error value from it
+// (INTEGRATION.md §2d).
+type LcaResult struct {
+	Code, Kind                      int
+	Commit                          Result // LcaTrusting / LcaCommit / a commit check's LcaPanic
+	Expected, Actual                int64
+	Idx, ValIdx                     int32
+	Byz                             []int32 // the computed list where validateABCIEvidence was reached
+	VerifiedTrusting, VerifiedLight uint32
+	Hash                            [32]byte // LightClientAttackEvidence.Hash() (zero for LcaNotDerived / LcaGoPath)
+}
+
+// lcaArgs builds the C requests and the output ranges of reqs in a.
+func lcaArgs(a *arena, reqs []LcaRequest) (*C.tmed_lca_request, []int32, []uint64, error) {
+	n := len(reqs)
+	creqs := (*[1 << 22]C.tmed_lca_request)(a.alloc(uintptr(n) * unsafe.Sizeof(C.tmed_lca_request{})))[:n:n]
+	hs := (*[1 << 24]C.tmed_header)(a.alloc(uintptr(2*n) * unsafe.Sizeof(C.tmed_header{})))[: 2*n : 2*n]
+	cs := (*[1 << 24]C.tmed_commit)(a.alloc(uintptr(2*n) * unsafe.Sizeof(C.tmed_commit{})))[: 2*n : 2*n]
+	vs := (*[1 << 24]C.tmed_valset)(a.alloc(uintptr(2*n) * unsafe.Sizeof(C.tmed_valset{})))[: 2*n : 2*n]
+	seenV := make(map[*ValSet]*C.tmed_valset, 2*n)
+	seenC := make(map[*CommitData]*C.tmed_commit, 2*n)
+	nv, nc := 0, 0
+	valset := func(v *ValSet) *C.tmed_valset {
+		cv, ok := seenV[v]
+		if !ok {
+			vs[nv] = a.valset(v)
+			cv = &vs[nv]
+			seenV[v] = cv
+			nv++
+		}
+		return cv
+	}
+	commit := func(c *CommitData) *C.tmed_commit {
+		cc, ok := seenC[c]
+		if !ok {
+			cs[nc] = a.commitC(c, nil)
+			cc = &cs[nc]
+			seenC[c] = cc
+			nc++
+		}
+		return cc
+	}
+	off := make([]uint64, n+1)
+	for i := range reqs {
+		r := &reqs[i]
+		if r.ConflictingHeader == nil || r.ConflictingCommit == nil || r.ConflictingVals == nil || r.TrustedHeader == nil ||
+			r.TrustedCommit == nil || r.CommonVals == nil || len(r.ByzAddresses) != 20*len(r.ByzPowers) {
+			return nil, nil, nil, errors.New("tmedgpu: light client attack: nil header, commit or validator set, or a claimed list of two lengths")
+		}
+		hs[2*i], hs[2*i+1] = a.headerC(r.ConflictingHeader), a.headerC(r.TrustedHeader)
+		var isNil C.uint8_t
+		if r.ByzIsNil {
+			isNil = 1
+		}
+		creqs[i] = C.tmed_lca_request{conflicting_header: &hs[2*i], conflicting_commit: commit(r.ConflictingCommit),
+			conflicting_vals: valset(r.ConflictingVals), common_height: C.int64_t(r.CommonHeight),
+			total_voting_power: C.int64_t(r.TotalVotingPower), n_byz: C.size_t(len(r.ByzPowers)), byz_is_nil: isNil,
+			byz_addresses: a.bytes(r.ByzAddresses), byz_address_lens: a.u32(r.ByzAddrLens), byz_powers: a.i64(r.ByzPowers),
+			common_header_height: C.int64_t(r.CommonHeaderHeight), trusted_header: &hs[2*i+1],
+			trusted_commit: commit(r.TrustedCommit), common_vals: valset(r.CommonVals)}
+		off[i+1] = off[i] + uint64(len(r.ConflictingCommit.Flags))
+	}
+	return &creqs[0], make([]int32, off[n]+1), off, nil
+}
+
+// ByzantineValidators is GetByzantineValidators for many evidences in one call
+// (tmed_byzantine_validators): the address lookups and the order by voting power are computed on the
+// device, with no map and no sort on the host.  An error means "take the original Go path".
+func (e *Engine) ByzantineValidators(reqs []LcaRequest) ([]ByzResult, error) {
+	n := len(reqs)
+	if n == 0 {
+		return nil, nil
+	}
+	a := e.getArena()
+	defer e.putArena(a)
+	creqs, byz, off, err := lcaArgs(a, reqs)
+	if err != nil {
+		return nil, err
+	}
+	res := make([]C.tmed_byz_result, n)
+	if rc := C.tmed_byzantine_validators(e.ctx, creqs, C.size_t(n), (*C.int32_t)(unsafe.Pointer(&byz[0])),
+		(*C.uint64_t)(unsafe.Pointer(&off[0])), &res[0]); rc != 0 {
+		return nil, errors.New(C.GoString(C.tmed_strerror(rc)))
+	}
+	out := make([]ByzResult, n)
+	for i := range res {
+		out[i] = ByzResult{Kind: int(res[i].kind), State: int(res[i].state)}
+		if m := uint64(res[i].count); m > 0 {
+			out[i].List = byz[off[i] : off[i]+m : off[i]+m]
+		}
+	}
+	return out, nil
+}
+
+// VerifyLightClientAttacks is VerifyLightClientAttack for many evidences in one call
+// (tmed_verify_light_client_attacks): both headers' hashes, both commit checks, the byzantine
+// validators and Hash() on the device, the reference's checks replayed in its order.  ValidateBasic,
+// the header loads and the age checks of Pool.verify stay with the caller.  An error means "take
+// the original Go path".
+func (e *Engine) VerifyLightClientAttacks(reqs []LcaRequest) ([]LcaResult, error) {
+	n := len(reqs)
+	if n == 0 {
+		return nil, nil
+	}
+	a := e.getArena()
+	defer e.putArena(a)
+	creqs, byz, off, err := lcaArgs(a, reqs)
+	if err != nil {
+		return nil, err
+	}
+	res := make([]C.tmed_lca_result, n)
+	if rc := C.tmed_verify_light_client_attacks(e.ctx, creqs, C.size_t(n), 0, (*C.int32_t)(unsafe.Pointer(&byz[0])),
+		(*C.uint64_t)(unsafe.Pointer(&off[0])), &res[0]); rc != 0 {
+		return nil, errors.New(C.GoString(C.tmed_strerror(rc)))
+	}
+	out := make([]LcaResult, n)
+	for i := range res {
+		o := LcaResult{Code: int(res[i].code), Kind: int(res[i].kind), Expected: int64(res[i].expected),
+			Actual: int64(res[i].actual), Idx: int32(res[i].idx), ValIdx: int32(res[i].val_idx),
+			VerifiedTrusting: uint32(res[i].verified_trusting), VerifiedLight: uint32(res[i].verified_light)}
+		o.Commit = toResults([]C.tmed_commit_result{res[i].commit})[0]
+		if m := uint64(res[i].n_byz_expected); m > 0 {
+			o.Byz = byz[off[i] : off[i]+m : off[i]+m]
+		}
+		for k := 0; k < 32; k++ {
+			o.Hash[k] = byte(res[i].hash[k])
+		}
+		out[i] = o
+	}
+	return out, nil
+}
