@@ -38,11 +38,19 @@
                  tmed_verify_light_client_attacks call against the route there was before:
                  tmed_verify_commits on the Trusting + Light pairs, tmed_header_hashes on the 2E
                  headers, tmed_byzantine_validators_host on one thread.
+  --config vb    block validation: validateBlock (state/validation.go:15-151) over a linked window of B
+                 blocks x V validators with a constant set (default 1000x10000 and 10000x175; --vb-shapes):
+                 one tmed_validate_blocks call against the composed route there was before it (the
+                 seven calls tmed_commit_hashes, tmed_txs_hashes, tmed_evidence_hashes,
+                 tmed_header_hashes, tmed_valset_hashes, tmed_median_times, tmed_verify_commits, then the
+                 proposer lookup and the compares on the host), alternated in the same run --runs times;
+                 --vb-route fused|composed times one route alone (one profiler run per route).
 Synthetic data (seeded keys, GPU RFC 8032 signer); prints one JSON line per config.
 """
 from __future__ import annotations
 
 import argparse
+import dataclasses
 import hashlib
 import json
 import os
@@ -1084,6 +1092,160 @@ def mt(eng, runs: int, shapes=((1000, 10_000), (10_000, 175))):
     return {"config": "mt", "metric": "state.MedianTime per window, device vs host vs VerifyCommit", "runs": runs, "shapes": out}
 
 
+def vb(eng, runs: int, shapes=("1000x10000", "10000x175"), route: str = "both"):
+    """validateBlock over a linked window per shape BxV (blocks x validators, one constant set, equal
+    powers, every signature valid, two transactions a block, no evidence): the chain is built block by
+    block (block h's LastCommit signs Header.Hash of block h - 1, its time is that commit's median), then
+    `runs` rounds of one fused tmed_validate_blocks call followed by the composed route over the same
+    C structs, each route's Python packing outside the timing.  Outcomes are compared request by request."""
+    import tmed.evidence as E
+    import tmed.merkle as MK
+    import tmed.state as S
+    import tmed.types as T
+    from tmed.workload import make_valset, pubkeys_of, seeds_from_tag, sign_commits
+    med = lambda xs: float(np.median(xs))
+    chain = "test_chain_id"
+    out = []
+    eng.keycache_config(True)
+    for shape in shapes:
+        blocks, nvals = (int(x) for x in shape.split("x"))
+        seeds = seeds_from_tag(b"tmed-vb-key", 0, nvals)
+        pubs = pubkeys_of(eng, seeds)
+        vals, order = make_valset(pubs, [10] * nvals)
+        addrs = np.array([np.frombuffer(v.address, np.uint8) for v in vals.validators])
+        vhash = MK.valset_hashes(eng, [vals])[0]
+        cons = hashlib.sha256(b"consensus-params").digest()
+        t_gen = time.perf_counter()
+        reqs, commits, headers = [], [], []
+        last_commit, last_id, last_time = T.Commit(0, 0, T.BlockID(), []), T.BlockID(), (T2023, 0)
+        st0 = S.BlockState(11, 0, chain, 1, 0, T.BlockID(), last_time, b"", cons, b"", vals, vals, vals, 1 << 20)
+        offset = None
+        for b in range(blocks + 1):  # block 0 is the initial block: the window is blocks 1 .. B
+            height = b + 1
+            txs = [b"tx-%d-a" % height, b"tx-%d-bb" % height]
+            if b == 0:
+                t = last_time
+            else:
+                if offset is None:  # the commit's median behind its base second, the same for every block
+                    code, mt_ = S.median_times(None, [(last_commit, vals)])[0]
+                    offset = (mt_[0] - int(last_commit.ts_seconds[0]), mt_[1])
+                t = (int(last_commit.ts_seconds[0]) + offset[0], offset[1])
+            ch = MK.commit_hashes(eng, [last_commit])[0]
+            hdr = {"version_block": 11, "version_app": 0, "chain_id": chain, "height": height, "time": t,
+                   "last_block_id": (last_id.hash, last_id.psh_total, last_id.psh_hash), "last_commit_hash": ch,
+                   "data_hash": MK.txs_hashes(eng, [txs])[0], "validators_hash": vhash, "next_validators_hash": vhash,
+                   "consensus_hash": cons, "app_hash": b"", "last_results_hash": b"",
+                   "evidence_hash": hashlib.sha256(b"").digest(), "proposer_address": vals.validators[b % nvals].address}
+            st = st0 if b < 2 else dataclasses.replace(st0, last_block_height=-1, last_block_time=(1, 1),
+                                                       last_block_id=T.BlockID(b"", 1, last_id.psh_hash))
+            if b == 1:
+                st = dataclasses.replace(st0, last_block_height=1, last_block_id=last_id, last_block_time=last_time)
+            if b >= 1:
+                reqs.append((S.Block(hdr, last_commit, txs), st, b >= 2))
+                commits.append(last_commit)
+                headers.append(hdr)
+            bid = T.BlockID(MK.header_hashes(eng, [hdr])[0], 1, hashlib.sha256(b"parts-%d" % height).digest())
+            last_commit = sign_commits(eng, chain, [(seeds[order], addrs, height, 0, bid, T2023 + 10 * height, None)])[0]
+            last_id, last_time = bid, t
+        t_gen = time.perf_counter() - t_gen
+        print("vb: %d blocks x %d validators generated in %.1fs" % (blocks, nvals, t_gen), file=sys.stderr, flush=True)
+        pb = S.PreparedBlocks(reqs)
+        # the composed route's calls over the same objects, packed once
+        chb = MK.CommitHashBatch(commits)
+        hb = MK.HeaderBatch(headers)
+        pm = S.PreparedMedian([(c, vals) for c in commits])
+        bids = [T.BlockID(bytes(h["last_block_id"][0]), h["last_block_id"][1], h["last_block_id"][2]) for h in headers]
+        pv = T.PreparedBatch([(T.MODE_COMMIT, vals, chain, bids[i], headers[i]["height"] - 1, commits[i], 0, 0)
+                              for i in range(blocks)])
+        want = {k: np.array([np.frombuffer(h[k], np.uint8) for h in headers]) for k in
+                ("last_commit_hash", "data_hash", "evidence_hash", "validators_hash", "next_validators_hash")}
+        link_want = np.array([np.frombuffer(h["last_block_id"][0], np.uint8) for h in headers])
+        times = np.array([h["time"] for h in headers], np.int64)
+        items, list_off = np.zeros(0, np.int64), np.zeros(blocks + 1, np.uint32)
+
+        prop_keys = [h["proposer_address"] for h in headers]
+        split = {"calls": 0.0, "host": 0.0}
+
+        def composed():
+            """-> codes (the checks the window can fail: the hashes, the link, the commit, the proposer, the time).
+            The seven calls and the host part (the proposer lookup and the compares) are timed apart."""
+            t0 = time.perf_counter()
+            cho, _ = chb.run(eng)
+            dh = MK.txs_hashes_packed(eng, pb.txs, pb.tx_off, pb.block_off)
+            _, eh, _, _ = E.evidence_hashes_packed(eng, [], items, list_off)
+            hh_list = hb.run(eng)
+            vh_bytes = MK.valset_hashes(eng, [vals])[0]
+            pm.run(eng)
+            pv.run(eng)
+            t1 = time.perf_counter()
+            code = np.zeros(blocks, np.int32)
+            first = lambda bad, c: np.where((code == 0) & bad, c, code)
+            hh = np.frombuffer(b"".join(hh_list), np.uint8).reshape(blocks, 32)
+            vh = np.frombuffer(vh_bytes, np.uint8)
+            code = first((cho != want["last_commit_hash"]).any(1), S.VB_LAST_COMMIT_HASH)
+            code = first((dh != want["data_hash"]).any(1), S.VB_DATA_HASH)
+            code = first((eh != want["evidence_hash"]).any(1), S.VB_EVIDENCE_HASH)
+            link = np.zeros(blocks, bool)
+            link[1:] = (hh[:-1] != link_want[1:]).any(1)
+            code = first(link, S.VB_LAST_BLOCK_ID)
+            code = first((vh != want["validators_hash"]).any(1), S.VB_VALIDATORS_HASH)
+            code = first((vh != want["next_validators_hash"]).any(1), S.VB_NEXT_VALIDATORS_HASH)
+            code = first(pv.codes() != 0, S.VB_LAST_COMMIT)
+            index = {}  # HasAddress: one address index of the set per call, one lookup per block
+            for i, v in enumerate(vals.validators):
+                index.setdefault(v.address, i)
+            found = np.array([k in index for k in prop_keys])
+            code = first(~found, S.VB_PROPOSER_UNKNOWN)
+            mtimes = np.array([r[1] for r in pm.results()], np.int64)
+            code = first((mtimes != times).any(1), S.VB_TIME_NOT_MEDIAN)
+            split["calls"], split["host"] = t1 - t0, time.perf_counter() - t1
+            return code
+
+        do_f, do_c = route in ("both", "fused"), route in ("both", "composed")  # one route alone: for a profiler
+        for _ in range(2):  # warm: buffers, and the key-set cache builds the set's keys between the rounds
+            if do_f:
+                pb.run(eng)
+            if do_c:
+                composed()
+            eng.keycache_wait()
+        fused, comp, kern, calls, host = [], [], [], [], []
+        mismatches = 0
+        for _ in range(runs):  # alternated in one session
+            if do_f:
+                t0 = time.perf_counter()
+                pb.run(eng)
+                fused.append(time.perf_counter() - t0)
+                kern.append(S.validate_kernel_ms(eng))
+            if do_c:
+                t0 = time.perf_counter()
+                ccodes = composed()
+                comp.append(time.perf_counter() - t0)
+                calls.append(split["calls"])
+                host.append(split["host"])
+            if do_f and do_c:
+                mismatches += int((pb.codes() != ccodes).sum())
+        if not do_f:  # the fields of the route that did not run stay 0
+            fused, kern = [0.0], [0.0]
+        if not do_c:
+            comp, calls, host = [0.0], [0.0], [0.0]
+        stats = S.validate_stats(eng) if do_f else (0, 0, 0)
+        final = pb.codes() if do_f else ccodes
+        out.append({"blocks": blocks, "validators": nvals, "all_ok": bool((final == 0).all()),
+                    "outcome_mismatches": mismatches,
+                    "fused_call_ms": round(med(fused) * 1e3, 3), "fused_call_ms_runs": [round(x * 1e3, 3) for x in fused],
+                    "composed_route_ms": round(med(comp) * 1e3, 3), "composed_route_ms_runs": [round(x * 1e3, 3) for x in comp],
+                    "composed_seven_calls_ms": round(med(calls) * 1e3, 3),
+                    "composed_seven_calls_ms_runs": [round(x * 1e3, 3) for x in calls],
+                    "composed_host_ms": round(med(host) * 1e3, 3), "composed_host_ms_runs": [round(x * 1e3, 3) for x in host],
+                    "fused_blocks_per_s": round(blocks / med(fused), 1) if do_f else 0.0,
+                    "composed_blocks_per_s": round(blocks / med(comp), 1) if do_c else 0.0, "route": route,
+                    "block_check_kernel_ms": round(med(kern), 4), "sets_hashed": stats[0], "sets_staged": stats[1],
+                    "blocks_checked": stats[2], "signatures_verified": int(sum(pb.res[q].verified for q in range(blocks))) if do_f else 0,
+                    "generate_s": round(t_gen, 2)})
+    return {"config": "vb", "metric": "validateBlock per linked window: one tmed_validate_blocks call vs the seven "
+                                      "existing calls + host proposer scan and compares", "runs": runs, "shapes": out}
+
+
 def votes(eng, runs: int, cpu: bool, shapes=(10_000, 175)):
     """One round of free-standing votes per shape: nvals prevotes and nvals precommits at one step
     against an nvals-validator set held as an explicit key set (the key-cached kernels on both routes).
@@ -1424,6 +1586,9 @@ def main():
     ap.add_argument("--evidence-shapes", default="2048x10000,1000x4x175",
                     help="evidence: NxV (one list of N evidences, V validators) or LxKxV (L lists of K), comma-separated")
     ap.add_argument("--lca-shapes", default="1x10000,50x175", help="lca: ExV (E evidences, V validators), comma-separated")
+    ap.add_argument("--vb-shapes", default="1000x10000,10000x175", help="vb: BxV (B linked blocks, V validators), comma-separated")
+    ap.add_argument("--vb-route", choices=["both", "fused", "composed"], default="both",
+                    help="vb: time both routes alternated (default), or one alone (a profiler run per route)")
     ap.add_argument("--rule", choices=["go", "zip215"], default="go",
                     help="the context's signature rule for every leg (tmed_set_rule): go, the default, or zip215")
     args = ap.parse_args()
@@ -1444,6 +1609,8 @@ def main():
             r = c3v(eng, args.headers, args.gap, args.c3_policy, args.runs)
         elif cfg == "mt" and rank == 0:
             r = mt(eng, args.runs)
+        elif cfg == "vb" and rank == 0:
+            r = vb(eng, args.runs, tuple(args.vb_shapes.split(",")), args.vb_route)
         elif cfg == "votes" and rank == 0:
             r = votes(eng, args.runs, not args.no_cpu)
         elif cfg == "evidence" and rank == 0:

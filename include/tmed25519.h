@@ -1314,6 +1314,203 @@ int tmed_verify_light_client_attacks_with(const tmed_lca_request *reqs, size_t n
                                           const uint8_t *trusted_hashes, const uint8_t *trusted_ok,
                                           tmed_batch_verify_fn verify, void *user);
 
+/* ------------------------------------------------- block validation: validateBlock */
+
+/*
+ * validateBlock (state/validation.go:15-151) with the Block.ValidateBasic it runs first
+ * (types/block.go:55-106) for n blocks in one call: what blocksync runs twice per block
+ * (blockchain/v0/reactor.go:371 and ApplyBlock, state/execution.go) and consensus on every proposal.
+ * (The section stands behind the evidence section, whose tmed_dup_evidence the batch carries.)
+ *
+ * tmed_block_state: the fields of State that validateBlock reads.
+ */
+#define TMED_VB_KNOW_APP_HASH 1u
+#define TMED_VB_KNOW_CONSENSUS_HASH 2u
+#define TMED_VB_KNOW_LAST_RESULTS_HASH 4u
+#define TMED_VB_KNOW_VALIDATORS 8u
+#define TMED_VB_KNOW_NEXT_VALIDATORS 16u
+#define TMED_VB_KNOW_ALL 31u
+
+typedef struct {
+  uint64_t version_block, version_app; /* state.Version.Consensus */
+  const char *chain_id;
+  uint32_t chain_id_len;
+  int64_t initial_height, last_block_height;
+  tmed_block_id last_block_id;
+  int64_t last_block_time_seconds;     /* LastBlockTime.Unix() */
+  int32_t last_block_time_nanos;       /* LastBlockTime.Nanosecond() */
+  const uint8_t *app_hash;
+  uint32_t app_hash_len;
+  const uint8_t *consensus_hash;       /* HashConsensusParams(state.ConsensusParams): 32 bytes from the caller (one
+                                          SHA-256 of an 18-byte proto) */
+  const uint8_t *last_results_hash;
+  uint32_t last_results_hash_len;
+  const tmed_valset *validators;       /* may be NULL iff TMED_VB_KNOW_VALIDATORS is clear: the proposer lookup is then
+                                          skipped with the hash check; `pubkeys`, `powers` and `addresses` are read */
+  const tmed_valset *next_validators;  /* may be NULL iff TMED_VB_KNOW_NEXT_VALIDATORS is clear */
+  const tmed_valset *last_validators;  /* VerifyCommit and MedianTime of LastCommit: everything tmed_verify_commits
+                                          and tmed_median_times read.  May be NULL for a block at the initial height */
+  int64_t evidence_max_bytes;          /* state.ConsensusParams.Evidence.MaxBytes */
+  /*
+   * A mask of TMED_VB_KNOW_*.  AppHash, LastResultsHash, the consensus params and the two validator
+   * sets exist only after ApplyBlock of the previous block, so a blocksync window validated ahead of
+   * execution does not have them (or has a prediction: a predicted set WITH its bit set is checked
+   * against the header's hash like a known one).  A check whose bit is clear is skipped, and the bit
+   * is set in the result's `skipped` when the replay reached the check.  THE CALLER'S DUTY: a skipped
+   * check is not a passed one.  When code == TMED_VB_OK the caller evaluates the skipped checks in Go
+   * before it relies on the block; when code != TMED_VB_OK and a skipped check orders before `code`,
+   * the caller evaluates the skipped checks in Go first, since the reference would have reported the
+   * first of them that fails.
+   */
+  uint32_t known;
+} tmed_block_state;
+
+#define TMED_VB_LINK_PREV 1u /* request flag, blocks i >= 1 (TMED_EINVAL on block 0): the state's last_block_id.hash,
+                                last_block_height and last block time are block i-1's of the same call, not the `state`
+                                struct's: the hash is Header.Hash() of block i-1 computed on the device in this call (a
+                                nil hash compares as empty bytes), the height and the time are its header's.  The
+                                PartSetHeader half of LastBlockID still comes from state->last_block_id (the caller has
+                                it from tmed_partset_roots / MakePartSet, reactor.go:359-361).  A failure of request
+                                i-1 does not change request i's outcome: the caller stops at the first failure. */
+
+typedef struct {
+  const tmed_header *header;
+  const tmed_commit *last_commit;  /* may be NULL when commit_basic_ok == 0 (a nil LastCommit); with n_sigs > 0 its
+                                      flags, addresses, ts_seconds, ts_nanos and sigs must all be given */
+  const tmed_block_state *state;
+  int64_t evidence_byte_size;      /* block.Evidence.ByteSize(), computed by the caller */
+  uint8_t header_basic_ok;         /* Header.ValidateBasic() == nil, run in Go as basic_ok of tmed_light_request is */
+  uint8_t commit_basic_ok;         /* LastCommit != nil && LastCommit.ValidateBasic() == nil */
+  int32_t evidence_basic_bad;      /* -1, or the index of the first evidence whose ValidateBasic fails */
+  uint32_t flags;                  /* TMED_VB_LINK_PREV */
+} tmed_block_request;
+
+/*
+ * n blocks.  The transactions are the arrays of tmed_txs_hashes (block b's are [block_off[b],
+ * block_off[b+1]); block_off == NULL: no block has transactions).  The evidence is the arrays of
+ * tmed_evidence_hashes with list b belonging to block b (list_off == NULL: no block has evidence;
+ * `opaque` / `opaque_off` carry LightClientAttackEvidence).
+ */
+typedef struct {
+  size_t n;
+  const tmed_block_request *blocks;
+  const uint8_t *txs;
+  const uint64_t *tx_off;
+  const uint32_t *block_off;
+  const tmed_dup_evidence *ev;
+  const int64_t *items;
+  const uint32_t *list_off;
+  const uint8_t *opaque;
+  const uint64_t *opaque_off;
+} tmed_block_batch;
+
+/* Outcome codes, numbered in the order the reference checks; the first failing check wins. */
+#define TMED_VB_OK 0
+#define TMED_VB_HEADER_BASIC 1          /* types/block.go:63-65 "invalid header: %w": header_basic_ok == 0 (the caller
+                                           re-runs the Go method for the text) */
+#define TMED_VB_COMMIT_BASIC 2          /* block.go:68-73 "nil LastCommit" / "wrong LastCommit: %v": commit_basic_ok == 0 */
+#define TMED_VB_LAST_COMMIT_HASH 3      /* block.go:75-80: hash = LastCommit.Hash() */
+#define TMED_VB_DATA_HASH 4             /* block.go:83-89: hash = Data.Hash() */
+#define TMED_VB_EVIDENCE_BASIC 5        /* block.go:92-96 "invalid evidence (#%d): %v": idx = evidence_basic_bad */
+#define TMED_VB_EVIDENCE_HASH 6         /* block.go:98-103: hash = Evidence.Hash() */
+#define TMED_VB_VERSION 7               /* state/validation.go:22-28 */
+#define TMED_VB_CHAIN_ID 8              /* :29-34 */
+#define TMED_VB_HEIGHT_INITIAL 9        /* :35-38: LastBlockHeight == 0 and Height != InitialHeight */
+#define TMED_VB_HEIGHT 10               /* :39-44: LastBlockHeight > 0 and Height != LastBlockHeight + 1 */
+#define TMED_VB_LAST_BLOCK_ID 11        /* :46-51: hash / hash_len = the linked request's computed Header.Hash() */
+#define TMED_VB_APP_HASH 12             /* :54-59 */
+#define TMED_VB_CONSENSUS_HASH 13       /* :60-66 */
+#define TMED_VB_LAST_RESULTS_HASH 14    /* :67-72 */
+#define TMED_VB_VALIDATORS_HASH 15      /* :73-78: hash = state.Validators.Hash() */
+#define TMED_VB_NEXT_VALIDATORS_HASH 16 /* :79-84: hash = state.NextValidators.Hash() */
+#define TMED_VB_INITIAL_HAS_SIGS 17     /* :87-90 "initial block can't have LastCommit signatures" */
+#define TMED_VB_LAST_COMMIT 18          /* :93-96: state.LastValidators.VerifyCommit failed; its tmed_commit_result in
+                                           `commit`, TMED_COMMIT_PANIC included (the caller runs Go, which panics) */
+#define TMED_VB_PROPOSER_SIZE 19        /* :102-107: len(ProposerAddress) != 20 */
+#define TMED_VB_PROPOSER_UNKNOWN 20     /* :108-112: !state.Validators.HasAddress(ProposerAddress) */
+#define TMED_VB_TIME_NOT_AFTER 21       /* :117-122: Height > InitialHeight and !Time.After(LastBlockTime) */
+#define TMED_VB_TIME_NOT_MEDIAN 22      /* :123-129: !Time.Equal(MedianTime(LastCommit, LastValidators)); the median in
+                                           median_seconds / median_nanos */
+#define TMED_VB_TIME_NOT_GENESIS 23     /* :131-138: Height == InitialHeight and !Time.Equal(LastBlockTime) */
+#define TMED_VB_HEIGHT_BELOW_INITIAL 24 /* :140-142: the switch's default, reached whatever last_block_height is */
+#define TMED_VB_EVIDENCE_OVERFLOW 25    /* :146-148 ErrEvidenceOverflow{evidence_max_bytes, evidence_byte_size} */
+#define TMED_VB_GO_PATH 26              /* the structs cannot decide the check the replay has reached: ok = 0 from
+                                           Commit.Hash or EvidenceList.Hash (tmed_commit_hashes / tmed_evidence_hashes
+                                           say when), TMED_MEDIAN_GO_PATH, or a block time or last block time outside
+                                           the proto Timestamp range (documented at tmed_commit_hashes) at the time
+                                           checks.  The caller runs the Go function; the other requests are unaffected */
+
+typedef struct {
+  int code;
+  uint32_t skipped;          /* TMED_VB_KNOW_* bits of the checks the replay reached and skipped */
+  uint32_t hash_len;         /* 32 with the hash codes; LAST_BLOCK_ID of a linked request: 32, or 0 for a nil hash */
+  uint8_t hash[32];          /* the computed value for LAST_COMMIT_HASH, DATA_HASH, EVIDENCE_HASH, VALIDATORS_HASH,
+                                NEXT_VALIDATORS_HASH and (linked) LAST_BLOCK_ID */
+  tmed_commit_result commit; /* LAST_COMMIT: the failing VerifyCommit's result (else zero) */
+  int64_t median_seconds;    /* TIME_NOT_MEDIAN: MedianTime as (Unix(), Nanosecond()) */
+  int32_t median_nanos;
+  int32_t idx;               /* EVIDENCE_BASIC: the evidence index */
+  int32_t proposer_idx;      /* the first validator of state.Validators with ProposerAddress, where the lookup ran
+                                and found one; else -1 */
+  uint32_t verified;         /* signatures sent to the verifier for this block's VerifyCommit */
+} tmed_block_result;
+
+/*
+ * The replay follows validation.go literally (csrc/validate_host.h validate_run), the `switch` on the
+ * height included.  Times are compared as Go's After / Equal on (seconds, nanoseconds); bytes.Equal
+ * against a header field of another length than the computed hash's is a mismatch.  It runs in two
+ * phases, so that a request failing an earlier check sends no signatures:
+ *   A  for the requests that pass the two basic checks: Commit.Hash, Data.Hash, EvidenceList.Hash,
+ *      Header.Hash (of block i-1 of every linked request i) and ValidatorSet.Hash of the known sets,
+ *      each distinct tmed_valset pointer once per call (a linked window over a constant set hashes it
+ *      once; tmed_valset.set_hash is a cache key and is never trusted here);
+ *   B  for the requests that pass everything through INITIAL_HAS_SIGS: VerifyCommit (the commit seam
+ *      in TMED_MODE_COMMIT under the context's rule, key-set cache and pipelining as for
+ *      tmed_verify_commits), MedianTime and the proposer lookup.
+ *
+ * Device work of tmed_validate_blocks: phase A's hashes by the kernels of tmed_commit_hashes,
+ * tmed_txs_hashes, tmed_evidence_hashes, tmed_header_hashes and tmed_valset_hashes under ONE hold of
+ * the context's lock.  The last commits' flags, addresses, timestamps and signatures are copied to the
+ * device once per call, into an arena of their own: the CommitSig leaf kernel reads them there and so
+ * do the median kernels of phase B (the verifier keeps its candidate staging: it packs only the
+ * signatures the loop reaches, with key references).  Every hash routine leaves its roots on the device
+ * as well; block_check_kernel (csrc/validate.hip): one wavefront per block, four blocks per 256-thread
+ * workgroup, compares the header's 32-byte fields with those device-resident hashes (48 lanes, one
+ * dword each, one ballot) and writes one uint32 mask of mismatches per block, and the same wave runs
+ * GetByAddress for ProposerAddress over the set's staged addresses (the scan of
+ * evidence_lookup_kernel; each distinct set's addresses staged once).  The decision reads only the
+ * masks and the proposer indexes; the computed hashes are also copied back, for the error values.
+ * Phase B: the commit seam, then the median kernels over the arena's arrays, for the blocks whose
+ * commit verified.  The call takes the context's lock three times, one hold after the other (phase A,
+ * the commit seam, the medians), as tmed_light_verify takes its own; another call on the context may
+ * run between them (a second tmed_validate_blocks refills the arena: the medians then stage their
+ * commits themselves).  Submitted blocksync windows are collected first, as by every seam call.  After
+ * the call tmed_last_kernel_ms reports the median kernels' time and tmed_validate_kernel_ms
+ * block_check_kernel's.
+ * TMED_EINVAL for malformed calls only: a NULL struct or array that is read, TMED_VB_LINK_PREV on
+ * block 0, unknown flags or `known` bits, a NULL set whose bit is set, transaction or evidence arrays
+ * tmed_txs_hashes / tmed_evidence_hashes would refuse.  Both entries check the same things.
+ *
+ * tmed_validate_blocks_with: the same replay with no device: every hash (n x 32 each, with n ok
+ * bytes where the hash can be nil or undecidable: commit_ok, evidence_ok, header_ok; header_hashes[i]
+ * is Header.Hash() of block i, read for block i+1's link), the medians (medians[i] for block i), the
+ * proposer lookups (proposer_idx[i], -1 for nobody) and the batch verifier are the caller's; the
+ * compares block_check_kernel makes run on the host.  The CPU test-suite drives it with the oracle.
+ */
+int tmed_validate_blocks(tmed_ctx *ctx, const tmed_block_batch *batch, tmed_block_result *out);
+int tmed_validate_blocks_with(const tmed_block_batch *batch, tmed_block_result *out, const uint8_t *commit_hashes,
+                              const uint8_t *commit_ok, const uint8_t *data_hashes, const uint8_t *evidence_hashes,
+                              const uint8_t *evidence_ok, const uint8_t *header_hashes, const uint8_t *header_ok,
+                              const uint8_t *validators_hashes, const uint8_t *next_validators_hashes,
+                              const tmed_median_result *medians, const int32_t *proposer_idx,
+                              tmed_batch_verify_fn verify, void *user);
+/* block_check_kernel's device time (ms) in the context's last tmed_validate_blocks. */
+float tmed_validate_kernel_ms(tmed_ctx *ctx);
+/* Counters of the context's last tmed_validate_blocks: out[0] the validator sets whose ValidatorSet.Hash
+ * was computed (distinct tmed_valset pointers), out[1] the sets whose addresses were staged for the
+ * proposer lookup, out[2] the blocks block_check_kernel took. */
+int tmed_validate_stats(tmed_ctx *ctx, uint64_t out[3]);
+
 /* ------------------------------------------------- blocksync replay (f4) */
 
 /*

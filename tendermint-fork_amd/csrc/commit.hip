@@ -38,6 +38,8 @@
 #include "votes_host.h"
 #include "evidence_host.h"
 #include "lca_host.h"
+#include "median_host.h"
+#include "validate_host.h"
 
 // One translation unit, by role (each header is included here only, in this order):
 //   seam_host.h   planning, aliasing, staging groups, scatter, replay: host C++ only
@@ -45,7 +47,7 @@
 //   blocksync.h   the context's pipelined batch stream and the tmed_blocksync_* entry points
 //                 (c_guard.h: the entry points' wrapper; debug_zero.h: diagnostics)
 // This file: the verify path of one seam call, the light client's hashes, the tmed_verify_commits,
-// tmed_light_verify, tmed_verify_light_client_attacks and *_multi entry points.
+// tmed_light_verify, tmed_verify_light_client_attacks, tmed_validate_blocks and *_multi entry points.
 #include "seam_host.h"
 #include "kc_resolve.h"
 #include "blocksync.h"
@@ -384,6 +386,46 @@ extern "C" int tmed_verify_light_client_attacks(tmed_ctx *ctx, const tmed_lca_re
           return tmed::locked(ctx, /*collect=*/true, [&] {
             return tmed::lca_tail_locked(ctx, reqs, live, ch, cok, need, kinds, byz, byz_off, bres, ev_hash);
           });
+        });
+  });
+}
+
+// ---- validateBlock (state/validation.go:15-151; the replay is validate_host.h) ---------------------
+// Three holds of the context's lock, one after the other, as tmed_light_verify takes its own: phase A
+// (validate.hip validate_hashes_locked: the last commits staged once into the arena, the hashes, then
+// block_check_kernel's masks and proposer indexes; submitted blocksync windows are collected first),
+// VerifyCommit as tmed_verify_commits runs it (the seam takes and drops the lock itself, so the call
+// cannot keep one hold across it), then MedianTime over the arena's arrays.  Another call on the
+// context may run between the holds: a second tmed_validate_blocks would refill the arena, which the
+// arena's generation shows, and the medians then stage their commits as tmed_median_times does; and the
+// diagnostics (tmed_last_kernel_ms, tmed_validate_kernel_ms, tmed_validate_stats) are the context's
+// last writer's, as for every call.
+extern "C" int tmed_validate_blocks(tmed_ctx *ctx, const tmed_block_batch *batch, tmed_block_result *out) {
+  if (!ctx) return TMED_EINVAL;
+  const int rule = tmed::seam_rule(ctx);
+  return c_guard(ctx, [&] {
+    tmed::CommitArena arena;
+    tmed::MedShared shared{nullptr, {}};
+    uint64_t gen = 0;
+    return tmed_validate::validate_run(
+        batch, out,
+        [&](const tmed_validate::Plan &plan, tmed_validate::Hashes &H) {
+          return tmed::locked(ctx, /*collect=*/true,
+                              [&] { return tmed::validate_hashes_locked(ctx, plan, H, &shared, &arena, &gen); });
+        },
+        [&](const tmed_median_request *mreqs, const std::vector<size_t> &m_of, tmed_median_result *mres,
+            const std::vector<size_t> &, int32_t *) {  // the proposers came with phase A
+          const size_t m = m_of.size();
+          for (size_t j = 0; j < m; j++)
+            if (tmed_median::check_request(mreqs[j]) != TMED_OK) return (int)TMED_EINVAL;
+          if (m == 0) return (int)TMED_OK;
+          return tmed::locked(ctx, /*collect=*/true, [&] {
+            const bool mine = shared.arena && gen == ctx->vb_gen;  // the arena still holds this call's commits
+            return tmed::median_times_locked(ctx, mreqs, m, mres, mine ? &shared : nullptr);
+          });
+        },
+        [&](const tmed_commit_request *rq, size_t m, tmed_commit_result *res) {
+          return verify_commits_impl(ctx, rq, m, res, rule);
         });
   });
 }

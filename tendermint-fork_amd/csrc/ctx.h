@@ -15,6 +15,10 @@
 
 struct tmed_ctx;
 struct BsStream;  // blocksync.h: the context's blocksync batch stream
+namespace tmed_validate {  // validate_host.h
+struct Plan;
+struct Hashes;
+}  // namespace tmed_validate
 
 namespace tmed {
 
@@ -142,12 +146,52 @@ void bs_release_collected(tmed_ctx *c);
 // of n_sets sets as tmed_header_hashes / tmed_valset_hashes compute them, arguments already checked;
 // ctx->mu held.
 bool header_pointers_ok(const tmed_header &h);  // no NULL array with a non-zero length
-int header_hashes_locked(tmed_ctx *c, const tmed_header *headers, size_t n, uint8_t *out, uint8_t *ok);
+// d_keep (nullable, device memory): the hashes are copied there too, on the stream, for a caller that
+// reads them on the device (validate.hip); header_hashes_locked's rows: see merkle.hip.
+int header_hashes_locked(tmed_ctx *c, const tmed_header *headers, size_t n, uint8_t *out, uint8_t *ok,
+                         uint8_t *d_keep = nullptr, uint32_t *row_of = nullptr);
+// the same over pointers to headers that lie apart (validate.hip: nothing is copied)
+int header_hashes_locked(tmed_ctx *c, const tmed_header *const *headers, size_t n, uint8_t *out, uint8_t *ok,
+                         uint8_t *d_keep = nullptr, uint32_t *row_of = nullptr);
 int valset_hashes_locked(tmed_ctx *c, const uint8_t *pubkeys, const int64_t *powers, const uint32_t *set_off,
-                         size_t n_sets, uint8_t *out);
-int valsets_hashes_locked(tmed_ctx *c, const tmed_valset *const *sets, size_t n_sets, uint8_t *out);
+                         size_t n_sets, uint8_t *out, uint8_t *d_keep = nullptr);
+int valsets_hashes_locked(tmed_ctx *c, const tmed_valset *const *sets, size_t n_sets, uint8_t *out,
+                          uint8_t *d_keep = nullptr);
+// The last commits of one tmed_validate_blocks call staged once (tmed_ctx::vb_commit, by
+// commit_hashes_held): device pointers of the arrays the CommitSig leaf kernel read, the raw flags
+// beside them, and the roots; base[j]: commit j's first signature there ((size_t)-1: not staged).
+struct CommitArena {
+  const uint8_t *flags = nullptr, *addr = nullptr, *roots = nullptr;
+  const int64_t *sec = nullptr;
+  const int32_t *nanos = nullptr;
+  std::vector<size_t> base;
+};
+// median.hip's view of it: where each commit pointer's signatures start.
+struct MedShared {
+  const CommitArena *arena;
+  std::unordered_map<const tmed_commit *, size_t> base;
+};
+// merkle.hip / evidence.hip, for block validation (validate.hip): Commit.Hash, Data.Hash and
+// EvidenceList.Hash as tmed_commit_hashes, tmed_txs_hashes and tmed_evidence_hashes compute them, for a
+// caller that holds ctx->mu and has collected the submitted windows (held = true).
+// shared / d_keep: as above (the commits go to the arena tmed_ctx::vb_commit and stay there).
+int commit_hashes_held(tmed_ctx *c, const tmed_commit *const *commits, size_t n, uint8_t *out, uint8_t *ok,
+                       CommitArena *shared = nullptr);
+int txs_hashes_held(tmed_ctx *c, const uint8_t *txs, const uint64_t *tx_off, const uint32_t *block_off, size_t n_blocks,
+                    uint8_t *out, uint8_t *d_keep = nullptr);
+int evidence_hashes_body(tmed_ctx *c, const tmed_dup_evidence *ev, const int64_t *items, const uint32_t *list_off,
+                         size_t n_lists, const uint8_t *opaque, const uint64_t *opaque_off, uint8_t *ev_hashes,
+                         uint8_t *roots, uint8_t *ev_ok, uint8_t *list_ok, bool held, uint8_t *d_keep = nullptr);
+// validate.hip: phase A of tmed_validate_blocks (validate_host.h Plan -> Hashes: the hashes, the compare
+// masks and the proposer indexes of block_check_kernel); ctx->mu held.
+// arena: receives the staged commits (its generation in *gen: tmed_ctx::vb_gen when it was filled).
+int validate_hashes_locked(tmed_ctx *c, const tmed_validate::Plan &plan, tmed_validate::Hashes &H, MedShared *shared,
+                           CommitArena *arena, uint64_t *gen);
 // median.hip: tmed_median_times over n checked requests (median_host.h check_request); ctx->mu held.
-int median_times_locked(tmed_ctx *c, const tmed_median_request *reqs, size_t n, tmed_median_result *out);
+// shared (nullable): the commits' flags, addresses and timestamps are already on the device (the arena
+// of the same tmed_validate_blocks call); the kernels read them there and only the sets are staged.
+int median_times_locked(tmed_ctx *c, const tmed_median_request *reqs, size_t n, tmed_median_result *out,
+                        const MedShared *shared = nullptr);
 // votes.hip: tmed_verify_votes over n checked requests (votes_host.h check_request) whose sets the
 // key-set cache has resolved; ctx->mu held.
 int verify_votes_locked(tmed_ctx *c, const tmed_vote_request *reqs, size_t n, uint8_t *codes);
@@ -367,6 +411,11 @@ struct tmed_ctx {
   float last_vote_prep_ms = 0.f;
   hipEvent_t ev_lookup = nullptr;        // the end of evidence_lookup_kernel (evidence.hip)
   float last_ev_ms[2] = {0.f, 0.f};      // evidence_lookup_kernel, evidence_prepare_kernel (tmed_evidence_kernel_times)
+  float last_vb_ms = 0.f;                // block_check_kernel (tmed_validate_kernel_ms)
+  uint64_t vb_stats[3] = {0, 0, 0};      // the last tmed_validate_blocks (tmed_validate_stats)
+  tmed::Staged vb_commit;                // the last commits of a tmed_validate_blocks call, staged once (CommitArena)
+  uint64_t vb_gen = 0;                   // counts the fillings of vb_commit: a later hold sees whether it is still its own
+  tmed::DevBuf d_vb;                     // phase A's hashes as rows of 32 bytes, read by block_check_kernel
   float last_lca_ms[2] = {0.f, 0.f};     // lca_lookup_kernel (its end is ev_lookup too), lca_rank_kernel (tmed_lca_kernel_times)
   tmed::DevBuf d_korder;  // key-grouped order of a key-cached batch: counts / cursors + permutation
   tmed::DevBuf d_zip;     // ZIP-215 batch mode scratch (zip215.hip zip_bufs: points, digits, sort, buckets)

@@ -372,6 +372,7 @@ struct EvHashCall {
   const uint8_t *opaque;
   const uint64_t *opaque_off;
   std::vector<uint32_t> counts;  // items per list
+  uint8_t *d_keep = nullptr;     // device memory that also receives the T roots (validate.hip)
 };
 
 // Evidences (host) -> hashes and roots (host; not yet zeroed where ev_ok / list_ok is 0).  ctx->mu held.
@@ -425,6 +426,7 @@ int evidence_hashes_locked(tmed_ctx *c, const EvHashCall &a, uint8_t *ev_hashes,
   if (e == hipSuccess) e = hipEventRecord(c->ev1, s);
   if (e == hipSuccess && T) e = merkle_build_levels(c, plan, s);
   if (e == hipSuccess && T) e = merkle_emit_roots(c, plan, d + o_roots, s);
+  if (e == hipSuccess && T && a.d_keep) e = hipMemcpyAsync(a.d_keep, d + o_roots, 32 * T, hipMemcpyDeviceToDevice, s);
   if (e == hipSuccess && n + T) e = hipMemcpyAsync(h + o_hash, d + o_hash, o_evleaf - o_hash, hipMemcpyDeviceToHost, s);
   rc = finish_call(c, s, e, &c->last_ms);
   if (rc != TMED_OK) return rc;
@@ -435,26 +437,16 @@ int evidence_hashes_locked(tmed_ctx *c, const EvHashCall &a, uint8_t *ev_hashes,
 
 }  // namespace
 
-}  // namespace tmed
-
-extern "C" {
-
-int tmed_evidence_kernel_times(tmed_ctx *c, float ms[2]) {
-  if (!c || !ms) return TMED_EINVAL;
-  ms[0] = c->last_ev_ms[0];
-  ms[1] = c->last_ev_ms[1];
-  return TMED_OK;
-}
-
-int tmed_evidence_hashes(tmed_ctx *c, const tmed_dup_evidence *ev, const int64_t *items, const uint32_t *list_off,
+// tmed_evidence_hashes inside the guard.  held: the caller holds ctx->mu already and has collected the
+// submitted windows (validate.hip).
+int evidence_hashes_body(tmed_ctx *c, const tmed_dup_evidence *ev, const int64_t *items, const uint32_t *list_off,
                          size_t n_lists, const uint8_t *opaque, const uint64_t *opaque_off, uint8_t *ev_hashes,
-                         uint8_t *roots, uint8_t *ev_ok, uint8_t *list_ok) {
-  using namespace tmed;
+                         uint8_t *roots, uint8_t *ev_ok, uint8_t *list_ok, bool held, uint8_t *d_keep) {
   if (!c || !ev || !tmed_evidence_host::evidence_arrays_ok(*ev)) return TMED_EINVAL;
   if (n_lists && (!list_off || !roots || list_off[0] != 0)) return TMED_EINVAL;
   if (n_lists > 0x7fffffffu) return TMED_EINVAL;
-  return guarded([&] {
-    EvHashCall a{ev, items, n_lists ? list_off[n_lists] : 0, n_lists, 0, opaque, opaque_off, {}};
+  {
+    EvHashCall a{ev, items, n_lists ? list_off[n_lists] : 0, n_lists, 0, opaque, opaque_off, {}, d_keep};
     if (a.K && !items) return (int)TMED_EINVAL;
     a.counts.resize(n_lists);
     for (size_t l = 0; l < n_lists; l++) {
@@ -485,7 +477,8 @@ int tmed_evidence_hashes(tmed_ctx *c, const tmed_dup_evidence *ev, const int64_t
       ok[i] = evidence_encodable(va, vb, r);
     }
     if (ev->n + n_lists == 0) return (int)TMED_OK;
-    const int rc = locked(c, /*collect=*/true, [&] { return evidence_hashes_locked(c, a, ev_hashes, roots); });
+    const int rc = held ? evidence_hashes_locked(c, a, ev_hashes, roots)
+                        : locked(c, /*collect=*/true, [&] { return evidence_hashes_locked(c, a, ev_hashes, roots); });
     if (rc != TMED_OK) return rc;
     for (size_t i = 0; i < ev->n; i++) {
       if (ev_ok) ev_ok[i] = ok[i];
@@ -498,6 +491,27 @@ int tmed_evidence_hashes(tmed_ctx *c, const tmed_dup_evidence *ev, const int64_t
       if (!good) memset(roots + 32 * l, 0, 32);
     }
     return (int)TMED_OK;
+  }
+}
+
+}  // namespace tmed
+
+extern "C" {
+
+int tmed_evidence_kernel_times(tmed_ctx *c, float ms[2]) {
+  if (!c || !ms) return TMED_EINVAL;
+  ms[0] = c->last_ev_ms[0];
+  ms[1] = c->last_ev_ms[1];
+  return TMED_OK;
+}
+
+int tmed_evidence_hashes(tmed_ctx *c, const tmed_dup_evidence *ev, const int64_t *items, const uint32_t *list_off,
+                         size_t n_lists, const uint8_t *opaque, const uint64_t *opaque_off, uint8_t *ev_hashes,
+                         uint8_t *roots, uint8_t *ev_ok, uint8_t *list_ok) {
+  if (!c) return TMED_EINVAL;
+  return guarded([&] {
+    return tmed::evidence_hashes_body(c, ev, items, list_off, n_lists, opaque, opaque_off, ev_hashes, roots, ev_ok, list_ok,
+                                      /*held=*/false, nullptr);
   });
 }
 

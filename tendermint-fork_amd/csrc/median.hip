@@ -250,7 +250,11 @@ static bool med_candidate(const tmed_commit &cm, const tmed_valset &vs) {
   return true;
 }
 
-int median_times_locked(tmed_ctx *c, const tmed_median_request *reqs, size_t n, tmed_median_result *out) {
+int median_times_locked(tmed_ctx *c, const tmed_median_request *reqs, size_t n, tmed_median_result *out,
+                        const MedShared *shared) {
+  if (shared)  // every commit of the call must lie in the arena, else the call stages as usual
+    for (size_t i = 0; i < n && shared; i++)
+      if (!shared->base.count(reqs[i].commit)) shared = nullptr;
   std::vector<size_t> dev, big, host;  // request indexes: wave shape (then the block shape appended) / host route
   for (size_t i = 0; i < n; i++) {
     const tmed_commit &cm = *reqs[i].commit;
@@ -270,7 +274,9 @@ int median_times_locked(tmed_ctx *c, const tmed_median_request *reqs, size_t n, 
     std::vector<size_t> coff, soff;
     size_t Nc = 0, Ns = 0;
     for (const size_t i : dev) {
-      if (cbase.emplace(reqs[i].commit, Nc).second) {
+      if (shared) {
+        cbase.emplace(reqs[i].commit, shared->base.find(reqs[i].commit)->second);
+      } else if (cbase.emplace(reqs[i].commit, Nc).second) {
         commits.push_back(reqs[i].commit);
         coff.push_back(Nc);
         Nc += reqs[i].commit->n_sigs;
@@ -305,8 +311,10 @@ int median_times_locked(tmed_ctx *c, const tmed_median_request *reqs, size_t n, 
       memcpy(h + lay.power + 8 * soff[k], vs.powers, 8 * vs.n);
       memcpy(h + lay.saddr + 20 * soff[k], vs.addresses, 20 * vs.n);
     });
-    const MedArrays arr{d + lay.flags, d + lay.caddr, (const int64_t *)(d + lay.sec), (const int32_t *)(d + lay.nanos),
-                        d + lay.saddr, (const int64_t *)(d + lay.power)};
+    const MedArrays arr = shared ? MedArrays{shared->arena->flags, shared->arena->addr, shared->arena->sec,
+                                             shared->arena->nanos, d + lay.saddr, (const int64_t *)(d + lay.power)}
+                                 : MedArrays{d + lay.flags, d + lay.caddr, (const int64_t *)(d + lay.sec),
+                                             (const int32_t *)(d + lay.nanos), d + lay.saddr, (const int64_t *)(d + lay.power)};
     const MedPair *dp = reinterpret_cast<const MedPair *>(d + lay.pairs);
     MedOut *dout = reinterpret_cast<MedOut *>(d + lay.out);
     e = hipMemcpyAsync(d, h, lay.out, hipMemcpyHostToDevice, s);  // one copy in

@@ -509,8 +509,11 @@ hipError_t hash_host_leaves(tmed_ctx *c, const uint8_t *leaves, const uint64_t *
 
 // Leaves on the host -> roots on the host: the common driver of the byte-slice root calls (the
 // transactions' leaf kernel is timed for tmed_last_kernel_ms).  ctx->mu held.
+// d_keep: device memory that also receives the T roots (a copy on the stream, for a caller that reads
+// them there: validate.hip).
 int roots_from_host_leaves_locked(tmed_ctx *c, const uint8_t *leaves, const uint64_t *leaf_off, size_t L,
-                                  const std::vector<uint32_t> &counts, uint8_t *roots, bool txs = false) {
+                                  const std::vector<uint32_t> &counts, uint8_t *roots, bool txs = false,
+                                  uint8_t *d_keep = nullptr) {
   const MerkleLevels plan(counts);
   const size_t T = counts.size();
   (void)hipSetDevice(c->device);
@@ -521,6 +524,7 @@ int roots_from_host_leaves_locked(tmed_ctx *c, const uint8_t *leaves, const uint
   if (e == hipSuccess) e = hash_host_leaves(c, leaves, leaf_off, L, txs, /*timed=*/txs, s);
   if (e == hipSuccess) e = build_levels(c, plan, s);
   if (e == hipSuccess) e = emit_roots(c, plan, (uint8_t *)c->d_out.p, s);
+  if (e == hipSuccess && d_keep) e = hipMemcpyAsync(d_keep, c->d_out.p, T * 32, hipMemcpyDeviceToDevice, s);
   if (e == hipSuccess) e = hipMemcpyAsync(roots, c->d_out.p, T * 32, hipMemcpyDeviceToHost, s);
   return finish_call(c, s, e, txs ? &c->last_ms : nullptr);
 }
@@ -528,15 +532,20 @@ int roots_from_host_leaves_locked(tmed_ctx *c, const uint8_t *leaves, const uint
 // ---- Commit.Hash (types/block.go:894-912) ---------------------------------------------------
 // The commits' arrays of one call, packed per kind: region offsets for N signatures.
 struct CsigLayout {
-  size_t sig, sec, meta, nanos, addr, roots, total;
-  CsigLayout(size_t N, size_t n_commits) {
+  size_t sig, sec, meta, nanos, addr, roots, flags, total;  // flags: the raw BlockIDFlag bytes, for a shared arena only
+  bool with_flags;
+  CsigLayout(size_t N, size_t n_commits, bool with_flags_ = false) : with_flags(with_flags_) {
     sig = 0;
     sec = align256(sig + 64 * N);
     meta = align256(sec + 8 * N);
     nanos = align256(meta + 4 * N);
     addr = align256(nanos + 4 * N);
     roots = align256(addr + 20 * N);
-    total = roots + 32 * n_commits;
+    flags = total = roots + 32 * n_commits;
+    if (with_flags) {
+      flags = align256(total);
+      total = flags + N;
+    }
   }
 };
 
@@ -563,6 +572,7 @@ int commit_scan(const tmed_commit &cm) {
 void commit_pack(const tmed_commit &cm, uint8_t *h, const CsigLayout &lay, size_t base) {
   const size_t n = cm.n_sigs;
   if (n == 0) return;
+  if (lay.with_flags) memcpy(h + lay.flags + base, cm.flags, n);
   if (cm.sigs) memcpy(h + lay.sig + 64 * base, cm.sigs, 64 * n);
   memcpy(h + lay.sec + 8 * base, cm.ts_seconds, 8 * n);
   memcpy(h + lay.nanos + 4 * base, cm.ts_nanos, 4 * n);
@@ -575,8 +585,17 @@ void commit_pack(const tmed_commit &cm, uint8_t *h, const CsigLayout &lay, size_
   }
 }
 
+// Element i of an array of structs or of an array of pointers to them: the hash bodies below take
+// either (a caller whose structs lie apart passes the pointers and copies nothing).
+template <class T>
+inline const T &item(const T *a, size_t i) { return a[i]; }
+template <class T>
+inline const T &item(const T *const *a, size_t i) { return *a[i]; }
+
 // Header.Hash of the headers idx[0 .. m) (all header_fused_ok) into out + 32 * idx[j].  ctx->mu held.
-int header_hashes_fused(tmed_ctx *c, const tmed_header *headers, const std::vector<size_t> &idx, uint8_t *out) {
+template <class HA>
+int header_hashes_fused(tmed_ctx *c, HA headers, const std::vector<size_t> &idx, uint8_t *out,
+                        uint8_t *d_keep = nullptr) {
   const size_t m = idx.size();
   if (m > 0x0fffffffu) return TMED_EINVAL;
   const size_t o_roots = m * (size_t)kHdrRecBytes;  // a multiple of 256
@@ -585,11 +604,12 @@ int header_hashes_fused(tmed_ctx *c, const tmed_header *headers, const std::vect
   hipError_t e = c->stage.ensure(o_roots + 32 * m, o_roots + 32 * m);
   if (e != hipSuccess) return map_err(e);
   uint8_t *h = c->stage.host(), *d = c->stage.dev();
-  host_for(m, pack_threads(m * 32), [&](size_t j) { header_pack(headers[idx[j]], h + j * kHdrRecBytes); });
+  host_for(m, pack_threads(m * 32), [&](size_t j) { header_pack(item(headers, idx[j]), h + j * kHdrRecBytes); });
   e = hipMemcpyAsync(d, h, o_roots, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipEventRecord(c->ev0, s);
   e = launch(e, header_hash_kernel, 16 * m, s, (const uint8_t *)d, (uint32_t)m, d + o_roots);
   if (e == hipSuccess) e = hipEventRecord(c->ev1, s);
+  if (e == hipSuccess && d_keep) e = hipMemcpyAsync(d_keep, d + o_roots, 32 * m, hipMemcpyDeviceToDevice, s);
   if (e == hipSuccess) e = hipMemcpyAsync(h + o_roots, d + o_roots, 32 * m, hipMemcpyDeviceToHost, s);
   const int rc = finish_call(c, s, e, &c->last_ms);
   if (rc != TMED_OK) return rc;
@@ -597,19 +617,29 @@ int header_hashes_fused(tmed_ctx *c, const tmed_header *headers, const std::vect
   return TMED_OK;
 }
 
-int commit_hashes_locked(tmed_ctx *c, const tmed_commit *commits, size_t n, const std::vector<uint32_t> &counts,
-                         const std::vector<size_t> &base, size_t N, uint8_t *out) {
+// shared: stage into the arena tmed_ctx::vb_commit instead of tmed_ctx::stage, with the raw flags beside
+// the other arrays, and report where they and the roots lie on the device: they stay there after the
+// call (no other routine uses that arena), for the median kernels and block_check_kernel of the same
+// tmed_validate_blocks call.
+template <class CA>
+int commit_hashes_locked(tmed_ctx *c, CA commits, size_t n, const std::vector<uint32_t> &counts,
+                         const std::vector<size_t> &base, size_t N, uint8_t *out, CommitArena *shared = nullptr) {
   const MerkleLevels plan(counts);
   (void)hipSetDevice(c->device);
   hipStream_t s = c->stream;
-  const CsigLayout lay(N, n);
+  const CsigLayout lay(N, n, shared != nullptr);
   int rc = ensure_nodes(c, plan);
   if (rc != TMED_OK) return rc;
-  hipError_t e = c->stage.ensure(lay.total, lay.total);
+  Staged &arena = shared ? c->vb_commit : c->stage;
+  hipError_t e = arena.ensure(lay.total, lay.total);
   if (e != hipSuccess) return map_err(e);
-  uint8_t *h = c->stage.host(), *d = c->stage.dev();
+  uint8_t *h = arena.host(), *d = arena.dev();
+  if (shared) {
+    shared->flags = d + lay.flags, shared->addr = d + lay.addr, shared->roots = d + lay.roots;
+    shared->sec = (const int64_t *)(d + lay.sec), shared->nanos = (const int32_t *)(d + lay.nanos);
+  }
   host_for(n, pack_threads(N), [&](size_t i) {
-    if (counts[i]) commit_pack(commits[i], h, lay, base[i]);
+    if (counts[i]) commit_pack(item(commits, i), h, lay, base[i]);
   });
   if (N) {  // one copy per array kind
     e = hipMemcpyAsync(d + lay.sig, h + lay.sig, 64 * N, hipMemcpyHostToDevice, s);
@@ -617,6 +647,7 @@ int commit_hashes_locked(tmed_ctx *c, const tmed_commit *commits, size_t n, cons
     if (e == hipSuccess) e = hipMemcpyAsync(d + lay.meta, h + lay.meta, 4 * N, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d + lay.nanos, h + lay.nanos, 4 * N, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d + lay.addr, h + lay.addr, 20 * N, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && shared) e = hipMemcpyAsync(d + lay.flags, h + lay.flags, N, hipMemcpyHostToDevice, s);
   }
   if (e == hipSuccess) e = hipEventRecord(c->ev0, s);
   e = launch(e, commit_leaf_kernel, N, s, (const uint32_t *)(d + lay.meta), (const int64_t *)(d + lay.sec),
@@ -628,6 +659,41 @@ int commit_hashes_locked(tmed_ctx *c, const tmed_commit *commits, size_t n, cons
   rc = finish_call(c, s, e, &c->last_ms);
   if (rc != TMED_OK) return rc;
   memcpy(out, h + lay.roots, n * 32);
+  return TMED_OK;
+}
+
+// tmed_commit_hashes once its pointers are checked: the scan of every commit, the device part under
+// the context's lock (held: the caller holds it already and has collected the submitted windows),
+// the hashes of the commits with ok = 0 zeroed.
+template <class CA>
+int commit_hashes_body(tmed_ctx *c, CA commits, size_t n, uint8_t *out, uint8_t *ok, bool held,
+                       CommitArena *shared = nullptr) {
+  std::vector<uint32_t> counts(n);
+  std::vector<size_t> base(n);
+  size_t N = 0, all = 0;
+  for (size_t i = 0; i < n; i++) all += item(commits, i).n_sigs;
+  std::vector<int> scan(n);
+  host_for(n, pack_threads(all), [&](size_t i) { scan[i] = commit_scan(item(commits, i)); });
+  for (size_t i = 0; i < n; i++) {
+    const int r = scan[i];
+    if (r < 0) return r;
+    ok[i] = (uint8_t)r;
+    base[i] = N;
+    if (item(commits, i).n_sigs > 0xffffffffu) return TMED_EINVAL;
+    counts[i] = r ? (uint32_t)item(commits, i).n_sigs : 0;  // a commit with ok = 0 contributes no leaves
+    N += counts[i];
+    if (N > 0xffffffffu) return TMED_EINVAL;
+  }
+  if (shared) {  // each commit's first signature in the arena's arrays (a commit with ok = 0 is not staged)
+    shared->base.assign(n, (size_t)-1);
+    for (size_t i = 0; i < n; i++)
+      if (counts[i] || item(commits, i).n_sigs == 0) shared->base[i] = base[i];
+  }
+  const int rc = held ? commit_hashes_locked(c, commits, n, counts, base, N, out, shared)
+                      : locked(c, /*collect=*/true, [&] { return commit_hashes_locked(c, commits, n, counts, base, N, out); });
+  if (rc != TMED_OK) return rc;
+  for (size_t i = 0; i < n; i++)
+    if (!ok[i]) memset(out + 32 * i, 0, 32);
   return TMED_OK;
 }
 
@@ -800,7 +866,7 @@ bool header_pointers_ok(const tmed_header &h) {
 }
 
 int valset_hashes_locked(tmed_ctx *c, const uint8_t *pubkeys, const int64_t *powers, const uint32_t *set_off,
-                         size_t n_sets, uint8_t *out) {
+                         size_t n_sets, uint8_t *out, uint8_t *d_keep) {
   const size_t N = set_off[n_sets];
   std::vector<uint32_t> counts(n_sets);
   for (size_t t = 0; t < n_sets; t++) counts[t] = set_off[t + 1] - set_off[t];
@@ -818,6 +884,7 @@ int valset_hashes_locked(tmed_ctx *c, const uint8_t *pubkeys, const int64_t *pow
              dev_nodes(c));
   if (e == hipSuccess) e = build_levels(c, plan, s);
   if (e == hipSuccess) e = emit_roots(c, plan, (uint8_t *)c->d_out.p, s);
+  if (e == hipSuccess && d_keep) e = hipMemcpyAsync(d_keep, c->d_out.p, n_sets * 32, hipMemcpyDeviceToDevice, s);
   if (e == hipSuccess) e = hipMemcpyAsync(out, c->d_out.p, n_sets * 32, hipMemcpyDeviceToHost, s);
   return finish_call(c, s, e);
 }
@@ -825,7 +892,7 @@ int valset_hashes_locked(tmed_ctx *c, const uint8_t *pubkeys, const int64_t *pow
 // ValidatorSet.Hash of n_sets validator sets given as structs: their keys and powers are packed
 // straight into the context's pinned staging (h_a / h_b: one pass over the callers' arrays, and the
 // copies to the device run from page-locked memory), then hashed as above.
-int valsets_hashes_locked(tmed_ctx *c, const tmed_valset *const *sets, size_t n_sets, uint8_t *out) {
+int valsets_hashes_locked(tmed_ctx *c, const tmed_valset *const *sets, size_t n_sets, uint8_t *out, uint8_t *d_keep) {
   std::vector<uint32_t> set_off(n_sets + 1, 0);
   for (size_t s = 0; s < n_sets; s++) {
     if (sets[s]->n > 0xffffffffu - set_off[s]) return TMED_EINVAL;
@@ -843,35 +910,67 @@ int valsets_hashes_locked(tmed_ctx *c, const tmed_valset *const *sets, size_t n_
     memcpy(pubs + 32 * (size_t)set_off[s], sets[s]->pubkeys, 32 * sets[s]->n);
     memcpy(pows + set_off[s], sets[s]->powers, 8 * sets[s]->n);
   });
-  return valset_hashes_locked(c, pubs, pows, set_off.data(), n_sets, out);
+  return valset_hashes_locked(c, pubs, pows, set_off.data(), n_sets, out, d_keep);
+}
+
+// Commit.Hash and Data.Hash as tmed_commit_hashes / tmed_txs_hashes compute them, for a caller that
+// holds ctx->mu and has collected the submitted windows (validate.hip); n, n_blocks >= 1.
+int commit_hashes_held(tmed_ctx *c, const tmed_commit *const *commits, size_t n, uint8_t *out, uint8_t *ok,
+                       CommitArena *shared) {
+  return commit_hashes_body(c, commits, n, out, ok, /*held=*/true, shared);
+}
+int txs_hashes_held(tmed_ctx *c, const uint8_t *txs, const uint64_t *tx_off, const uint32_t *block_off, size_t n_blocks,
+                    uint8_t *out, uint8_t *d_keep) {
+  if (!tx_off || !block_off) return TMED_EINVAL;
+  std::vector<uint32_t> counts;
+  const int rc = forest_counts(block_off, n_blocks, tx_off, txs, counts);
+  if (rc != TMED_OK) return rc;
+  return roots_from_host_leaves_locked(c, txs, tx_off, block_off[n_blocks], counts, out, /*txs=*/true, d_keep);
 }
 
 // Eligible headers (header_fused_ok) through header_hash_kernel, the others through host-encoded
 // leaves and the generic leaf and level kernels; ok = 0 and a zeroed hash where ValidatorsHash is
 // empty (Header.Hash returns nil, types/block.go:441-443).
-int header_hashes_locked(tmed_ctx *c, const tmed_header *headers, size_t n, uint8_t *out, uint8_t *ok) {
+// d_keep (n x 32, device): also receives the hashes there, the headers of the fused route first, in
+// their order, then the others in theirs; row_of[i] (n entries) tells header i's row.
+template <class HA>
+static int header_hashes_any(tmed_ctx *c, HA headers, size_t n, uint8_t *out, uint8_t *ok, uint8_t *d_keep,
+                         uint32_t *row_of) {
   std::vector<size_t> fused, rest;
-  for (size_t i = 0; i < n; i++) (header_fused_ok(headers[i]) ? fused : rest).push_back(i);
+  for (size_t i = 0; i < n; i++) (header_fused_ok(item(headers, i)) ? fused : rest).push_back(i);
+  if (row_of) {
+    for (size_t j = 0; j < fused.size(); j++) row_of[fused[j]] = (uint32_t)j;
+    for (size_t j = 0; j < rest.size(); j++) row_of[rest[j]] = (uint32_t)(fused.size() + j);
+  }
   int rc = TMED_OK;
-  if (!fused.empty()) rc = header_hashes_fused(c, headers, fused, out);
+  if (!fused.empty()) rc = header_hashes_fused(c, headers, fused, out, d_keep);
   if (rc == TMED_OK && !rest.empty()) {
     std::vector<uint8_t> leaves, roots(32 * rest.size());
     std::vector<uint64_t> off;
     leaves.reserve(rest.size() * 200);
     off.reserve(rest.size() * 14 + 1);
     off.push_back(0);
-    for (const size_t i : rest) header_leaves(headers[i], leaves, off);
+    for (const size_t i : rest) header_leaves(item(headers, i), leaves, off);
     const std::vector<uint32_t> counts(rest.size(), 14);
-    rc = roots_from_host_leaves_locked(c, leaves.data(), off.data(), off.size() - 1, counts, roots.data());
+    rc = roots_from_host_leaves_locked(c, leaves.data(), off.data(), off.size() - 1, counts, roots.data(), /*txs=*/false,
+                                       d_keep ? d_keep + 32 * fused.size() : nullptr);
     if (rc == TMED_OK)
       for (size_t j = 0; j < rest.size(); j++) memcpy(out + 32 * rest[j], roots.data() + 32 * j, 32);
   }
   if (rc != TMED_OK) return rc;
   for (size_t i = 0; i < n; i++) {
-    ok[i] = headers[i].hash_lens[2] != 0;
+    ok[i] = item(headers, i).hash_lens[2] != 0;
     if (!ok[i]) memset(out + 32 * i, 0, 32);
   }
   return TMED_OK;
+}
+int header_hashes_locked(tmed_ctx *c, const tmed_header *headers, size_t n, uint8_t *out, uint8_t *ok, uint8_t *d_keep,
+                         uint32_t *row_of) {
+  return header_hashes_any(c, headers, n, out, ok, d_keep, row_of);
+}
+int header_hashes_locked(tmed_ctx *c, const tmed_header *const *headers, size_t n, uint8_t *out, uint8_t *ok,
+                         uint8_t *d_keep, uint32_t *row_of) {
+  return header_hashes_any(c, headers, n, out, ok, d_keep, row_of);
 }
 
 }  // namespace tmed
@@ -881,30 +980,7 @@ extern "C" {
 int tmed_commit_hashes(tmed_ctx *c, const tmed_commit *commits, size_t n, uint8_t *out, uint8_t *ok) {
   if (!c || (n && (!commits || !out || !ok))) return TMED_EINVAL;
   if (n == 0) return TMED_OK;
-  return guarded([&] {
-    std::vector<uint32_t> counts(n);
-    std::vector<size_t> base(n);
-    size_t N = 0, all = 0;
-    for (size_t i = 0; i < n; i++) all += commits[i].n_sigs;
-    std::vector<int> scan(n);
-    host_for(n, pack_threads(all), [&](size_t i) { scan[i] = commit_scan(commits[i]); });
-    for (size_t i = 0; i < n; i++) {
-      const int r = scan[i];
-      if (r < 0) return r;
-      ok[i] = (uint8_t)r;
-      base[i] = N;
-      if (commits[i].n_sigs > 0xffffffffu) return TMED_EINVAL;
-      counts[i] = r ? (uint32_t)commits[i].n_sigs : 0;  // a commit with ok = 0 contributes no leaves
-      N += counts[i];
-      if (N > 0xffffffffu) return TMED_EINVAL;
-    }
-    const int rc =
-        locked(c, /*collect=*/true, [&] { return commit_hashes_locked(c, commits, n, counts, base, N, out); });
-    if (rc != TMED_OK) return rc;
-    for (size_t i = 0; i < n; i++)
-      if (!ok[i]) memset(out + 32 * i, 0, 32);
-    return TMED_OK;
-  });
+  return guarded([&] { return commit_hashes_body(c, commits, n, out, ok, /*held=*/false); });
 }
 
 int tmed_txs_hashes(tmed_ctx *c, const uint8_t *txs, const uint64_t *tx_off, const uint32_t *block_off,

@@ -232,6 +232,8 @@ void tmed_destroy(tmed_ctx *c) {
                     &c->d_zip, &c->d_kbases})
     b->release();
   c->stage.release();
+  c->vb_commit.release();
+  c->d_vb.release();
   if (c->vote_ev) hipEventDestroy(c->vote_ev);
   if (c->ev_lookup) hipEventDestroy(c->ev_lookup);
   c->h_kup.release();

@@ -2057,3 +2057,238 @@ func (e *Engine) VerifyLightClientAttacks(reqs []LcaRequest) ([]LcaResult, error
 	}
 	return out, nil
 }
+
+// ---- validateBlock (state/validation.go:15-151 over Block.ValidateBasic, types/block.go:55-106) ----
+
+// Outcome codes of ValidateBlocks: the first check that fails, in the reference's order (see
+// tmed25519.h, which cites the reference lines of each).
+const (
+	VbOK                 = C.TMED_VB_OK
+	VbHeaderBasic        = C.TMED_VB_HEADER_BASIC
+	VbCommitBasic        = C.TMED_VB_COMMIT_BASIC
+	VbLastCommitHash     = C.TMED_VB_LAST_COMMIT_HASH
+	VbDataHash           = C.TMED_VB_DATA_HASH
+	VbEvidenceBasic      = C.TMED_VB_EVIDENCE_BASIC
+	VbEvidenceHash       = C.TMED_VB_EVIDENCE_HASH
+	VbVersion            = C.TMED_VB_VERSION
+	VbChainID            = C.TMED_VB_CHAIN_ID
+	VbHeightInitial      = C.TMED_VB_HEIGHT_INITIAL
+	VbHeight             = C.TMED_VB_HEIGHT
+	VbLastBlockID        = C.TMED_VB_LAST_BLOCK_ID
+	VbAppHash            = C.TMED_VB_APP_HASH
+	VbConsensusHash      = C.TMED_VB_CONSENSUS_HASH
+	VbLastResultsHash    = C.TMED_VB_LAST_RESULTS_HASH
+	VbValidatorsHash     = C.TMED_VB_VALIDATORS_HASH
+	VbNextValidatorsHash = C.TMED_VB_NEXT_VALIDATORS_HASH
+	VbInitialHasSigs     = C.TMED_VB_INITIAL_HAS_SIGS
+	// VbLastCommit: state.LastValidators.VerifyCommit failed; BlockResult.Commit holds its outcome.
+	VbLastCommit         = C.TMED_VB_LAST_COMMIT
+	VbProposerSize       = C.TMED_VB_PROPOSER_SIZE
+	VbProposerUnknown    = C.TMED_VB_PROPOSER_UNKNOWN
+	VbTimeNotAfter       = C.TMED_VB_TIME_NOT_AFTER
+	VbTimeNotMedian      = C.TMED_VB_TIME_NOT_MEDIAN
+	VbTimeNotGenesis     = C.TMED_VB_TIME_NOT_GENESIS
+	VbHeightBelowInitial = C.TMED_VB_HEIGHT_BELOW_INITIAL
+	VbEvidenceOverflow   = C.TMED_VB_EVIDENCE_OVERFLOW
+	// VbGoPath: the flat fields cannot decide the check the replay reached: the caller runs
+	// validateBlock itself for this block.
+	VbGoPath = C.TMED_VB_GO_PATH
+	// The bits of BlockState.Known and BlockResult.Skipped.
+	VbKnowAppHash         uint32 = C.TMED_VB_KNOW_APP_HASH
+	VbKnowConsensusHash   uint32 = C.TMED_VB_KNOW_CONSENSUS_HASH
+	VbKnowLastResultsHash uint32 = C.TMED_VB_KNOW_LAST_RESULTS_HASH
+	VbKnowValidators      uint32 = C.TMED_VB_KNOW_VALIDATORS
+	VbKnowNextValidators  uint32 = C.TMED_VB_KNOW_NEXT_VALIDATORS
+	VbKnowAll             uint32 = C.TMED_VB_KNOW_ALL
+)
+
+// BlockState is a flat copy of the fields of state.State that validateBlock reads.  Known is a mask
+// of VbKnow*: a check whose bit is clear is skipped and reported in BlockResult.Skipped (a blocksync
+// window validated ahead of ApplyBlock does not have those values); the caller evaluates the skipped
+// checks in Go before it relies on the block, and first of all when a skipped check orders before a
+// failure's code.
+type BlockState struct {
+	VersionBlock, VersionApp        uint64
+	ChainID                         string
+	InitialHeight, LastBlockHeight  int64
+	LastBlockID                     BlockID
+	LastBlockTimeSeconds            int64
+	LastBlockTimeNanos              int32
+	AppHash                         []byte
+	ConsensusHash                   []byte // types.HashConsensusParams(state.ConsensusParams), 32 bytes
+	LastResultsHash                 []byte
+	Validators, NextValidators      *ValSet // nil allowed where the set's bit is clear
+	LastValidators                  *ValSet
+	EvidenceMaxBytes                int64
+	Known                           uint32
+}
+
+// BlockRequest is one block against one state.  LinkPrev (requests 1..): the state's last block hash,
+// height and time are the previous request's block's, its Header.Hash computed on the device in the
+// same call; the PartSetHeader half of LastBlockID still comes from State.LastBlockID.
+type BlockRequest struct {
+	Header           *HeaderData
+	LastCommit       *CommitData // nil: a nil LastCommit (CommitBasicOK must be false)
+	State            *BlockState
+	Txs              [][]byte
+	Evidence         []EvidenceItem // indexes into ValidateBlocks' evidence argument, or marshalled bytes
+	EvidenceByteSize int64          // block.Evidence.ByteSize()
+	HeaderBasicOK    bool           // Header.ValidateBasic() == nil
+	CommitBasicOK    bool           // LastCommit != nil && LastCommit.ValidateBasic() == nil
+	EvidenceBasicBad int32          // -1, or the index of the first evidence whose ValidateBasic fails
+	LinkPrev         bool
+}
+
+// BlockResult is one block's outcome; the caller builds the reference's error value from it
+// (INTEGRATION.md).
+type BlockResult struct {
+	Code          int
+	Skipped       uint32
+	Hash          []byte // the computed value of the hash codes (nil where none)
+	Commit        Result // VbLastCommit: the failing VerifyCommit's outcome
+	MedianSeconds int64  // VbTimeNotMedian: state.MedianTime
+	MedianNanos   int32
+	Idx           int32 // VbEvidenceBasic
+	ProposerIdx   int32 // the proposer's index in State.Validators, -1 where not looked up or not found
+	Verified      uint32
+}
+
+// ValidateBlocks is validateBlock for many blocks in one call (tmed_validate_blocks): the hashes of
+// Block.ValidateBasic, the validator-set hashes, the compares and the proposer lookup on the device,
+// VerifyCommit through the commit seam, MedianTime by its kernels, and the reference's checks replayed
+// in its order.  evidence holds the DuplicateVoteEvidence of all blocks (nil: none).  An error means
+// "take the original Go path".
+func (e *Engine) ValidateBlocks(reqs []BlockRequest, evidence *DupEvidenceData) ([]BlockResult, error) {
+	n := len(reqs)
+	if n == 0 {
+		return nil, nil
+	}
+	a := e.getArena()
+	defer e.putArena(a)
+	creqs := (*[1 << 24]C.tmed_block_request)(a.alloc(uintptr(n) * unsafe.Sizeof(C.tmed_block_request{})))[:n:n]
+	hs := (*[1 << 24]C.tmed_header)(a.alloc(uintptr(n) * unsafe.Sizeof(C.tmed_header{})))[:n:n]
+	cs := (*[1 << 24]C.tmed_commit)(a.alloc(uintptr(n) * unsafe.Sizeof(C.tmed_commit{})))[:n:n]
+	ss := (*[1 << 24]C.tmed_block_state)(a.alloc(uintptr(n) * unsafe.Sizeof(C.tmed_block_state{})))[:n:n]
+	vs := (*[1 << 24]C.tmed_valset)(a.alloc(uintptr(3*n) * unsafe.Sizeof(C.tmed_valset{})))[: 3*n : 3*n]
+	// one C copy per distinct *ValSet, *BlockState and *CommitData: the library hashes, stages and
+	// resolves each set once per call
+	seenV := make(map[*ValSet]*C.tmed_valset, 3)
+	seenS := make(map[*BlockState]*C.tmed_block_state, n)
+	seenC := make(map[*CommitData]*C.tmed_commit, n)
+	nv, ns := 0, 0
+	valset := func(v *ValSet) *C.tmed_valset {
+		if v == nil {
+			return nil
+		}
+		cv, ok := seenV[v]
+		if !ok {
+			vs[nv] = a.valset(v)
+			cv = &vs[nv]
+			seenV[v] = cv
+			nv++
+		}
+		return cv
+	}
+	var txs, opaque []byte
+	var items []int64
+	txOff, opOff := []uint64{0}, []uint64{0}
+	blockOff, listOff := []uint32{0}, []uint32{0}
+	flag := func(b bool) C.uint8_t {
+		if b {
+			return 1
+		}
+		return 0
+	}
+	for i := range reqs {
+		r := &reqs[i]
+		if r.Header == nil || r.State == nil || (r.LastCommit == nil && r.CommitBasicOK) {
+			return nil, errors.New("tmedgpu: ValidateBlocks: nil header, state or commit")
+		}
+		hs[i] = a.headerC(r.Header)
+		var cc *C.tmed_commit
+		if r.LastCommit != nil {
+			var ok bool
+			if cc, ok = seenC[r.LastCommit]; !ok {
+				cs[i] = a.commitC(r.LastCommit, nil)
+				cc = &cs[i]
+				seenC[r.LastCommit] = cc
+			}
+		}
+		st, ok := seenS[r.State]
+		if !ok {
+			s := r.State
+			ss[ns] = C.tmed_block_state{version_block: C.uint64_t(s.VersionBlock), version_app: C.uint64_t(s.VersionApp),
+				chain_id: a.cstring(s.ChainID), chain_id_len: C.uint32_t(len(s.ChainID)),
+				initial_height: C.int64_t(s.InitialHeight), last_block_height: C.int64_t(s.LastBlockHeight),
+				last_block_id: a.blockID(&s.LastBlockID), last_block_time_seconds: C.int64_t(s.LastBlockTimeSeconds),
+				last_block_time_nanos: C.int32_t(s.LastBlockTimeNanos), app_hash: a.bytes(s.AppHash),
+				app_hash_len: C.uint32_t(len(s.AppHash)), consensus_hash: a.bytes(s.ConsensusHash),
+				last_results_hash: a.bytes(s.LastResultsHash), last_results_hash_len: C.uint32_t(len(s.LastResultsHash)),
+				validators: valset(s.Validators), next_validators: valset(s.NextValidators),
+				last_validators: valset(s.LastValidators), evidence_max_bytes: C.int64_t(s.EvidenceMaxBytes),
+				known: C.uint32_t(s.Known)}
+			if s.Known&VbKnowConsensusHash != 0 && len(s.ConsensusHash) != 32 {
+				return nil, errors.New("tmedgpu: ValidateBlocks: ConsensusHash must be 32 bytes")
+			}
+			st = &ss[ns]
+			seenS[r.State] = st
+			ns++
+		}
+		var flags C.uint32_t
+		if r.LinkPrev {
+			flags = C.TMED_VB_LINK_PREV
+		}
+		creqs[i] = C.tmed_block_request{header: &hs[i], last_commit: cc, state: st,
+			evidence_byte_size: C.int64_t(r.EvidenceByteSize), header_basic_ok: flag(r.HeaderBasicOK),
+			commit_basic_ok: flag(r.CommitBasicOK), evidence_basic_bad: C.int32_t(r.EvidenceBasicBad), flags: flags}
+		for _, tx := range r.Txs {
+			txs = append(txs, tx...)
+			txOff = append(txOff, uint64(len(txs)))
+		}
+		blockOff = append(blockOff, uint32(len(txOff)-1))
+		for _, it := range r.Evidence {
+			if it.Opaque != nil {
+				items = append(items, int64(-len(opOff)))
+				opaque = append(opaque, it.Opaque...)
+				opOff = append(opOff, uint64(len(opaque)))
+			} else {
+				items = append(items, int64(it.Index))
+			}
+		}
+		listOff = append(listOff, uint32(len(items)))
+	}
+	txs = append(txs, make([]byte, 8)...) // the device readers may touch the last dword
+	opaque = append(opaque, make([]byte, 8)...)
+	if evidence == nil {
+		evidence = NewDupEvidenceData(0)
+	}
+	ce := (*C.tmed_dup_evidence)(a.alloc(unsafe.Sizeof(C.tmed_dup_evidence{})))
+	*ce = a.dupEvidenceC(evidence)
+	var citems *C.int64_t
+	if len(items) > 0 {
+		citems = a.i64(items)
+	}
+	batch := (*C.tmed_block_batch)(a.alloc(unsafe.Sizeof(C.tmed_block_batch{})))
+	*batch = C.tmed_block_batch{n: C.size_t(n), blocks: &creqs[0], txs: a.bytes(txs), tx_off: a.u64(txOff),
+		block_off: a.u32(blockOff), ev: ce, items: citems, list_off: a.u32(listOff), opaque: a.bytes(opaque),
+		opaque_off: a.u64(opOff)}
+	res := make([]C.tmed_block_result, n)
+	if rc := C.tmed_validate_blocks(e.ctx, batch, &res[0]); rc != 0 {
+		return nil, errors.New(C.GoString(C.tmed_strerror(rc)))
+	}
+	out := make([]BlockResult, n)
+	for i := range res {
+		o := BlockResult{Code: int(res[i].code), Skipped: uint32(res[i].skipped), MedianSeconds: int64(res[i].median_seconds),
+			MedianNanos: int32(res[i].median_nanos), Idx: int32(res[i].idx), ProposerIdx: int32(res[i].proposer_idx),
+			Verified: uint32(res[i].verified)}
+		o.Commit = toResults([]C.tmed_commit_result{res[i].commit})[0]
+		if hl := int(res[i].hash_len); hl > 0 {
+			o.Hash = make([]byte, hl)
+			for k := 0; k < hl; k++ {
+				o.Hash[k] = byte(res[i].hash[k])
+			}
+		}
+		out[i] = o
+	}
+	return out, nil
+}

@@ -6,7 +6,7 @@ over the gfx950 C ABI in ``include/tmed25519.h``.
 """
 from ._native import LIB_PATH, TmedError, lib  # noqa: F401
 from .engine import Engine, PinnedBuffer, pack_messages  # noqa: F401
-from .state import median_times  # noqa: F401
+from .state import median_times, validate_blocks  # noqa: F401
 from .votes import Vote, VoteRequest, verify_votes  # noqa: F401
 from .evidence import (DuplicateVoteEvidence, EvidenceRequest, evidence_bytes, evidence_hashes,  # noqa: F401
                        verify_duplicate_votes)

@@ -176,6 +176,7 @@ EXPORTED_SYMBOLS = [
     "tmed_verify_duplicate_votes_host",
     "tmed_byzantine_validators", "tmed_byzantine_validators_host", "tmed_lca_kernel_times",
     "tmed_verify_light_client_attacks", "tmed_verify_light_client_attacks_with",
+    "tmed_validate_blocks", "tmed_validate_blocks_with", "tmed_validate_kernel_ms", "tmed_validate_stats",
     "tmed_verify_commits_multi", "tmed_blocksync_verify_multi", "tmed_window_stats", "tmed_b_window_bits", "tmed_keyset_b_window_bits", "tmed_keyset_a_window_bits", "tmed_keyset_comb_entry", "tmed_seam_phase_us",
     "tmed_verify_batch_zip215", "tmed_verify_batch_zip215_device", "tmed_zip215_set_seed", "tmed_zip215_stats",
     "tmed_host_alloc", "tmed_host_free", "tmed_host_register", "tmed_host_unregister",
